@@ -95,6 +95,42 @@ def clip_base(B, k):
     return 0 if B > 16 else B * k
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs: array bytes written in all (the .npy headers add a few hundred)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, frames, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: what the timed path returned to its caller in the last timed step — the [B, H, W, 3] fp32 frames that
+    eng.interpolate wrote — as .npy files, so that two builds run with the same arguments (identical seeded inputs and weights) can
+    be compared output for output.  Written whole as ``frames.npy`` when it fits the budget; otherwise ``frame0.npy`` (task 0 in
+    full, when it fits half the budget) and ``frames_sample.npy``: the RGB values [n, 3] at n pixel positions of the flattened
+    [B * H * W] grid drawn with torch.randint from a CPU generator seeded DUMP_SAMPLE_SEED and sorted — the same positions for the
+    same arguments.  Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+
+    B, H, W, C = frames.shape
+    written = {}
+
+    def save(name, t):
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+        return a.nbytes
+
+    if frames.numel() * 4 <= budget:
+        save("frames", frames)
+        return written
+    left = budget
+    if H * W * C * 4 <= budget // 2:
+        left -= save("frame0", frames[0])
+    n = min(B * H * W, left // (C * 4))
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+    idx = torch.randint(0, B * H * W, (n,), generator=g, dtype=torch.int64).sort().values
+    save("frames_sample", frames.reshape(B * H * W, C)[idx.to(frames.device)])
+    return written
+
+
 def host_cpu_model():
     try:
         import subprocess
@@ -1099,6 +1135,7 @@ def main_single_process(args):
     if errors:
         raise errors[0]
     elapsed = times["t1"] - times["t0"]
+    dumped = dump_outputs(args.dump_outputs, bufs[0][(K - 1) & 1][:B]) if args.dump_outputs else None
 
     # roofline leg: the dominant kernel's launch duration by HIP events on device 0's stream (the library's tracer is
     # process-wide, so this pass runs device 0 alone: K steps, no collective)
@@ -1120,6 +1157,8 @@ def main_single_process(args):
     res = result_line(args, N, elapsed, traced, rep, eng0, f"all_gather_v ({mode}; in place, comm streams), overlapped" if gather else "none")
     res["config"]["launch"] = f"one process, {N} device thread(s) (multidev.py; weights broadcast over RCCL)"
     res["config"]["reserved_cus"] = reserve
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     _lib.load().vfi_set_reserved_cus(0)
     if not args.no_strong:
         try:
@@ -1345,6 +1384,9 @@ def main():
     ap.add_argument("--dry-run-ranks", type=int, default=0,
                     help="plumbing check on ONE GPU: run the full N-rank control flow (weight broadcast, reserve trials, gather, strong leg, watchdog) "
                          "as N gloo ranks that all use device 0; the numbers in the line mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames the last timed step computed (rank 0 / device 0) to DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed, seeded pixel sample when the step's output is larger): see dump_outputs()")
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.device_threads:
         return main_single_process(args)
@@ -1519,6 +1561,7 @@ def main():
         clock["timed"] = clock_summary(probe.finish(), "resconv_c64")
     # tasks 0 / B/2 / B-1 of the LAST timed step's launch
     last_frames = [outs[(K - 1) & 1][j].cpu() for j in par_slots] if rank == 0 and oracle_frames is not None else None
+    dumped = dump_outputs(args.dump_outputs, outs[(K - 1) & 1]) if rank == 0 and args.dump_outputs else None
     gather_cost = None
     if world > 1:
         ctl_dev = dev if args.backend == "nccl" else "cpu"
@@ -1584,6 +1627,8 @@ def main():
         if cpu_base is not None and "error" not in cpu_base:
             res["cpu_baseline"] = cpu_base
         res["config"]["launch"] = "one process per GPU (torch.distributed)" if world > 1 else "one process, one GPU"
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         # what the communicator itself reports (not the --gpus argument): ranks and backend of the default process group
         res["n_ranks_seen_by_rccl"] = dist.get_world_size() if world > 1 else 1
         res["collective_backend"] = (dist.get_backend() + (" (= RCCL on ROCm)" if dist.get_backend() == "nccl" else "")) if world > 1 else "none (N = 1)"

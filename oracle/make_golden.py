@@ -38,9 +38,28 @@ def demo_pair(name0, name1, y0, x0, h, w):
     return torch.stack(out)  # [2,h,w,3]
 
 
+def live_check_vector(ref):
+    """tests/test_oracle_golden.py::test_oracle_bit_exact_vs_live_reference's own input (weights seed 7, a 70x90 smooth pair, t = 0.3)
+    through the reference's IFNet("4.7"), with the host signature that decides whether the stored output pins bit-exactly."""
+    from oracle import golden_stats
+
+    sd = synth.rife47_synth_state_dict(7)
+    net = ref.IFNet("4.7")
+    net.load_state_dict(sd, strict=True)
+    net.eval()
+    fr = synth.smooth_frames(2, 70, 90, seed=9, shift=3.0)
+    i0 = fr[0:1].permute(0, 3, 1, 2).contiguous()
+    i1 = fr[1:2].permute(0, 3, 1, 2).contiguous()
+    with torch.inference_mode():
+        out = net(i0, i1, torch.tensor([0.3]).view(1, 1, 1, 1), [8, 4, 2, 1], False, False)
+    np.savez_compressed(os.path.join(OUT, "rife47_live_check.npz"), frames=fr.numpy(), timestep=np.float32(0.3), out=out.numpy())
+    golden_stats.write_host_signature(os.path.join(OUT, "rife47_live_check_host.json"))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = ref_import.rife_arch()
+    live_check_vector(ref)
     sd = synth.rife47_synth_state_dict(1234)
     net = ref.IFNet("4.7")
     net.load_state_dict(sd, strict=True)

@@ -58,3 +58,46 @@ def costvol_out(one, two):
     out = np.empty((n, 81, h, w), np.float32)
     _launch("costvol_out", a.shape, n * h * w, [a.ctypes.data, b.ctypes.data, out.ctypes.data])
     return out
+
+
+# ---- stored digests: the prebuilt kernels' outputs on seeded inputs, so that the C oracle is pinned to them where oracle/_ref is absent
+DIGESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ref_kernels_digests.json")
+
+
+def digest(arr):
+    """SHA-256 of a float32 array's shape and bytes: equal digests <=> np.array_equal (bit for bit)."""
+    import hashlib
+
+    a = np.ascontiguousarray(arr, np.float32)
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def seeded_cases(softsplat_shapes, costvol_shapes):
+    """(op, shape, inputs) of tests/test_oracle_m2m_ops.py's comparison with the prebuilt kernels: one numpy generator (seed 5) drawn
+    in this order — softsplat shapes with N*H*W <= 200000 (flow N(0, 9 px), one NaN source), costvol shapes with N*H*W <= 5000."""
+    rng = np.random.default_rng(5)
+    for shp in softsplat_shapes:
+        if shp[0] * shp[2] * shp[3] > 200000:
+            continue
+        a = rng.random(shp, dtype=np.float32)
+        f = (rng.standard_normal((shp[0], 2, shp[2], shp[3])) * 9).astype(np.float32)
+        f[0, 0, 1, 1] = np.nan
+        yield "softsplat_out", shp, (a, f)
+    for shp in costvol_shapes:
+        if shp[0] * shp[2] * shp[3] > 5000:
+            continue
+        yield "costvol_out", shp, (rng.standard_normal(shp).astype(np.float32), rng.standard_normal(shp).astype(np.float32))
+
+
+def write_digests():
+    """python oracle/ref_kernels.py — needs the prebuilt oracle/_ref (build() where the reference checkout exists)."""
+    assert available(), "oracle/_ref is not built"
+    ss, cv = shapes("softsplat_out"), shapes("costvol_out")
+    cases = [[op, list(shp), digest(globals()[op](*inputs))] for op, shp, inputs in seeded_cases(ss, cv)]
+    with open(DIGESTS, "w") as f:
+        json.dump({"softsplat_out_shapes": [list(s) for s in ss], "costvol_out_shapes": [list(s) for s in cv], "cases": cases}, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    write_digests()

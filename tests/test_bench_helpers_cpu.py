@@ -55,3 +55,27 @@ def test_golden_tolerance_follows_the_host_signature(tmp_path):
     assert golden_stats.golden_tol(str(other)) == golden_stats.CROSS_HOST_TOL      # written elsewhere: the cross-host spread
     assert golden_stats.golden_tol(str(tmp_path / "missing.json")) == golden_stats.CROSS_HOST_TOL
     assert golden_stats.CROSS_HOST_TOL <= 2e-4 < 1e-3
+
+
+def test_dump_outputs_whole_or_seeded_sample(tmp_path):
+    import numpy as np
+
+    frames = torch.rand(3, 20, 30, 3)
+    assert bench.dump_outputs(str(tmp_path / "whole"), frames) == {"frames.npy": [3, 20, 30, 3]}
+    assert np.array_equal(np.load(tmp_path / "whole" / "frames.npy"), frames.numpy())
+    # over budget: frame 0 in full (it fits half the budget) + a seeded sample of pixels that fills the rest; same positions every run
+    budget = 2 * 20 * 30 * 3 * 4          # 2 of the 3 frames: frame 0 is exactly half of it
+    got = bench.dump_outputs(str(tmp_path / "a"), frames, budget=budget)
+    assert got == {"frame0.npy": [20, 30, 3], "frames_sample.npy": [(budget - 20 * 30 * 3 * 4) // 12, 3]}
+    sizes = sum(os.path.getsize(tmp_path / "a" / f) for f in got)
+    assert sizes <= budget + 2 * 256 and all(np.load(tmp_path / "a" / f).dtype == np.float32 for f in got)
+    assert np.array_equal(np.load(tmp_path / "a" / "frame0.npy"), frames[0].numpy())
+    bench.dump_outputs(str(tmp_path / "b"), frames, budget=budget)
+    assert np.array_equal(np.load(tmp_path / "a" / "frames_sample.npy"), np.load(tmp_path / "b" / "frames_sample.npy"))
+    g = torch.Generator(device="cpu").manual_seed(bench.DUMP_SAMPLE_SEED)
+    idx = torch.randint(0, 3 * 20 * 30, ((budget - 20 * 30 * 3 * 4) // 12,), generator=g).sort().values
+    assert np.array_equal(np.load(tmp_path / "a" / "frames_sample.npy"), frames.reshape(-1, 3)[idx].numpy())
+    # the 1080p default (32 x 1080 x 1920 x 3 fp32 = 796 MB) stays within 64 MB
+    H, W, B = 1080, 1920, 32
+    n = (bench.DUMP_BUDGET_BYTES - H * W * 12) // 12
+    assert H * W * 12 <= bench.DUMP_BUDGET_BYTES // 2 and H * W * 12 + n * 12 <= bench.DUMP_BUDGET_BYTES < 64 * 10 ** 6 and n < B * H * W

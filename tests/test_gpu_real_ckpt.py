@@ -2,7 +2,9 @@
 ``rife47.pth`` / ``rife49.pth`` / ``M2M.pth`` / ``film_net_fp32.pt`` (vfi_utils.py:14-40,112-133; film/__init__.py:74), so every
 other parity test runs on seeded synthetic weights.  These tests ACTIVATE BY THEMSELVES for each file found at the place the
 reference's loader keeps it — ``comfyui-frame-interpolation_amd/ckpts/<model>/<file>`` (config.yaml: ckpts_path, the same contract as
-the reference's vfi_utils.py:84-85) — or under ``$VFI_REAL_CKPTS/<model>/<file>``, and skip with a reason otherwise.
+the reference's vfi_utils.py:84-85) — or under ``$VFI_REAL_CKPTS/<model>/<file>``.  Where a file is absent, the same case runs on a
+seeded stand-in of the file's architecture, saved under the file's name as a ``torch.save`` state dict (a format the package's loaders
+accept), so that the node path and the gate below run on every machine; each case prints which of the two it ran on.
 
 For every file present, on the real 1080p pair (bocchi, tests/golden/bocchi_pair_u8.npz) and the 540p anime pair
 (rife47_node_anime540.npz): the node class of this package against the reference semantics executed on the host CPU —
@@ -10,7 +12,8 @@ For every file present, on the real 1080p pair (bocchi, tests/golden/bocchi_pair
     also goes through this package's strict key / shape check (= ``load_state_dict(strict=True)``, rife/__init__.py:115-118);
   * FILM: the artifact itself — ``torch.jit.load(path)`` run on the CPU exactly as the reference node runs it
     (film/__init__.py:74-76,34) — which is also the first meeting of this package's TorchScript-state-dict key mapping
-    (film.py:_load_state_dict) with the real file.
+    (film.py:_load_state_dict) with the real file; a stand-in (a state dict, not a TorchScript program) against the in-repo oracle
+    (oracle/film_oracle.py, bit-exact with the reference's Interpolator, oracle/VALIDATION_FILM.log).
 Gate: per-pixel |d| <= 1e-3 on every value of every new frame (north_star)."""
 import os
 
@@ -22,6 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_CKPTS = os.path.join(ROOT, "comfyui-frame-interpolation_amd", "ckpts")
 FILES = [("rife", "rife47.pth"), ("rife", "rife49.pth"), ("m2m", "M2M.pth"), ("film", "film_net_fp32.pt")]
+STAND_IN_SEEDS = {"rife47.pth": 4711, "rife49.pth": 4912, "M2M.pth": 4711, "film_net_fp32.pt": 4711}
 
 
 def find_ckpt(model, name):
@@ -30,6 +34,17 @@ def find_ckpt(model, name):
         if os.path.isfile(p) and os.path.getsize(p) > 1 << 20:
             return p
     return None
+
+
+def stand_in(model, name, directory):
+    """A seeded synthetic checkpoint of ``name``'s architecture (rife49.pth: arch 4.7, as the real file), saved as ``directory/model/name``."""
+    from cfi_amd import synth
+
+    make = {"rife": synth.rife47_synth_state_dict, "m2m": synth.m2m_synth_state_dict, "film": synth.film_synth_state_dict}[model]
+    os.makedirs(os.path.join(directory, model), exist_ok=True)
+    path = os.path.join(directory, model, name)
+    torch.save(make(STAND_IN_SEEDS[name]), path)
+    return path
 
 
 def pairs(golden_dir):
@@ -45,10 +60,14 @@ def _gate(got, want, what):
 
 
 @pytest.mark.parametrize("model,name", FILES)
-def test_real_checkpoint_node_vs_reference_semantics(hip_lib, golden_dir, monkeypatch, model, name, oracle_threads):
+def test_real_checkpoint_node_vs_reference_semantics(hip_lib, golden_dir, monkeypatch, tmp_path, model, name, oracle_threads):
     path = find_ckpt(model, name)
-    if path is None:
-        pytest.skip(f"{name} not found under {PKG_CKPTS}/{model}/ or $VFI_REAL_CKPTS/{model}/ (no network here: drop the real file in to activate)")
+    real = path is not None
+    if real:
+        print(f"{name}: real file {path}")
+    else:
+        path = stand_in(model, name, str(tmp_path))
+        print(f"{name}: not found under {PKG_CKPTS}/{model}/ or $VFI_REAL_CKPTS/{model}/ — seeded stand-in {path}")
     from cfi_amd import ckpt
 
     ckpt.clear_engine_cache()
@@ -97,19 +116,27 @@ def test_real_checkpoint_node_vs_reference_semantics(hip_lib, golden_dir, monkey
         import cfi_amd.film as FM
 
         monkeypatch.setattr(FM, "load_file_from_github_release", lambda model_type, ckpt_: path)
-        ts = torch.jit.load(path, map_location="cpu").eval()
+        if real:
+            ts = torch.jit.load(path, map_location="cpu").eval()
+        else:
+            from oracle import film_oracle
+
+            sd = FM._load_state_dict(path)
         for what, fr in pairs(golden_dir):
             (out,) = FM.FILM_VFI().vfi(name, fr, multiplier=2)
             x = fr.permute(0, 3, 1, 2).contiguous()
-            with torch.no_grad():
-                want = ts(x[0:1], x[1:2], x.new_full((1, 1), 0.5)).clamp(0, 1).float().permute(0, 2, 3, 1)
+            if real:
+                with torch.no_grad():
+                    want = ts(x[0:1], x[1:2], x.new_full((1, 1), 0.5)).clamp(0, 1).float().permute(0, 2, 3, 1)
+            else:
+                want = film_oracle.film_vfi(sd, fr, multiplier=2)[1:2]
             _gate(out[1:2], want, f"{name} x2 {what}")
     ckpt.clear_engine_cache()
 
 
 def test_activation_with_stand_in_files(hip_lib, tmp_path):
-    """The machinery itself, exercised: seeded stand-ins for rife47.pth and M2M.pth under $VFI_REAL_CKPTS make exactly those two
-    cases run (and pass: same code path a real file takes), the other two stay skipped with their reason."""
+    """The machinery itself, exercised: files for rife47.pth and M2M.pth dropped under $VFI_REAL_CKPTS are found and used for exactly
+    those two cases (and pass: same code path a real file takes); the other two run on their generated stand-ins and say so."""
     import subprocess
     import sys
 
@@ -120,8 +147,10 @@ def test_activation_with_stand_in_files(hip_lib, tmp_path):
     torch.save(synth.rife47_synth_state_dict(4711), tmp_path / "rife" / "rife47.pth")
     torch.save(synth.m2m_synth_state_dict(4711), tmp_path / "m2m" / "M2M.pth")
     env = {k: v for k, v in os.environ.items() if k != "VFI_REAL_CKPTS"}
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-rs", "-k", "node_vs_reference_semantics"],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-s", "-m", "gpu", "-rs", "-k", "node_vs_reference_semantics",
+                        "--basetemp", str(tmp_path / "inner")],
                        env=dict(env, VFI_REAL_CKPTS=str(tmp_path)), capture_output=True, text=True, timeout=1200)
-    tail = r.stdout[-3000:]
-    assert r.returncode == 0 and "2 passed, 2 skipped" in tail, tail + r.stderr[-2000:]
-    assert "rife49.pth not found" in tail and "film_net_fp32.pt not found" in tail
+    out = r.stdout
+    assert r.returncode == 0 and "4 passed" in out[-3000:] and "skipped" not in out[-3000:], out[-3000:] + r.stderr[-2000:]
+    assert f"rife47.pth: real file {tmp_path / 'rife' / 'rife47.pth'}" in out and f"M2M.pth: real file {tmp_path / 'm2m' / 'M2M.pth'}" in out, out[-3000:]
+    assert "rife49.pth: not found" in out and "film_net_fp32.pt: not found" in out, out[-3000:]
