@@ -173,6 +173,35 @@ int vfi_costvol9x9(const float* one_dev, int one_cs, const float* two_dev, int t
 /* one/two are channel windows (pixel strides one_cs/two_cs); two_swap != 0 reads `two` from the partner image
  * n^1 of a batch of direction pairs (the reference runs the decoder on (a,b) and on (b,a), M2M_arch.py:521-546). */
 
+/* ---- the reference's remaining custom ops, NCHW (the drop-in ops backend cfi_amd.ops) ------------------- */
+/* Every `*_strides` argument is a host array of 4 element strides (n, c, y, x) of that NCHW operand, so channel slices are
+ * read in place.  fp32 only; nothing is allocated and nothing synchronises. */
+
+/* Separable adaptive convolution: out[n,c,y,x] = sum_fy sum_fx in[n,c,y+fy,x+fx] * ver[n,fy,y,x] * hor[n,fx,y,x], K taps
+ * each way; `in` is pre-padded (Hin >= Ho + K - 1, Win >= Wo + K - 1).  Replaces sepconv_func.forward / sepconv_out,
+ * vfi_models/ops/cupy_ops/sepconv.py:86-117,155-199 (plain fp32 sums of row sums instead of the Kahan-compensated sum). */
+int vfi_sepconv(const float* in_dev, const long long* in_strides, const float* ver_dev, const long long* ver_strides,
+                const float* hor_dev, const long long* hor_strides, float* out_dev, const long long* out_strides, int N, int C,
+                int Hin, int Win, int Ho, int Wo, int K, void* stream);
+
+/* AdaCoF forward: out[n,c,i,j] = sum_{k,l < F} weight[n,kF+l,i,j] * bilinear(input[n,c], i + k*dilation + alpha,
+ * j + l*dilation + beta) with alpha/beta = offset_i/offset_j[n,kF+l,i,j], corners clamped to the image, the integer part
+ * (int)alpha truncated toward zero.  Contiguous NCHW operands; Ho/Wo must satisfy the reference's asserts.  Replaces
+ * FunctionAdaCoF.forward / kernel_AdaCoF_updateOutput, vfi_models/ops/cupy_ops/adacof.py:5-65,259-333. */
+int vfi_adacof(const float* input_dev, const float* weight_dev, const float* offset_i_dev, const float* offset_j_dev,
+               float* out_dev, int N, int C, int H, int W, int F, int dilation, int Ho, int Wo, void* stream);
+
+/* PWC correlation: out[n, 9*(dy+4)+(dx+4), y, x] = (1/C) sum_c a[n,c,y,x] * b[n,c,y+dy,x+dx], |dy|,|dx| <= 4, b outside the
+ * image = 0; out is a contiguous [N,81,H,W] tensor.  Replaces _FunctionCorrelation.forward / kernel_Correlation_rearrange +
+ * kernel_Correlation_updateOutput, vfi_models/ops/cupy_ops/correlation.py:4-102,232-296 (one kernel, no padded copies). */
+int vfi_correlation81(const float* a_dev, const long long* a_strides, const float* b_dev, const long long* b_strides,
+                      float* out_dev, int N, int C, int H, int W, void* stream);
+
+/* Distance transform of contiguous [N,H,W] data: tmp = min(diam2, min_j data[row][j] + (x-j)^2) along rows, then
+ * out = sqrt(min(diam2, min_i tmp[i][col] + (y-i)^2)) along columns.  H, W <= 16384; tmp must not alias data or out.
+ * Replaces the two kernel_dt launches + the final sqrt of batch_edt, vfi_models/ops/cupy_ops/batch_edt.py:10-100. */
+int vfi_edt(const float* data_dev, float* tmp_dev, float* out_dev, int N, int H, int W, float diam2, void* stream);
+
 /* ---- M2M network building blocks (vfi_models/m2m/M2M_arch.py) -------------------------------- */
 
 /* Generalised layer object: kind 0 = nn.Conv2d(Cin, Cout, k, stride, padding) with (k,stride) in
