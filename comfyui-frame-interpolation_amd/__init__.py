@@ -13,6 +13,7 @@ _LAZY = {
     "IFRNet_VFI": ("ifrnet", "IFRNet_VFI"),
     "GMFSS_Fortuna_VFI": ("gmfss", "GMFSS_Fortuna_VFI"),
     "IFUnet_VFI": ("ifunet", "IFUnet_VFI"),
+    "CAIN_VFI": ("cain", "CAIN_VFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -26,6 +27,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f"{__name__}.{mod}"), attr)
     if name == "NODE_CLASS_MAPPINGS":
         return _node_class_mappings()
+    if name == "NODE_DISPLAY_NAME_MAPPINGS":
+        return dict(_DISPLAY_NAMES, **dict(EXTRA_NODES[n] for n in extra_nodes()))
     raise AttributeError(name)
 
 
@@ -38,6 +41,11 @@ def _node_class_mappings():
     from .rife import RIFE_VFI
     from .schedule import MakeInterpolationStateList
 
+    extra = {}
+    if "cain" in extra_nodes():
+        from .cain import CAIN_VFI
+
+        extra["CAIN VFI"] = CAIN_VFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -46,10 +54,27 @@ def _node_class_mappings():
         "GMFSS Fortuna VFI": GMFSS_Fortuna_VFI,
         "IFUnet VFI": IFUnet_VFI,
         "Make Interpolation State List": MakeInterpolationStateList,
+        **extra,
     }
 
 
-NODE_DISPLAY_NAME_MAPPINGS = {
+# Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
+# list such as "cain".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
+EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)")}
+
+
+def extra_nodes():
+    from .ckpt import load_config
+
+    spec = str(load_config().get("extra_nodes", "") or "")
+    names = [s.strip().lower() for s in spec.split(",") if s.strip()]
+    unknown = [n for n in names if n not in EXTRA_NODES]
+    if unknown:
+        raise ValueError(f"extra_nodes / VFI_EXTRA_NODES: unknown node(s) {unknown}; known: {sorted(EXTRA_NODES)}")
+    return names
+
+
+_DISPLAY_NAMES = {
     "RIFE VFI": "RIFE VFI (MI355X HIP; rife47 / rife49)",
     "FILM VFI": "FILM VFI (MI355X HIP)",
     "M2M VFI": "M2M VFI (MI355X HIP)",

@@ -175,6 +175,16 @@ PROTOTYPES = {
     "vfi_test_film_schedule": (C.c_int, [C.c_int, c_int_p, C.c_int]),
     "vfi_test_linspace01": (C.c_int, [C.c_int, C.c_void_p]),
     "vfi_film_debug_read_flow": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "vfi_cain_frame_in": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vfi_cain_frame_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_channel_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vfi_cain_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
+    "vfi_cain_destroy": (None, [C.c_void_p]),
+    "vfi_cain_forward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "vfi_cain_release_workspace": (C.c_int, [C.c_void_p]),
+    "vfi_cain_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_m2m_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
     "vfi_m2m_destroy": (None, [C.c_void_p]),
     "vfi_m2m_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

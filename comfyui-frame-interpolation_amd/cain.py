@@ -1,0 +1,180 @@
+"""CAIN VFI node — host-side mirror of the reference's ``CAIN_VFI`` over the HIP library.
+
+Node shape follows vfi_models/cain/__init__.py:11-64; the frame loop is vfi_utils.generic_frame_loop in its non-timestep mode
+(vfi_utils.py:161-170,202-206): per pair, the m-1 new frames come from recursive bisection, every model call interpolating between
+two frames it has already (the pair's frames or earlier model outputs, kept in full precision on the device).  The output order and
+the model calls are planned in schedule.bisect_output_plan; here each pair's tree is evaluated level by level, the calls of a level
+batched into one vfi_cain_forward (csrc/cain_net.hip: the whole CAIN forward, ~320 launches per call).  No clamp.
+"""
+import ctypes as C
+import typing
+
+import torch
+
+from . import _lib
+from .cain_spec import cain_shapes, load_file
+from .ckpt import begin_call, cached_engine, end_call, load_file_from_github_release
+from .dist import all_gather_frames, world
+from .schedule import InterpolationStateList, bisect_output_plan, shard_tasks
+
+MODEL_TYPE = "cain"
+CKPT_NAMES = ["pretrained_cain.pth"]
+MAX_BATCH = 8        # model calls per vfi_cain_forward (about 215 MB of workspace per call at 1080p)
+
+
+class CainEngine:
+    """Device-resident CAIN: ``forward(frames0, frames1)`` = ``model(f0, f1)[0]`` for a batch of pairs in one library call."""
+
+    def __init__(self, state_dict, device=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("CAIN VFI (HIP): no GPU visible; this node has no CPU fallback")
+        self.lib = _lib.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
+        keys = list(cain_shapes().keys())
+        tensors = [state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in keys]
+        ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
+        numels = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
+        self.handle = self.lib.vfi_cain_create(ptrs, numels, len(keys))
+        if not self.handle:
+            raise RuntimeError("vfi_cain_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.vfi_cain_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def release_workspace(self):
+        _lib.check(self.lib.vfi_cain_release_workspace(self.handle), "vfi_cain_release_workspace")
+
+    def workspace_bytes(self):
+        return int(self.lib.vfi_cain_workspace_bytes(self.handle)) if getattr(self, "handle", None) else 0
+
+    def forward(self, frames0, frames1, out=None):
+        """frames0 / frames1: sequences of N [H,W,C>=3] fp32 contiguous device tensors (not written) -> out [N,H,W,3]."""
+        n = len(frames0)
+        assert n == len(frames1) and n > 0
+        H, W, Cc = frames0[0].shape
+        for f in list(frames0) + list(frames1):
+            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        if out is None:
+            out = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.device)
+        p0 = (C.c_void_p * n)(*[f.data_ptr() for f in frames0])
+        p1 = (C.c_void_p * n)(*[f.data_ptr() for f in frames1])
+        _lib.check(self.lib.vfi_cain_forward(self.handle, p0, p1, n, Cc, H, W, out.data_ptr(), _lib.stream_ptr()), "vfi_cain_forward")
+        return out
+
+
+def eval_pair(engine, f0, f1, calls, max_batch=MAX_BATCH):
+    """Evaluate one pair's bisection tree: calls = [(pos, lo, hi), ...] of schedule.bisect_calls.  Returns {pos: [H,W,3] device tensor},
+    positions 0 and 1 being f0 / f1.  The calls of one tree level only read positions of earlier levels, so each level is one batch."""
+    have = {0: f0, 1: f1}
+    level = {0: 0, 1: 0}
+    by_level = {}
+    for pos, lo, hi in calls:
+        level[pos] = max(level[lo], level[hi]) + 1
+        by_level.setdefault(level[pos], []).append((pos, lo, hi))
+    for lv in sorted(by_level):
+        todo = by_level[lv]
+        for s in range(0, len(todo), max_batch):
+            part = todo[s:s + max_batch]
+            out = engine.forward([have[lo] for _, lo, _ in part], [have[hi] for _, _, hi in part])
+            for k, (pos, _, _) in enumerate(part):
+                have[pos] = out[k]
+    return have
+
+
+def run_plan(engine, frames, plan, tasks, name="CAIN VFI"):
+    """frames: [N,H,W,C] host tensor; plan / tasks from schedule.bisect_output_plan.  Pairs are block-partitioned over ranks, the
+    new frames all-gathered.  Host side as the M2M node (hostpipe.py): frames uploaded once ahead of the compute stream, new and
+    pass-through frames written into their rows of the output tensor in the background."""
+    if not plan:   # list multiplier of zeros: the reference fails in torch.cat of an empty list (vfi_utils.py:386)
+        raise RuntimeError(f"{name}: every frame pair was dropped (multiplier 0 everywhere) - nothing to output")
+    dev = engine.device
+    frames = frames[..., :3]
+    H, W = frames.shape[1:3]
+    rank, ws = world()
+    lo, hi = shard_tasks(tasks, rank, ws)
+    counts = [sum(len(t[1]) for t in tasks[slice(*shard_tasks(tasks, r, ws))]) for r in range(ws)]
+    mine = tasks[lo:hi]
+
+    from .hostpipe import OutputWriter, Uploader
+    main = torch.cuda.current_stream(dev)
+    wr = OutputWriter(len(plan), H, W, dev)
+    new_row = {}
+    for i, (kind, idx) in enumerate(plan):
+        if kind == "src":
+            wr.put_host(i, frames[idx])
+        else:
+            new_row[idx] = i
+    order = sorted({f for pair, _, _ in mine for f in (pair, pair + 1)})
+    item_of = {f: i for i, f in enumerate(order)}
+    first_new = sum(counts[:rank])
+    local = [] if ws > 1 else None
+    in_flight = []      # (event, tensor): outputs the writer still reads
+    up = Uploader(frames, order, dev, main, depth=min(4, len(order)) or 1) if order else None
+    try:
+        pos, released = 0, 0
+        for pair, outs, calls in mine:
+            f0, f1 = up.get(item_of[pair]), up.get(item_of[pair + 1])
+            have = eval_pair(engine, f0, f1, calls)
+            for p in outs:
+                if ws == 1:
+                    in_flight.append((wr.put_dev(new_row[first_new + pos], have[p]), have[p]))
+                else:
+                    local.append(have[p])
+                pos += 1
+            del have
+            in_flight = [(e, t) for e, t in in_flight if e is not None and not e.query()]
+            while released < item_of[pair + 1]:      # frames before pair+1 are never needed again (pairs ascend)
+                up.release(released)
+                released += 1
+        if ws > 1:
+            loc = torch.stack(local) if local else torch.empty((0, H, W, 3), dtype=torch.float32, device=dev)
+            new = all_gather_frames(loc, counts)
+            for k in range(new.shape[0]):
+                wr.put_dev(new_row[k], new[k])
+    finally:
+        if up is not None:
+            up.close()
+    return wr.finish()
+
+
+class CAIN_VFI:
+    @classmethod
+    def INPUT_TYPES(s):
+        return {
+            "required": {
+                "ckpt_name": (CKPT_NAMES,),
+                "frames": ("IMAGE",),
+                "clear_cache_after_n_frames": ("INT", {"default": 10, "min": 1, "max": 1000}),
+                "multiplier": ("INT", {"default": 2, "min": 2, "max": 1000}),
+            },
+            "optional": {"optional_interpolation_states": ("INTERPOLATION_STATES",)},
+        }
+
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "vfi"
+    CATEGORY = "ComfyUI-Frame-Interpolation/VFI"
+
+    def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames: typing.SupportsInt = 1,
+            multiplier: typing.SupportsInt = 2, optional_interpolation_states: InterpolationStateList = None, **kwargs):
+        # (vfi_utils.assert_batch_size with vfi_name = "CAIN_VFI".replace('_', ' ').replace('VFI', ''), vfi_utils.py:145-147,351)
+        assert len(frames) >= 2, (f"VFI model CAIN  requires at least 2 frames to work with, only found {frames.shape[0]}. "
+                                  "Please check the frame input using PreviewImage.")
+        plan, tasks = bisect_output_plan(len(frames), multiplier, optional_interpolation_states)
+        model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
+        engine, cached = cached_engine(MODEL_TYPE, model_path, lambda: CainEngine(load_file(model_path)))
+        try:
+            begin_call(engine, tuple(frames.shape[1:3]))
+            return (run_plan(engine, frames, plan, tasks),)
+        finally:
+            if cached:
+                torch.cuda.synchronize(engine.device)
+            end_call(engine, cached)

@@ -30,7 +30,7 @@ namespace vfi {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// EXT: extended feature set (replicate padding, per-channel PReLU / sigmoid, post affine, interleaved
+// EXT: extended feature set (replicate / reflect padding, per-channel PReLU / sigmoid, post affine, interleaved
 // transposed-conv store) compiled as a separate instantiation; the RIFE path runs EXT = false.
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
@@ -88,9 +88,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         const int pix = idx / Q, q = idx - pix * Q;
         const int py = pix / TWI, px = pix - py * TWI;
         const int iy = iy0 + py, ix = ix0 + px;
-        if (EXT && a.pad_replicate) {
+        if (EXT && a.pad_mode) {
             gok[i] = idx < NITEM;
-            const int cy = min(max(iy, 0), a.Hin - 1), cx = min(max(ix, 0), a.Win - 1);
+            const int cy = pad_index(iy, a.Hin, a.pad_mode), cx = pad_index(ix, a.Win, a.pad_mode);
             goff[i] = gok[i] ? (cy * a.Win + cx) * pstr + q * qstr : 0;
         } else {
             gok[i] = idx < NITEM && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
@@ -329,7 +329,7 @@ static int launch_t(ConvArgs a, hipStream_t s, const char* name) {
                 name, a.Cout_p, WN * NT * 32);
     dim3 grid(a.N * a.tiles_x * a.tiles_y, GROUPED ? a.Cout_p / 32 : a.Cout_p / (WN * NT * 32));
     TraceScope ts(name, s);
-    if (a.pad_replicate || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2)
+    if (a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2)
         hipLaunchKernelGGL((conv_mfma_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, true>), grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL((conv_mfma_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, false>), grid, dim3(256), 0, s, a);

@@ -57,7 +57,7 @@ struct Conv2Geom {
     static constexpr int NBW = (NB_INSTR + 3) / 4;
 };
 
-// EXT = the layer uses the extended feature set (replicate padding, per-channel PReLU / sigmoid, post affine,
+// EXT = the layer uses the extended feature set (replicate / reflect padding, per-channel PReLU / sigmoid, post affine,
 // interleaved transposed-conv store): compiled separately so the RIFE / FILM hot path carries none of its branches.
 // MASKED (2x2 taps only; round 6): the layer is "nearest-neighbour up-sampling x2, then a 2x2 'same' convolution" (FILM's Fusion,
 // film_arch.py:282-292) computed on the LOW-resolution input: output parity (py, px) of the up-sampled image reads low-resolution pixels
@@ -112,8 +112,8 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
             const int pix = idx / Q, q = idx - pix * Q;
             const int py = pix / TWI, px = pix - py * TWI;
             const int iy = iy0 + py, ix = ix0 + px;
-            if (EXT && a.pad_replicate) {  // edge clamp instead of the descriptor's zero fill
-                const int cy = min(max(iy, 0), a.Hin - 1), cx = min(max(ix, 0), a.Win - 1);
+            if (EXT && a.pad_mode) {  // edge clamp (replicate) or mirror (reflect) instead of the descriptor's zero fill
+                const int cy = pad_index(iy, a.Hin, a.pad_mode), cx = pad_index(ix, a.Win, a.pad_mode);
                 avoff[i] = pix < G::NPIX ? ((cy * a.Win + cx) * pstr + q * qstr) * 4 : (int)0x80000000;
             } else {
                 const bool ok = pix < G::NPIX && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
@@ -597,7 +597,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         p.ksplit = ks, p.split_stride = (long)slice;
         {
             TraceScope ts(name, s);
-            // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_replicate implies EXT)
+            // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_mode implies EXT)
             hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>), dim3(T, ny, ks), dim3(256), G::LDS_BYTES, s, p);
             VFI_CHECK_HIP(hipGetLastError());
         }
@@ -626,7 +626,7 @@ static int launch2_masked(const ConvArgs& a, hipStream_t s, const char* name) {
 
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED>
 static int launch2_t(const ConvArgs& a, hipStream_t s, const char* name) {
-    const bool ext = a.pad_replicate || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
+    const bool ext = a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
     return ext ? launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, true>(a, s, name)
                : launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, false>(a, s, name);
 }

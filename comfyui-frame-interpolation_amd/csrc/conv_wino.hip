@@ -333,8 +333,8 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
             const int sl = sp ^ wino_key(py);
             const int code = sp < G::NITEM ? (sl & 1) : -1;
             const int iy = c.Ry0 - 1 + py, ix = c.Rx0 - 1 + ((sl >> 1) - py * PW);
-            const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);       // replicate padding = edge clamp
-            const bool ok = code >= 0 && c.valid && (a.pad_replicate || (cy == iy && cx == ix));
+            const int cy = pad_index(iy, H, a.pad_mode), cx = pad_index(ix, W, a.pad_mode);   // replicate: edge clamp, reflect: mirror
+            const bool ok = code >= 0 && c.valid && (a.pad_mode || (cy == iy && cx == ix));
             avtab[i * 64 + ol] = ok ? ((cy * W + cx) * a.in_cs + (code & 1) * 4) * 4 : (int)0x80000000;
         }
     };

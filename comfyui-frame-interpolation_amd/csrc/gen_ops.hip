@@ -327,7 +327,8 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
                                int pad_mode, const int* chan_map, int Cin_phys, const float* prelu_host) {
     const bool conv_ok = kind == 0 && ((k == 3 && (stride == 1 || stride == 2)) || (k == 2 && stride == 2) || (k == 1 && stride == 1));
     const bool deconv_ok = kind == 1 && k == 4 && stride == 2;
-    if (!w_host || Cout <= 0 || Cin <= 0 || !(conv_ok || deconv_ok) || Cin_phys % 8 || Cin_phys < Cin || pad_mode < 0 || pad_mode > 1) {
+    if (!w_host || Cout <= 0 || Cin <= 0 || !(conv_ok || deconv_ok) || Cin_phys % 8 || Cin_phys < Cin || pad_mode < 0 || pad_mode > 2 ||
+        (pad_mode == 2 && !(kind == 0 && k == 3))) {
         set_error("vfi_conv_create_ex: unsupported layer (kind=%d Cout=%d Cin=%d k=%d stride=%d pad_mode=%d Cin_phys=%d)", kind, Cout,
                   Cin, k, stride, pad_mode, Cin_phys);
         return nullptr;
@@ -408,6 +409,7 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
 int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs, int N,
                         int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs, void* stream) {
     VFI_REQUIRE(c && in_dev && out_dev && N > 0 && Hin > 0 && Win > 0, "vfi_conv_forward_ex: bad arguments");
+    VFI_REQUIRE(c->pad_mode != 2 || (Hin >= 2 && Win >= 2), "vfi_conv_forward_ex: reflection padding needs at least 2x2 pixels (%dx%d)", Hin, Win);
     VFI_REQUIRE(in_cs >= c->Cin_p && in_cs % 4 == 0 && ((uintptr_t)in_dev & 15) == 0,
                 "vfi_conv_forward_ex: input window must hold %d channels, 16-byte aligned (in_cs=%d)", c->Cin_p, in_cs);
     VFI_REQUIRE(act != 3 || c->prelu, "vfi_conv_forward_ex: act 3 (per-channel PReLU) needs slopes given at create time");
@@ -436,7 +438,7 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
     a.split_ok = 1;
     a.post_scale = post_scale;
     a.post_shift = post_shift;
-    a.pad_replicate = c->pad_mode;
+    a.pad_mode = c->pad_mode;
     char name[80];
     if (c->kind == 1) {
         VFI_REQUIRE(!res_dev, "vfi_conv_forward_ex: residual not supported for transposed convs");

@@ -94,6 +94,14 @@ int softsplat4_launch(const float* in, const float* flow, float* out, int N, int
 
 constexpr int kMaxDevices = 16;   // devices one process may drive (per-device caches are indexed by the HIP device id)
 
+// Row / column read for halo index i of an n-pixel image in pad_mode 1 (replicate) or 2 (reflect: -1 -> 1, n -> n - 2, as
+// torch.nn.ReflectionPad2d(1); needs n >= 2).  The result is clamped into [0, n) in both modes: halo pixels of tiles that hang over
+// the image's end (whose outputs are never stored) must still read inside it.
+__host__ __device__ __forceinline__ int pad_index(int i, int n, int mode) {
+    if (mode == 2) i = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+    return min(max(i, 0), n - 1);
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
 
@@ -121,7 +129,7 @@ struct ConvArgs {
                            //    [N][2][4*Hout][4*Wout][4] (channel c of Cout/4 -> plane c/4, component c%4);
                            //    2 (grouped only): plain transposed-conv output, NHWC [N][2*Hout][2*Wout][out_cs]
     int out_planes;        // out_mode 1: planes per image of the planar4 output (0 = 2)
-    int pad_replicate;     // 0: zero padding; 1: replicate (edge clamp) padding of the input
+    int pad_mode;          // 0: zero padding; 1: replicate (edge clamp); 2: reflect (ReflectionPad2d(1)) padding of the input
     const float* prelu;    // [Cout_p] per-channel negative slopes (act == 3)
     float post_scale, post_shift;  // y = act(...) * post_scale + post_shift  (post_scale == 0 means "not set" = 1, 0)
     int split_ok;          // caller: the launcher may cut K over several workgroups (split-K; generic layer objects only — the

@@ -7,6 +7,7 @@ Mirrors — by behaviour, not by text — the reference's
 Known answers for these are in SURVEY.md Appendix A11 and tests/test_schedule.py.
 """
 import typing
+from fractions import Fraction
 
 
 class InterpolationStateList:
@@ -121,6 +122,53 @@ def generic_output_plan(n_frames, multiplier, states=None):
     else:
         raise NotImplementedError(f"multipiler of {type(multiplier)}")
     return plan, tasks
+
+
+def bisect_calls(n):
+    """The model calls of the reference's recursive non-timestep mode for n new frames between two frames
+    (``non_timestep_inference``, vfi_utils.py:161-170): returns ``(outputs, calls)`` with ``outputs`` the positions in (0, 1) of
+    the n frames it returns, in order, and ``calls`` = ``[(pos, lo, hi), ...]`` in the reference's call order — the model
+    interpolates the frames at ``lo`` and ``hi`` (0 / 1 = the pair's frames, else an earlier call's output) into ``pos``.
+    Positions are exact Fractions.  Every call is a different position: with even n the middle frame is computed but not output."""
+    if n < 1:
+        raise ValueError(f"bisection for {n} new frames: the reference recurses without end (RecursionError)")
+    calls = []
+
+    def rec(lo, hi, k):
+        mid = (lo + hi) / 2
+        calls.append((mid, lo, hi))
+        if k == 1:
+            return [mid]
+        first, second = rec(lo, mid, k // 2), rec(mid, hi, k // 2)
+        return first + [mid] + second if k % 2 else first + second
+
+    return rec(Fraction(0), Fraction(1), n), calls
+
+
+def bisect_output_plan(n_frames, multiplier, states=None):
+    """Output order of ``generic_frame_loop`` in non-timestep mode (``use_timestep=False``, vfi_utils.py:149-389; CAIN and
+    Sepconv).  Every pair outputs m - 1 new frames as in timestep mode, so ``plan`` is :func:`generic_output_plan`'s (list
+    multipliers, skip lists, m == 0 dropping a pair); ``tasks`` = ``[(pair_idx, outputs, calls), ...]`` from :func:`bisect_calls`,
+    whose outputs are numbered k = 0.. in order.  A pair the model would run with m == 1 (an int multiplier below 2, or a list entry
+    of 1) raises ValueError up front: the reference's recursion never ends there."""
+    plan, tasks = generic_output_plan(n_frames, multiplier, states)
+    if type(multiplier) == int and multiplier < 2:
+        skipped = [states is not None and states.is_frame_skipped(p) for p in range(n_frames - 1)]
+        if not all(skipped):
+            raise ValueError(f"multiplier {multiplier}: the reference's non-timestep frame loop recurses without end for fewer than "
+                             "one new frame per pair")
+    elif type(multiplier) == list:
+        ms = list(map(int, multiplier)) + [2] * max(0, n_frames - len(multiplier) - 1)
+        skipped = states is not None and states.is_frame_skipped(0)
+        for pair in range(n_frames - 1):
+            if ms[pair] == 1 and not skipped:
+                raise ValueError(f"multiplier 1 of pair {pair}: the reference's non-timestep frame loop recurses without end "
+                                 "(RecursionError) for a pair with no new frame")
+    out = []
+    for pair, ts in tasks:
+        outputs, calls = bisect_calls(len(ts))
+        out.append((pair, outputs, calls))
+    return plan, out
 
 
 def shard_tasks(tasks, rank, world):

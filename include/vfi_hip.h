@@ -206,7 +206,7 @@ int vfi_edt(const float* data_dev, float* tmp_dev, float* out_dev, int N, int H,
 
 /* Generalised layer object: kind 0 = nn.Conv2d(Cin, Cout, k, stride, padding) with (k,stride) in
  * {(3,1),(3,2),(2,2),(1,1)}: k=3 pads 1 — pad_mode 0 zeros (M2M_arch.py:589-602), 1 replicate (the "conv(3,replpad)"
- * of Basic, :228-260); k=2/s=2 pads 0 ("sconv(2)" after evenize, :205-226 — sizes must be even).
+ * of Basic, :228-260), 2 reflect (ReflectionPad2d(1) + Conv2d, CAIN's ConvNorm, cain/common.py:26-45; inputs >= 2x2); k=2/s=2 pads 0 ("sconv(2)" after evenize, :205-226 — sizes must be even).
  * kind 1 = nn.ConvTranspose2d(Cin, Cout, 4, 2, 1) (deconv(), :605-618), weights [Cin,Cout,4,4].
  * prelu_host (nullable): Cout per-channel PReLU slopes, applied by act 3. */
 vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_host, int Cout, int Cin, int k, int stride,
@@ -573,6 +573,37 @@ int vfi_comm_all_gather_v(vfi_comm_t* comm, float* const* bufs_dev, const int64_
 int64_t vfi_comm_plan_all_gather(int n, const int64_t* counts, int64_t* plan, int64_t cap);
 /* What vfi_comm_all_gather_v uses in this process: 0 = direct peer copies, 1 = RCCL grouped broadcasts. */
 int vfi_comm_all_gather_mode(void);
+
+/* ---- CAIN (vfi_models/cain/cain_arch.py CAIN(depth=3), common.py) ----------------------------------------------------------- */
+
+/* CAIN frame-in for one [H,W,C] fp32 frame (C >= 3; channels 0..2 used): mean_dev[c] = the frame's mean of channel c (sub_mean,
+ * common.py:7-10); the mean-free frame reflect-padded to a multiple of 128 (InOutPaddings, floor half before, :12-23) and
+ * pixel-unshuffled by 8 (pixel_shuffle(1/8), :208-210) into out[Hp/8, Wp/8, out_cs] channels 0..191 (channel c*64 + dy*8 + dx).
+ * The frame is not written.  workspace_dev >= 3 KiB.  Fails when the padding on a side is not smaller than the frame. */
+int vfi_cain_frame_in(const float* frame_dev, int C, int H, int W, float* out_dev, int out_cs, float* mean_dev, float* workspace_dev,
+                      int64_t workspace_bytes, void* stream);
+/* CAIN frame-out: pixel_shuffle(8) of feat [N, Hp/8, Wp/8, 192], cropped to H x W (the inverse padding), + (m0 + m1) / 2 per channel
+ * with means_dev [N][2][3] (frame 0's, frame 1's means), into out [N,H,W,3] fp32.  No clamp (cain_arch.py:66-74). */
+int vfi_cain_frame_out(const float* feat_dev, const float* means_dev, float* out_dev, int N, int H, int W, void* stream);
+/* Squeeze-and-excitation channel attention plus residual (CALayer + RCAB's `out += res`, common.py:132-178), contiguous NHWC:
+ * out[n,p,c] = t[n,p,c] * sigmoid(b2 + w2 . relu(b1 + w1 . mean_p t[n,p,:]))[c] + x[n,p,c]; w1 [R][C], w2 [C][R] (1x1 conv weights),
+ * C % 4 == 0, C <= 256, R <= 64.  Deterministic: per-workgroup partial sums in fixed slots, summed in a fixed order (no atomics).
+ * out may alias t or x.  workspace_dev >= N * 257 * C floats. */
+int vfi_channel_attention(const float* t_dev, const float* x_dev, float* out_dev, int N, int64_t HW, int C, const float* w1_dev,
+                          const float* b1_dev, const float* w2_dev, const float* b2_dev, int R, void* workspace_dev, int64_t workspace_bytes,
+                          void* stream);
+
+typedef struct vfi_cain vfi_cain_t;
+/* The 494 state_dict tensors of CAIN(depth=3) in cain_spec.cain_shapes() order (fp32 host memory, copied). */
+vfi_cain_t* vfi_cain_create(const float* const* tensors, const int64_t* numels, int n_tensors);
+void vfi_cain_destroy(vfi_cain_t* net);
+/* model(frame0, frame1)[0] for N pairs in one call (cain_arch.py:56-74): frame0_dev / frame1_dev = host arrays of N device pointers
+ * to [H,W,C] fp32 frames (C >= 3), out_dev [N,H,W,3].  Frames are not written.  A pair's result does not depend on its batch mates
+ * wherever every layer takes the Winograd kernel (chosen per image: feature maps from about 64 x 128, i.e. 512 x 1024 frames). */
+int vfi_cain_forward(vfi_cain_t* net, const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W,
+                     float* out_dev, void* stream);
+int vfi_cain_release_workspace(vfi_cain_t* net);
+int64_t vfi_cain_workspace_bytes(const vfi_cain_t* net);
 
 #ifdef __cplusplus
 }
