@@ -247,11 +247,14 @@ __global__ __launch_bounds__(256) void correlation_kernel(const float* __restric
 // line, staged whole in LDS; the line is rows (element stride 1) in the first pass and columns (element stride W) in the second —
 // the reference transposes in between instead.  Every candidate is formed exactly as in the reference and min does not depend on
 // order, so the result is bit-identical for any data, not only for binary masks.  The second pass also takes the square root,
-// meant to be correctly rounded like torch's sqrt after the reference's kernels (sqrt_rn below; __fsqrt_rn differed by an ulp on
-// gfx950).  Bit-identical to the reference's goldens; at 1080p distances one-ulp differences from the host's sqrt remain in
-// some pixels, cause not yet found (tests/test_gpu_ref_ops.py::test_edt_1080p reports the count).
-// Correctly rounded sqrt of a non-negative float: the hardware estimate, then moved by an ulp while m lies outside the square of
-// the rounding interval [mid(prev, s), mid(s, next)] — the midpoints have 25 significant bits, so their squares are exact in double.
+// correctly rounded like the GPU sqrt after the reference's kernels.  Bit-identical to the exact distance transform at every shape
+// tested, 1080p included (tests/test_gpu_ref_ops_edges.py, test_gpu_ref_ops.py::test_edt_1080p).  The one-ulp differences once
+// seen at 1080p were the host's: torch's CPU sqrt of a float32 tensor is not correctly rounded (on an EPYC host it is one ulp off
+// in 14 % of those pixels); the tests now take numpy's float64 sqrt rounded to float32.
+// Correctly rounded sqrt of a non-negative float: sqrtf, then moved by an ulp while m lies outside the square of the rounding
+// interval [mid(prev, s), mid(s, next)] — the midpoints have 25 significant bits, so their squares are exact in double.  On gfx950
+// sqrtf already lowers to v_sqrt_f32 plus an fma test of both neighbours and is correctly rounded by itself (every integer below
+// 2^24 and 2^22 random floats below 2^25, test_edt_sqrt_exhaustive, with or without the loop); the loop is kept as a guard.
 __device__ __forceinline__ float sqrt_rn(float m) {
     float s = sqrtf(m);
 #pragma unroll
