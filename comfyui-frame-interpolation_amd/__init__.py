@@ -14,6 +14,7 @@ _LAZY = {
     "GMFSS_Fortuna_VFI": ("gmfss", "GMFSS_Fortuna_VFI"),
     "IFUnet_VFI": ("ifunet", "IFUnet_VFI"),
     "CAIN_VFI": ("cain", "CAIN_VFI"),
+    "SepconvVFI": ("sepconv", "SepconvVFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -46,6 +47,10 @@ def _node_class_mappings():
         from .cain import CAIN_VFI
 
         extra["CAIN VFI"] = CAIN_VFI
+    if "sepconv" in extra_nodes():
+        from .sepconv import SepconvVFI
+
+        extra["Sepconv VFI"] = SepconvVFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -59,8 +64,8 @@ def _node_class_mappings():
 
 
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
-# list such as "cain".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
-EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)")}
+# list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
+EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)")}
 
 
 def extra_nodes():

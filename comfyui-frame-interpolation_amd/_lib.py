@@ -185,6 +185,15 @@ PROTOTYPES = {
                                    C.c_void_p]),
     "vfi_cain_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_cain_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "vfi_conv_accept_odd": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfi_sepconv_pair_out": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfi_sepconvnet_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
+    "vfi_sepconvnet_destroy": (None, [C.c_void_p]),
+    "vfi_sepconvnet_forward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "vfi_sepconvnet_release_workspace": (C.c_int, [C.c_void_p]),
+    "vfi_sepconvnet_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_m2m_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
     "vfi_m2m_destroy": (None, [C.c_void_p]),
     "vfi_m2m_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -185,6 +185,7 @@ struct vfi_conv {
     int Cout = 0, Cout_p = 0, Cin = 0, Cin_p = 0, kh = 0, kw = 0, taps = 0;
     int stride = 1, pad_mode = 0, kind = 0;  // kind 0: Conv2d, 1: ConvTranspose2d(4, 2, 1), 2: nearest x2 up-sampling + Conv2d(2, 'same') (vfi_conv_create_up2x2)
     unsigned char* tapmask = nullptr;         // kind 2: taps of every 64-channel N block's parity
+    bool odd_ok = false;                      // 3x3 stride-2 layer that takes odd input sizes (vfi_conv_accept_odd)
 };
 
 static unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
@@ -406,6 +407,12 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
     return c;
 }
 
+int vfi_conv_accept_odd(vfi_conv_t* c, int on) {
+    VFI_REQUIRE(c && c->kind == 0 && c->kh == 3 && c->stride == 2, "vfi_conv_accept_odd: only 3x3 stride-2 layers (kind 0) take odd sizes");
+    c->odd_ok = on != 0;
+    return 0;
+}
+
 int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs, int N,
                         int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs, void* stream) {
     VFI_REQUIRE(c && in_dev && out_dev && N > 0 && Hin > 0 && Win > 0, "vfi_conv_forward_ex: bad arguments");
@@ -413,7 +420,9 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
     VFI_REQUIRE(in_cs >= c->Cin_p && in_cs % 4 == 0 && ((uintptr_t)in_dev & 15) == 0,
                 "vfi_conv_forward_ex: input window must hold %d channels, 16-byte aligned (in_cs=%d)", c->Cin_p, in_cs);
     VFI_REQUIRE(act != 3 || c->prelu, "vfi_conv_forward_ex: act 3 (per-channel PReLU) needs slopes given at create time");
-    VFI_REQUIRE(c->stride == 1 || (Hin % 2 == 0 && Win % 2 == 0) || c->kind == 1,
+    // a 3x3 stride-2 layer opted in through vfi_conv_accept_odd takes odd sizes (nn.Conv2d(k=3, s=2, p=1): ceil(Hin/2) rows; the direct
+    // kernels bound their input reads by Hin / Win, so the missing last row / column reads as padding); every other one stays even-only
+    VFI_REQUIRE(c->stride == 1 || (Hin % 2 == 0 && Win % 2 == 0) || c->kind == 1 || c->odd_ok,
                 "vfi_conv_forward_ex: stride-2 layers need even input sizes (%dx%d)", Hin, Win);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -447,8 +456,8 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
         a.out_mode = 2;
         snprintf(name, sizeof(name), "deconv4x4s2_%dto%d", c->Cin_p, c->Cout);
     } else {
-        a.Hout = Hin / c->stride;
-        a.Wout = Win / c->stride;
+        a.Hout = (Hin + c->stride - 1) / c->stride;     // = Hin / stride for the even sizes
+        a.Wout = (Win + c->stride - 1) / c->stride;
         a.tap_y0 = a.tap_x0 = c->kh == 3 ? -1 : 0;
         snprintf(name, sizeof(name), "conv%dx%ds%d_%dto%d", c->kh, c->kw, c->stride, c->Cin_p, c->Cout);
     }

@@ -75,6 +75,8 @@ enum Option {
     kOptM2mSide,         // 1: M2M prepare runs the image-pyramid convolutions (EncDec's c features) on a side stream beside the PWC flow network, 0: one stream (default: r6 A/B measured the fork neutral on one pair — 7.00-7.04 vs 7.0-7.1 ms — and 8 % SLOWER under three pair lanes)
     kOptFilmSide,        // 1: FILM forward runs image 1's feature extraction and the backward flow pyramid on a side stream (another hardware queue) beside image 0's / the forward one, 0: one stream
     kOptWinoProbe,       // 1..4: the hot Winograd instantiation takes its cycle-ledger form (conv_wino.hip: g_wino_probe_out; default 0)
+    kOptSepconvSplitHeads,  // 1: SepConv++'s four head first-convs as four 64 -> 64 layers, each reading up2(row1) (default 0: one 64 -> 256 layer)
+    kOptSepconvPlanar,      // 1: SepConv++'s heads transposed to planar before the output stage (default), 0: the output stage reads them NHWC
     kOptCount
 };
 long option(Option o);

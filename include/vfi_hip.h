@@ -214,7 +214,11 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
 /* out = post_scale * act(layer(in) + bias + res) + post_shift.  act: 0 none, 1 LeakyReLU / single-parameter PReLU
  * (slope), 2 clamp01, 3 per-channel PReLU, 4 sigmoid, 5 GELU (erf form, nn.GELU()).  post_scale == 0 disables the affine.  res (nullable):
  * [N,Hout,Wout,res_cs] added before the activation (the decoder's `flow + netMain(...)`, :503).
- * Output is [N, Hin/stride, Win/stride, out_cs] (kind 0) or [N, 2*Hin, 2*Win, out_cs] (kind 1). */
+ * Output is [N, ceil(Hin/stride), ceil(Win/stride), out_cs] (kind 0; stride-2 layers need even sizes unless vfi_conv_accept_odd) or [N, 2*Hin, 2*Win, out_cs] (kind 1). */
+/* Let a 3x3 stride-2 layer (kind 0) take odd input sizes, as nn.Conv2d(k=3, s=2, p=1) does: output ceil(Hin/2) x ceil(Win/2), the
+ * missing row / column read as padding.  Off by default (such a layer rejects odd sizes); even sizes compute the same bits either way.
+ * Fails for any other layer. */
+int vfi_conv_accept_odd(vfi_conv_t* conv, int on);
 int vfi_conv_forward_ex(const vfi_conv_t* conv, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs,
                         int N, int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs,
                         void* stream);
@@ -604,6 +608,31 @@ int vfi_cain_forward(vfi_cain_t* net, const float* const* frame0_dev, const floa
                      float* out_dev, void* stream);
 int vfi_cain_release_workspace(vfi_cain_t* net);
 int64_t vfi_cain_workspace_bytes(const vfi_cain_t* net);
+
+/* ---- SepConv++ (vfi_models/sepconv/sepconv_enhanced.py Network) ------------------------------------------------------------ */
+
+/* SepConv++'s output stage for N frame pairs in one pass: frame0_dev / frame1_dev = host arrays of N device pointers to [H,W,C] fp32
+ * frames (C >= 3, channels 0..2 used; not written); ver0 / ver1 / hor0 / hor1 = the four heads' 51-tap filters (netVerone, netVertwo,
+ * netHorone, netHortwo) as NHWC [N, Hp, Wp, head_cs] tensors (Hp >= H, Wp >= W; each pointer at its head's first channel, so one
+ * tensor may hold all four).  out_dev [N,H,W,3] = (S0 + S1)[:3] / n with S_f = sepconv(pad25_replicate(frame_f) | 1, ver_f, hor_f) and
+ * n = (S0 + S1)[3], set to 1 where |n| < 0.01 (sepconv_enhanced.py:644-700); the frames are read with clamp-to-frame addressing.  No
+ * clamp of the result. */
+int vfi_sepconv_pair_out(const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W, const float* ver0_dev,
+                         const float* ver1_dev, const float* hor0_dev, const float* hor1_dev, int head_cs, int Hp, int Wp, float* out_dev,
+                         void* stream);
+
+typedef struct vfi_sepconvnet vfi_sepconvnet_t;
+/* The 88 state_dict tensors of SepConv++'s Network in sepconv_spec.sepconv_shapes() order (fp32 host memory, copied). */
+vfi_sepconvnet_t* vfi_sepconvnet_create(const float* const* tensors, const int64_t* numels, int n_tensors);
+void vfi_sepconvnet_destroy(vfi_sepconvnet_t* net);
+/* model(frame0, frame1) for N pairs in one call (sepconv_enhanced.py:605-700): frame0_dev / frame1_dev = host arrays of N device pointers
+ * to [H,W,C] fp32 frames (C >= 3), out_dev [N,H,W,3].  Frames are not written.  The pairs run one after another through the same
+ * launches as a call with one pair, so a pair's result does not depend on its batch mates (whichever kernel each layer takes); the
+ * workspace is sized for one pair. */
+int vfi_sepconvnet_forward(vfi_sepconvnet_t* net, const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W,
+                           float* out_dev, void* stream);
+int vfi_sepconvnet_release_workspace(vfi_sepconvnet_t* net);
+int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* net);
 
 #ifdef __cplusplus
 }
