@@ -3,8 +3,9 @@
 Node shape follows vfi_models/cain/__init__.py:11-64; the frame loop is vfi_utils.generic_frame_loop in its non-timestep mode
 (vfi_utils.py:161-170,202-206): per pair, the m-1 new frames come from recursive bisection, every model call interpolating between
 two frames it has already (the pair's frames or earlier model outputs, kept in full precision on the device).  The output order and
-the model calls are planned in schedule.bisect_output_plan; here each pair's tree is evaluated level by level, the calls of a level
-batched into one vfi_cain_forward (csrc/cain_net.hip: the whole CAIN forward, ~320 launches per call).  No clamp.
+the model calls are planned in schedule.bisect_output_plan; here (eval_pair, the pair kind of nodeloop.run_plan) each pair's tree is
+evaluated level by level, the calls of a level batched into one vfi_cain_forward (csrc/cain_net.hip: the whole CAIN forward, ~320
+launches per call).  No clamp.
 """
 import ctypes as C
 import typing
@@ -13,9 +14,9 @@ import torch
 
 from . import _lib
 from .cain_spec import cain_shapes, load_file
-from .ckpt import begin_call, cached_engine, end_call, load_file_from_github_release
-from .dist import all_gather_frames, world
-from .schedule import InterpolationStateList, bisect_output_plan, shard_tasks
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
+from .nodeloop import run_plan
+from .schedule import InterpolationStateList, bisect_output_plan
 
 MODEL_TYPE = "cain"
 CKPT_NAMES = ["pretrained_cain.pth"]
@@ -71,9 +72,11 @@ class CainEngine:
         return out
 
 
-def eval_pair(engine, f0, f1, calls, max_batch=MAX_BATCH):
-    """Evaluate one pair's bisection tree: calls = [(pos, lo, hi), ...] of schedule.bisect_calls.  Returns {pos: [H,W,3] device tensor},
-    positions 0 and 1 being f0 / f1.  The calls of one tree level only read positions of earlier levels, so each level is one batch."""
+def eval_pair(engine, f0, f1, task, max_batch=MAX_BATCH):
+    """The bisection pair kind of nodeloop.run_plan (CAIN, Sepconv): task = (pair, outputs, calls) of schedule.bisect_output_plan.
+    Evaluates the pair's tree, positions 0 and 1 being f0 / f1, and returns the frames at ``outputs`` ([H,W,3] device tensors).  The calls
+    of one tree level only read positions of earlier levels, so each level is one batch."""
+    _, outputs, calls = task
     have = {0: f0, 1: f1}
     level = {0: 0, 1: 0}
     by_level = {}
@@ -87,63 +90,7 @@ def eval_pair(engine, f0, f1, calls, max_batch=MAX_BATCH):
             out = engine.forward([have[lo] for _, lo, _ in part], [have[hi] for _, _, hi in part])
             for k, (pos, _, _) in enumerate(part):
                 have[pos] = out[k]
-    return have
-
-
-def run_plan(engine, frames, plan, tasks, name="CAIN VFI"):
-    """frames: [N,H,W,C] host tensor; plan / tasks from schedule.bisect_output_plan.  Pairs are block-partitioned over ranks, the
-    new frames all-gathered.  Host side as the M2M node (hostpipe.py): frames uploaded once ahead of the compute stream, new and
-    pass-through frames written into their rows of the output tensor in the background."""
-    if not plan:   # list multiplier of zeros: the reference fails in torch.cat of an empty list (vfi_utils.py:386)
-        raise RuntimeError(f"{name}: every frame pair was dropped (multiplier 0 everywhere) - nothing to output")
-    dev = engine.device
-    frames = frames[..., :3]
-    H, W = frames.shape[1:3]
-    rank, ws = world()
-    lo, hi = shard_tasks(tasks, rank, ws)
-    counts = [sum(len(t[1]) for t in tasks[slice(*shard_tasks(tasks, r, ws))]) for r in range(ws)]
-    mine = tasks[lo:hi]
-
-    from .hostpipe import OutputWriter, Uploader
-    main = torch.cuda.current_stream(dev)
-    wr = OutputWriter(len(plan), H, W, dev)
-    new_row = {}
-    for i, (kind, idx) in enumerate(plan):
-        if kind == "src":
-            wr.put_host(i, frames[idx])
-        else:
-            new_row[idx] = i
-    order = sorted({f for pair, _, _ in mine for f in (pair, pair + 1)})
-    item_of = {f: i for i, f in enumerate(order)}
-    first_new = sum(counts[:rank])
-    local = [] if ws > 1 else None
-    in_flight = []      # (event, tensor): outputs the writer still reads
-    up = Uploader(frames, order, dev, main, depth=min(4, len(order)) or 1) if order else None
-    try:
-        pos, released = 0, 0
-        for pair, outs, calls in mine:
-            f0, f1 = up.get(item_of[pair]), up.get(item_of[pair + 1])
-            have = eval_pair(engine, f0, f1, calls)
-            for p in outs:
-                if ws == 1:
-                    in_flight.append((wr.put_dev(new_row[first_new + pos], have[p]), have[p]))
-                else:
-                    local.append(have[p])
-                pos += 1
-            del have
-            in_flight = [(e, t) for e, t in in_flight if e is not None and not e.query()]
-            while released < item_of[pair + 1]:      # frames before pair+1 are never needed again (pairs ascend)
-                up.release(released)
-                released += 1
-        if ws > 1:
-            loc = torch.stack(local) if local else torch.empty((0, H, W, 3), dtype=torch.float32, device=dev)
-            new = all_gather_frames(loc, counts)
-            for k in range(new.shape[0]):
-                wr.put_dev(new_row[k], new[k])
-    finally:
-        if up is not None:
-            up.close()
-    return wr.finish()
+    return [have[p] for p in outputs]
 
 
 class CAIN_VFI:
@@ -170,11 +117,6 @@ class CAIN_VFI:
                                   "Please check the frame input using PreviewImage.")
         plan, tasks = bisect_output_plan(len(frames), multiplier, optional_interpolation_states)
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
-        engine, cached = cached_engine(MODEL_TYPE, model_path, lambda: CainEngine(load_file(model_path)))
-        try:
-            begin_call(engine, tuple(frames.shape[1:3]))
-            return (run_plan(engine, frames, plan, tasks),)
-        finally:
-            if cached:
-                torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)
+        entry = cached_engine(MODEL_TYPE, model_path, lambda: CainEngine(load_file(model_path)))
+        with engine_call(entry, tuple(frames.shape[1:3])) as engine:
+            return (run_plan(engine, frames, plan, tasks, eval_pair, "CAIN VFI"),)

@@ -5,9 +5,11 @@ Behaviour mirrored from vfi_utils.py:84-137: a checkpoint lives at
 not there every base URL and then the per-file mirrors are tried in order, and one combined
 exception is raised when all fail.
 """
+import contextlib
 import os
 import traceback
 
+import torch
 import yaml
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -97,16 +99,28 @@ def cached_engine(model_type, path, build):
 KEEP_WORKSPACE_BYTES = 16 << 30
 
 
-def begin_call(engine, shape):
-    """before a cached engine's node call: a kept workspace is for ONE frame shape (its root tensors are keyed by shape and would pile up)"""
+@contextlib.contextmanager
+def engine_call(entry, shape_key):
+    """One node call: ``with engine_call(cached_engine(...), shape_key) as engine:``, entry = cached_engine's (engine, cached).  A kept
+    workspace is for ONE ``shape_key`` (its root tensors are keyed by shape and would pile up): another key releases it first.  Afterwards
+    the device is drained, then an uncached engine is closed and a cached one's workspace released unless it may stay (KEEP_WORKSPACE_BYTES)."""
+    engine, cached = entry
+    try:
+        _begin_call(engine, shape_key)
+        yield engine
+    finally:
+        torch.cuda.synchronize(engine.device)
+        _end_call(engine, cached)
+
+
+def _begin_call(engine, shape):
     kept = getattr(engine, "_kept_shape", None)
     if kept is not None and kept != tuple(shape):
         engine.release_workspace()
     engine._kept_shape = tuple(shape)
 
 
-def end_call(engine, cached):
-    """after a node call: close an uncached engine; release a cached one's workspace unless it may stay (KEEP_WORKSPACE_BYTES)"""
+def _end_call(engine, cached):
     if not cached:
         engine.close()
         return

@@ -24,11 +24,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ckpt import cached_engine, load_file_from_github_release
-from .lanes import lane_set, lanes_of, tell_lone_pair
-from .dist import all_gather_frames, world
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film_spec import check_state_dict, film_shapes
-from .schedule import InterpolationStateList, shard_tasks
+from .lanes import lane_set
+from .nodeloop import run_plan
+from .schedule import InterpolationStateList, film_output_plan
 
 MODEL_TYPE = "film"
 
@@ -107,6 +107,16 @@ def film_schedule(inter_frames):
     return calls
 
 
+def film_pair(eng, f0, f1, task):
+    """FILM's pair kind of nodeloop.run_plan: task = (pair, positions) of schedule.film_output_plan.  The greedy bisection runs
+    sequentially on the current stream, every output clamped to [0, 1] and re-used as an input."""
+    new = task[1]
+    res = {0: f0, len(new) + 1: f1}
+    for l, r, k in film_schedule(len(new)):
+        res[k] = eng.forward(res[l], res[r], clamp=True)
+    return [res[k] for k in new]
+
+
 def _load_state_dict(path):
     try:
         return torch.jit.load(path, map_location="cpu").state_dict()   # the reference's artifact (film/__init__.py:74)
@@ -139,94 +149,6 @@ class FILM_VFI:
         def build():
             sd = _load_state_dict(model_path)
             return lane_set("film", lambda: FilmEngine(sd))
-        engine, cached = cached_engine(MODEL_TYPE, model_path, build)
-        try:
-            frames = frames[..., :3]
-            n = len(frames)
-            if type(multiplier) == int:
-                multipliers = [multiplier] * n
-            else:
-                multipliers = list(map(int, multiplier))
-                multipliers += [2] * (n - len(multipliers) - 1)
-            # inference(..., inter_frames = m - 1) (film/__init__.py:12-41): m in {-1, 0, 1} runs no iteration and the pair contributes
-            # frame_i alone; m <= -2 fails in torch.linspace(0, 1, m + 1)
-            kept = [i for i in range(n - 1)
-                    if not (optional_interpolation_states is not None and optional_interpolation_states.is_frame_skipped(i))]
-            if any(multipliers[i] <= -2 for i in kept):
-                raise RuntimeError(f"FILM: multiplier {min(multipliers[i] for i in kept)} — the reference fails in torch.linspace for multipliers <= -2")
-            multipliers = [max(int(m), 1) for m in multipliers]
-            dev = engine.device
-            H, W = frames.shape[1:3]
-            # pairs are independent (the bisection inside a pair is sequential): block-partition the kept pairs over
-            # ranks, all-gather the per-rank frame blocks
-            pairs = [i for i in range(n - 1)
-                     if not (optional_interpolation_states is not None and optional_interpolation_states.is_frame_skipped(i))]
-            rank, ws = world()
-            lo, hi = shard_tasks(pairs, rank, ws)
-            per_pair = [multipliers[i] for i in pairs]           # output frames contributed by each kept pair
-            counts = [sum(per_pair[slice(*shard_tasks(pairs, r, ws))]) for r in range(ws)]
-            # host side (hostpipe.py): new frames and pass-through frames land in their rows of the output tensor in the
-            # background while the next pair computes
-            from .hostpipe import OutputWriter, Uploader
-            wr = OutputWriter(sum(per_pair) + 1, H, W, dev)
-            row0 = [0]
-            for m in per_pair:
-                row0.append(row0[-1] + m)          # first output row of each kept pair
-            local = torch.empty((counts[rank], H, W, 3), dtype=torch.float32, device=dev) if ws > 1 else None
-            mine = pairs[lo:hi]
-            order = sorted({f for i in mine for f in (i, i + 1)})       # every needed frame is uploaded once, ahead of use
-            item_of = {f: k for k, f in enumerate(order)}
-            # pair lanes (lanes.py): kept pair j runs on lane j % n_lanes = its own engine on its own stream (the bisection inside a
-            # pair stays sequential on that stream); `main` only carries the bookkeeping events
-            main = torch.cuda.current_stream(dev)
-            if hasattr(engine, "apart_from"):      # (a LaneSet) its streams stay clear of the copy streams' hardware queues where there are enough
-                from .hostpipe import _stream
-                engine.apart_from = [_stream(dev, "down"), _stream(dev, "up"), main]
-            lane, n_lanes = lanes_of(engine, len(mine))
-            tell_lone_pair(engine, n_lanes)      # the forward's own two-stream fork is for a lone pair
-            up = Uploader(frames, order, dev, main, depth=min(max(4, n_lanes + 2), len(order)) or 1)
-            keep, pos, released, pending = [], 0, 0, []
-            try:
-                for j in range(lo, hi):
-                    i = pairs[j]
-                    eng, st = lane((j - lo) % n_lanes)
-                    res = {0: up.get(item_of[i], st), multipliers[i]: up.get(item_of[i + 1], st)}
-                    with torch.cuda.stream(st):
-                        for (l, r, new) in film_schedule(multipliers[i] - 1):
-                            res[new] = eng.forward(res[l], res[r], clamp=True)
-                        for n_k, k in enumerate(sorted(res)[:-1]):
-                            if ws > 1:
-                                local[pos] = res[k]      # res[0] is the uploaded original: bit-exact round trip
-                            elif k == 0:
-                                wr.put_host(row0[j] + n_k, frames[i])
-                            else:
-                                wr.put_dev(row0[j] + n_k, res[k], st)
-                                keep.append(res[k])      # alive until the copy-back has read it
-                            pos += 1
-                        if n_lanes > 1:
-                            done = torch.cuda.Event()
-                            done.record(st)
-                            pending.append(done)
-                    if released < item_of[i + 1]:        # frames before i+1 are not needed again (pairs ascend)
-                        for ev in pending:               # ... once every lane that read them is through
-                            main.wait_event(ev)
-                        pending = []
-                        while released < item_of[i + 1]:
-                            up.release(released)
-                            released += 1
-            finally:
-                for ev in pending:
-                    main.wait_event(ev)
-                up.close()
-            if ws > 1:
-                allf = all_gather_frames(local, counts)
-                for k in range(allf.shape[0]):
-                    wr.put_dev(k, allf[k])
-            wr.put_host(sum(per_pair), frames[-1])
-            return (wr.finish(),)
-        finally:
-            if cached:
-                torch.cuda.synchronize(engine.device)
-                engine.release_workspace()
-            else:
-                engine.close()
+        with engine_call(cached_engine(MODEL_TYPE, model_path, build), tuple(frames.shape[1:3])) as engine:
+            plan, tasks = film_output_plan(len(frames), multiplier, optional_interpolation_states)
+            return (run_plan(engine, frames, plan, tasks, film_pair, "FILM VFI"),)

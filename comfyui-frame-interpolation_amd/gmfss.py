@@ -662,26 +662,21 @@ class GMFSS_Fortuna_VFI:
 
     def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10, multiplier: typing.SupportsInt = 2,
             optional_interpolation_states: InterpolationStateList = None, **kwargs):
-        from .ckpt import load_file_from_github_release
+        from .ckpt import cached_engine, engine_call, load_file_from_github_release
+        from .lanes import lane_set
         from .m2m import run_plan
 
         assert len(frames) >= 2, f"VFI model GMFSS Fortuna requires at least 2 frames to work with, only found {frames.shape[0]}."
         if ckpt_name not in CKPTS_PATH_CONFIG:
             raise KeyError(ckpt_name)
-        from .ckpt import begin_call, cached_engine, end_call
-        from .lanes import lane_set
         paths = {part: load_file_from_github_release(*loc) for part, loc in CKPTS_PATH_CONFIG[ckpt_name].items()}
 
         def build():
             sds = {part: _load(path) for part, path in paths.items()}
             return lane_set("gmfss", lambda: GMFSSEngine(sds))
         # (the reference rebuilds the model on every call, gmfss_fortuna/__init__.py:129-130.  Here the packed weights stay between calls —
-        # a constructor is 60-90 ms per lane — keyed by the variant and its fusion-net file; see ckpt.cached_engine)
-        engine, cached = cached_engine(MODEL_TYPE + ":" + ckpt_name, paths["fusionnet"], build)
-        try:
-            begin_call(engine, frames.shape[1:3])
+        # a constructor is 60-90 ms per lane — keyed by the variant and its fusion-net file; see ckpt.cached_engine.  The workspace and the
+        # captured graphs stay for the next call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)
+        with engine_call(cached_engine(MODEL_TYPE + ":" + ckpt_name, paths["fusionnet"], build), frames.shape[1:3]) as engine:
             plan, tasks = generic_output_plan(len(frames), multiplier, optional_interpolation_states)
             return (run_plan(engine, frames, plan, tasks, name="GMFSS Fortuna VFI"),)
-        finally:
-            torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)      # (the workspace and the captured graphs stay for the next call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)

@@ -27,7 +27,7 @@ import typing
 import torch
 
 from . import _lib
-from .ckpt import begin_call, cached_engine, end_call, load_file_from_github_release
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .lanes import lane_set
 from .lanes import configure as configure_lanes
 from .ifrnet_spec import CKPT_NAMES, CONFIG, check_state_dict, decoder_io, kind_of
@@ -335,14 +335,10 @@ class IFRNet_VFI:
         def build():
             sd = _load_state_dict(model_path)
             return lane_set("ifrnet", lambda: IFRNetEngine(sd, kind))
-        engine, cached = cached_engine(MODEL_TYPE + kind, model_path, build)
-        try:
-            begin_call(engine, tuple(frames.shape[1:3]) + (float(scale_factor), multiplier if isinstance(multiplier, int) else -1))
+        # (the scratch tensors stay for the next call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)
+        shape_key = tuple(frames.shape[1:3]) + (float(scale_factor), multiplier if isinstance(multiplier, int) else -1)
+        with engine_call(cached_engine(MODEL_TYPE + kind, model_path, build), shape_key) as engine:
             embt = float(scale_factor)           # positional mis-binding of the reference's call, see the module docstring
             configure_lanes(engine, lambda e: setattr(e, "embt", embt))
             plan, tasks = generic_output_plan(len(frames), multiplier, optional_interpolation_states)
             return (run_plan(engine, frames, plan, tasks, name="IFRNet VFI"),)
-        finally:
-            if cached:
-                torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)      # (the scratch tensors stay for the next call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)

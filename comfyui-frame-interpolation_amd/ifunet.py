@@ -399,27 +399,22 @@ class IFUnet_VFI:
     def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames: typing.SupportsInt = 1,
             multiplier: typing.SupportsInt = 2, scale_factor: typing.SupportsFloat = 1.0, ensemble: bool = True,
             optional_interpolation_states: InterpolationStateList = None, **kwargs):
-        from .ckpt import load_file_from_github_release
+        from .ckpt import cached_engine, engine_call, load_file_from_github_release
+        from .lanes import configure as configure_lanes
+        from .lanes import lane_set
         from .m2m import run_plan
 
         assert len(frames) >= 2, f"VFI model IFUNet requires at least 2 frames to work with, only found {frames.shape[0]}."
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
-        from .ckpt import begin_call, cached_engine, end_call
-        from .lanes import configure as configure_lanes
-        from .lanes import lane_set
 
         def build():
             sd = torch.load(model_path, map_location="cpu", weights_only=False)
             return lane_set("ifunet", lambda: IFUNetEngine(sd))
         # (the reference rebuilds the model on every call; here the packed weights stay between calls — the constructor, Winograd weight
-        # transforms of ~250 layers, is 0.4 s per lane; see ckpt.cached_engine)
-        engine, cached = cached_engine(MODEL_TYPE, model_path, build)
-        sc, ens = float(scale_factor), bool(ensemble)
-        configure_lanes(engine, lambda e: (setattr(e, "scale", sc), setattr(e, "ensemble", ens)))
-        try:
-            begin_call(engine, frames.shape[1:3])
+        # transforms of ~250 layers, is 0.4 s per lane; see ckpt.cached_engine.  The workspace and the captured graphs stay for the next
+        # call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)
+        with engine_call(cached_engine(MODEL_TYPE, model_path, build), frames.shape[1:3]) as engine:
+            sc, ens = float(scale_factor), bool(ensemble)
+            configure_lanes(engine, lambda e: (setattr(e, "scale", sc), setattr(e, "ensemble", ens)))
             plan, tasks = generic_output_plan(len(frames), multiplier, optional_interpolation_states)
             return (run_plan(engine, frames, plan, tasks, name="IFUnet VFI"),)
-        finally:
-            torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)      # (the workspace and the captured graphs stay for the next call of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)

@@ -26,11 +26,11 @@ import typing
 import torch
 
 from . import _lib
-from .ckpt import cached_engine, end_call, load_file_from_github_release
-from .lanes import LaneSet, lane_set
-from .dist import all_gather_frames, world
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
+from .lanes import lane_set
 from .m2m_spec import check_state_dict, m2m_shapes
-from .schedule import InterpolationStateList, generic_output_plan, shard_tasks
+from . import nodeloop
+from .schedule import InterpolationStateList, generic_output_plan
 
 MODEL_TYPE = "m2m"
 RATIO = 4        # M2M_PWC.forward default ratio (the node never overrides it, vfi_models/m2m/__init__.py:51-55)
@@ -129,97 +129,21 @@ def _load_state_dict(path):
     return sd.state_dict() if hasattr(sd, "state_dict") else sd
 
 
+def timestep_pair(eng, f0, f1, task):
+    """The timestep pair kind of nodeloop.run_plan (M2M, IFRNet, GMFSS, IFUNet): task = (pair, [timesteps]); ``prepare`` once, then
+    ``render(t, out)`` per timestep, each frame into a tensor of its own (allocated on the current stream: the pair's lane).  Yields
+    every frame as soon as its render is queued, so that its copy-back is queued before the next render."""
+    eng.prepare(f0, f1)
+    for t in task[1]:
+        out = torch.empty(f0.shape[:2] + (3,), dtype=torch.float32, device=f0.device)
+        eng.render(t, out)
+        yield out
+
+
 def run_plan(engine, frames, plan, tasks, name="M2M VFI"):
-    """Shared by the node and the tests.  frames: [N,H,W,C] host tensor; plan/tasks from generic_output_plan.
-
-    Pairs are independent: the (pair, timesteps) tasks are block-partitioned over ranks and the new frames
-    all-gathered.  Host side (hostpipe.py): every needed frame is uploaded once through pinned staging ahead of the
-    compute stream; new frames and pass-through frames land in their final rows of the output tensor in the background."""
-    if not plan:  # list multiplier of zeros: the reference fails in torch.cat of an empty list (vfi_utils.py:386)
-        raise RuntimeError(f"{name}: every frame pair was dropped (multiplier 0 everywhere) - nothing to output")
-    dev = engine.device
-    frames = frames[..., :3]
-    H, W = frames.shape[1:3]
-    rank, ws = world()
-    lo, hi = shard_tasks(tasks, rank, ws)
-    counts = [sum(len(ts) for _, ts in tasks[slice(*shard_tasks(tasks, r, ws))]) for r in range(ws)]
-    if dev.type != "cuda":  # stand-in engines of the CPU tests: same control flow without the device pipeline
-        engine = engine.engines[0] if isinstance(engine, LaneSet) else engine
-        local = torch.empty((counts[rank], H, W, 3), dtype=torch.float32, device=dev)
-        pos = 0
-        for pair, ts in tasks[lo:hi]:
-            engine.prepare(frames[pair].to(dev, torch.float32).contiguous(), frames[pair + 1].to(dev, torch.float32).contiguous())
-            for t in ts:
-                engine.render(t, local[pos])
-                pos += 1
-        new = all_gather_frames(local, counts).cpu()
-        src = frames.to("cpu", torch.float32)
-        out = torch.empty((len(plan), H, W, 3), dtype=torch.float32)
-        for i, (kind, idx) in enumerate(plan):
-            out[i] = src[idx] if kind == "src" else new[idx]
-        return out
-
-    from .hostpipe import OutputWriter, Uploader
-    from .lanes import lanes_of, tell_lone_pair
-    main = torch.cuda.current_stream(dev)
-    wr = OutputWriter(len(plan), H, W, dev)
-    new_row = {}
-    for i, (kind, idx) in enumerate(plan):
-        if kind == "src":
-            wr.put_host(i, frames[idx])
-        else:
-            new_row[idx] = i
-    mine = tasks[lo:hi]
-    # pair lanes (lanes.py): pair j runs on lane j % n_lanes = its own engine on its own stream; `main` only carries the bookkeeping
-    # events (a frame's staging slot is released on main after main has waited for every lane that read it)
-    if isinstance(engine, LaneSet):      # the lanes' streams stay clear of the copy streams' hardware queues where there are enough of them
-        from .hostpipe import _stream
-        engine.apart_from = [_stream(dev, "down"), _stream(dev, "up"), main]
-    lane, n_lanes = lanes_of(engine, len(mine))
-    tell_lone_pair(engine, n_lanes)
-    order = sorted({f for pair, _ in mine for f in (pair, pair + 1)})
-    up = Uploader(frames, order, dev, main, depth=min(max(4, n_lanes + 2), len(order)) or 1)
-    item_of = {f: i for i, f in enumerate(order)}
-    local = torch.empty((counts[rank], H, W, 3), dtype=torch.float32, device=dev)
-    first_new = sum(counts[:rank])
-    pending = []          # completion events of lanes main has not waited for yet
-    try:
-        pos, released = 0, 0
-        for j, (pair, ts) in enumerate(mine):
-            eng, st = lane(j % n_lanes)
-            f0, f1 = up.get(item_of[pair], st), up.get(item_of[pair + 1], st)
-            with torch.cuda.stream(st):
-                eng.prepare(f0, f1)
-                for t in ts:
-                    eng.render(t, local[pos])
-                    if ws == 1:
-                        wr.put_dev(new_row[first_new + pos], local[pos], st)
-                    pos += 1
-                if n_lanes > 1:
-                    done = torch.cuda.Event()
-                    done.record(st)
-                    pending.append(done)
-            # Release only after the LAST render of the pair: some engines' prepare() keeps references to the ring-slot
-            # tensors and render() re-reads them (IFRNet, IFUNet), so the `consumed` event must follow those reads.
-            if released < item_of[pair + 1]:          # frames before pair+1 are never needed again (tasks ascend)
-                for ev in pending:
-                    main.wait_event(ev)
-                pending = []
-                while released < item_of[pair + 1]:
-                    up.release(released)
-                    released += 1
-        for ev in pending:
-            main.wait_event(ev)
-        pending = []
-        if ws > 1:
-            new = all_gather_frames(local, counts)
-            for k in range(new.shape[0]):
-                wr.put_dev(new_row[k], new[k])
-    finally:
-        for ev in pending:      # (an error path: the staging rings go back with a `busy` event recorded on main)
-            main.wait_event(ev)
-        up.close()
-    return wr.finish()
+    """nodeloop.run_plan with the timestep pair kind: the frame loop of the M2M, IFRNet, GMFSS and IFUNet nodes.  frames: [N,H,W,C] host
+    tensor; plan / tasks from schedule.generic_output_plan."""
+    return nodeloop.run_plan(engine, frames, plan, tasks, timestep_pair, name)
 
 
 class M2M_VFI:
@@ -247,11 +171,7 @@ class M2M_VFI:
         def build():
             sd = _load_state_dict(model_path)
             return lane_set("m2m", lambda: M2MEngine(sd))
-        engine, cached = cached_engine(MODEL_TYPE, model_path, build)
-        try:
+        # (the workspace, 0.3 GB per lane at 1080p, stays for the next clip of this frame shape: ckpt.KEEP_WORKSPACE_BYTES)
+        with engine_call(cached_engine(MODEL_TYPE, model_path, build), tuple(frames.shape[1:3])) as engine:
             plan, tasks = generic_output_plan(len(frames), multiplier, optional_interpolation_states)
             return (run_plan(engine, frames, plan, tasks),)
-        finally:
-            if cached:
-                torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)      # (0.3 GB per lane at 1080p: stays for the next clip, ckpt.KEEP_WORKSPACE_BYTES)

@@ -171,6 +171,31 @@ def bisect_output_plan(n_frames, multiplier, states=None):
     return plan, out
 
 
+def film_output_plan(n_frames, multiplier, states=None):
+    """Output order of the FILM node (vfi_models/film/__init__.py:63-113) in :func:`generic_output_plan`'s form; ``tasks`` =
+    ``[(pair_idx, positions), ...]`` with ``positions`` = 1..m-1, the new frames' places on the pair's grid of m + 1
+    (film.film_schedule).  List multipliers are padded with 2; the skip list is consulted with the pair's own index and a skipped
+    pair contributes nothing, not even its first frame.  inference(..., inter_frames = m - 1) (film/__init__.py:12-41): m in
+    {-1, 0, 1} runs no iteration and the pair contributes frame_i alone; m <= -2 fails in torch.linspace(0, 1, m + 1)."""
+    if type(multiplier) == int:
+        ms = [multiplier] * n_frames
+    else:
+        ms = list(map(int, multiplier))
+        ms += [2] * (n_frames - len(ms) - 1)
+    kept = [i for i in range(n_frames - 1) if not (states is not None and states.is_frame_skipped(i))]
+    if any(ms[i] <= -2 for i in kept):
+        raise RuntimeError(f"FILM: multiplier {min(ms[i] for i in kept)} — the reference fails in torch.linspace for multipliers <= -2")
+    plan, tasks, n_new = [], [], 0
+    for i in kept:
+        new = list(range(1, max(int(ms[i]), 1)))
+        tasks.append((i, new))
+        plan.append(("src", i))
+        plan += [("new", n_new + k) for k in range(len(new))]
+        n_new += len(new)
+    plan.append(("src", n_frames - 1))
+    return plan, tasks
+
+
 def shard_tasks(tasks, rank, world):
     """Contiguous block partition of the task list over ``world`` ranks.
 

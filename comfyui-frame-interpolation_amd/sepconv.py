@@ -2,8 +2,8 @@
 
 Node shape follows vfi_models/sepconv/__init__.py:11-56; the frame loop is vfi_utils.generic_frame_loop in its non-timestep mode, the
 same loop as CAIN's: per pair, the m-1 new frames come from recursive bisection (schedule.bisect_output_plan), evaluated level by level
-through cain.run_plan / eval_pair.  Each model call is one vfi_sepconvnet_forward (csrc/sepconv_net.hip: the whole network plus the fused
-output stage).  No clamp.
+(nodeloop.run_plan with cain.eval_pair).  Each model call is one vfi_sepconvnet_forward (csrc/sepconv_net.hip: the whole network plus
+the fused output stage).  No clamp.
 """
 import ctypes as C
 import typing
@@ -11,8 +11,9 @@ import typing
 import torch
 
 from . import _lib
-from .cain import run_plan
-from .ckpt import begin_call, cached_engine, end_call, load_file_from_github_release
+from .cain import eval_pair
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
+from .nodeloop import run_plan
 from .schedule import InterpolationStateList, bisect_output_plan
 from .sepconv_spec import load_file, sepconv_shapes
 
@@ -93,11 +94,6 @@ class SepconvVFI:
                                   "Please check the frame input using PreviewImage.")
         plan, tasks = bisect_output_plan(len(frames), multiplier, optional_interpolation_states)
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
-        engine, cached = cached_engine(MODEL_TYPE, model_path, lambda: SepconvEngine(load_file(model_path)))
-        try:
-            begin_call(engine, tuple(frames.shape[1:3]))
-            return (run_plan(engine, frames, plan, tasks, name="Sepconv VFI"),)
-        finally:
-            if cached:
-                torch.cuda.synchronize(engine.device)
-            end_call(engine, cached)
+        entry = cached_engine(MODEL_TYPE, model_path, lambda: SepconvEngine(load_file(model_path)))
+        with engine_call(entry, tuple(frames.shape[1:3])) as engine:
+            return (run_plan(engine, frames, plan, tasks, eval_pair, "Sepconv VFI"),)

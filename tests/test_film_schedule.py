@@ -50,3 +50,40 @@ def test_c_side_linspace_equals_torch(hip_lib):
         out = np.zeros(n, np.float32)
         assert hip_lib.vfi_test_linspace01(n, out.ctypes.data) == n
         assert np.array_equal(out, torch.linspace(0, 1, n).numpy()), n
+
+
+def test_output_plan_known_answers():
+    """FILM_VFI's output order (vfi_models/film/__init__.py:63-113): a pair contributes frame_i and its m-1 new frames, a skipped pair
+    nothing, the clip's last frame closes the output"""
+    import pytest
+
+    from cfi_amd.schedule import InterpolationStateList, film_output_plan
+
+    def src(i):
+        return ("src", i)
+
+    def new(k):
+        return ("new", k)
+
+    plan, tasks = film_output_plan(3, 3)
+    assert plan == [src(0), new(0), new(1), src(1), new(2), new(3), src(2)]
+    assert tasks == [(0, [1, 2]), (1, [1, 2])]
+    plan, tasks = film_output_plan(4, [4])                        # a list is padded with 2
+    assert plan == [src(0), new(0), new(1), new(2), src(1), new(3), src(2), new(4), src(3)]
+    assert tasks == [(0, [1, 2, 3]), (1, [1]), (2, [1])]
+    skip = InterpolationStateList([1], True)                      # the skip list sees the pair's own index, also for a list multiplier
+    for m in (2, [2, 2, 2]):
+        plan, tasks = film_output_plan(4, m, skip)
+        assert plan == [src(0), new(0), src(2), new(1), src(3)] and tasks == [(0, [1]), (2, [1])]
+    plan, tasks = film_output_plan(4, 3, InterpolationStateList([0], False))
+    assert plan == [src(0), new(0), new(1), src(3)] and tasks == [(0, [1, 2])]
+    plan, tasks = film_output_plan(4, [-1, 0, 1])                 # m in {-1, 0, 1}: frame_i alone
+    assert plan == [src(0), src(1), src(2), src(3)] and tasks == [(0, []), (1, []), (2, [])]
+    plan, tasks = film_output_plan(3, 1)
+    assert plan == [src(0), src(1), src(2)] and tasks == [(0, []), (1, [])]
+    with pytest.raises(RuntimeError, match="linspace"):           # m <= -2: torch.linspace(0, 1, m + 1) fails in the reference
+        film_output_plan(3, [2, -2])
+    with pytest.raises(RuntimeError, match="multiplier -3"):
+        film_output_plan(3, -3)
+    plan, tasks = film_output_plan(3, [2, -2], InterpolationStateList([1], True))      # ... unless the pair is skipped
+    assert plan == [src(0), new(0), src(2)] and tasks == [(0, [1])]

@@ -1,5 +1,5 @@
 """End-to-end node timing (host tensor in, host tensor out) of the op-by-op nodes — IFUnet VFI, GMFSS Fortuna VFI — at 1080p, call after call
-(engines, workspaces and captured graphs stay between calls of one frame shape: ckpt.end_call).   usage: node_e2e_ops.py [frames] [ifunet|gmfss]"""
+(engines, workspaces and captured graphs stay between calls of one frame shape: ckpt.engine_call).   usage: node_e2e_ops.py [frames] [ifunet|gmfss]"""
 import os
 import sys
 import tempfile
