@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — interpolated frames/s of the RIFE 4.7 2x hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W        (one process per GPU: the driver's launch)
-    python bench.py --gpus N --steps K --warmup W                          (ONE process, N device threads: multidev.py)
+    python bench.py --gpus N --steps K --warmup W --device-threads         (ONE process, N device threads: multidev.py)
 
 One "step" = one pass of the hot path over one batch of a synthetic 1080p frame-pair stream that is
 already resident in HBM: for each of B new frames  clamp/pad/encode (vfi_rife_load_frame)  and for
@@ -13,7 +13,11 @@ pass over the whole 33-frame clip of SURVEY 8d config 2),
 outputs written to HBM.  N>1: every rank runs its own stream (weak scaling, pairs are independent)
 and the new frames are all-gathered over RCCL/xGMI, overlapped with the next step.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the
+--dump-outputs files, and the line's headline keys (metric, value, unit, ms_per_step, higher_is_better, dtype, config, ...).
+--full adds the objects below: the oracle forwards before the warm-up, the clock probe and sysfs sampler around the timed steps,
+and the legs after them (N > 1: also the all-gather's cost and the sharded FILM / M2M legs).  --no-cpu-baseline, --no-parity,
+--no-e2e, --no-extras, --no-strong and --peer-copy-leg choose among them.  Extra objects (--full):
   roofline     — dominant kernel (block3 ResConv 3x3, 64->64 ch @272x480, fp32 MFMA).  The kernel is the Winograd F(2x2,3x3) form
                  (csrc/conv_wino.hip): `achieved` / `frac` count the MFMA FLOP it ISSUES per launch (direct form / 2.25, on whole
                  16x8-pixel regions) / the average launch duration measured with HIP events on the launch stream (library-side
@@ -1137,30 +1141,34 @@ def main_single_process(args):
     elapsed = times["t1"] - times["t0"]
     dumped = dump_outputs(args.dump_outputs, bufs[0][(K - 1) & 1][:B]) if args.dump_outputs else None
 
-    # roofline leg: the dominant kernel's launch duration by HIP events on device 0's stream (the library's tracer is
-    # process-wide, so this pass runs device 0 alone: K steps, no collective)
     torch.cuda.set_device(0)
     lib = _lib.load()
-    lib.vfi_trace_reset()
-    lib.vfi_trace_enable(1)
-    eng0 = group.engines[0]
-    t0 = time.perf_counter()
-    for i in range(K):
-        eng0.load_frames(list(range(B + 1)), [raw[0][clip_base(B, i & 1) + j] for j in range(B + 1)])
-        eng0.interpolate(slot0, slot1, ts, bufs[0][i & 1][:B])
-    torch.cuda.synchronize(0)
-    traced = time.perf_counter() - t0
-    lib.vfi_trace_enable(0)
-    rep = _lib.trace_report()
-    lib.vfi_trace_reset()
     mode = "RCCL grouped per-root broadcasts" if lib.vfi_comm_all_gather_mode() == 1 else "direct peer copies, one per ordered device pair"
-    res = result_line(args, N, elapsed, traced, rep, eng0, f"all_gather_v ({mode}; in place, comm streams), overlapped" if gather else "none")
+    collective = f"all_gather_v ({mode}; in place, comm streams), overlapped" if gather else "none"
+    if args.full:
+        # roofline leg: the dominant kernel's launch duration by HIP events on device 0's stream (the library's tracer is
+        # process-wide, so this pass runs device 0 alone: K steps, no collective)
+        lib.vfi_trace_reset()
+        lib.vfi_trace_enable(1)
+        eng0 = group.engines[0]
+        t0 = time.perf_counter()
+        for i in range(K):
+            eng0.load_frames(list(range(B + 1)), [raw[0][clip_base(B, i & 1) + j] for j in range(B + 1)])
+            eng0.interpolate(slot0, slot1, ts, bufs[0][i & 1][:B])
+        torch.cuda.synchronize(0)
+        traced = time.perf_counter() - t0
+        lib.vfi_trace_enable(0)
+        rep = _lib.trace_report()
+        lib.vfi_trace_reset()
+        res = result_line(args, N, elapsed, traced, rep, eng0, collective)
+    else:
+        res = headline(args, N, elapsed, collective)
     res["config"]["launch"] = f"one process, {N} device thread(s) (multidev.py; weights broadcast over RCCL)"
     res["config"]["reserved_cus"] = reserve
     if dumped is not None:
         res["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     _lib.load().vfi_set_reserved_cus(0)
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         try:
             res["strong_4k_x4"] = strong_4k_x4(args, torch.device("cuda", 0), N, 0, "nccl", group=group)
         except Exception as e:
@@ -1171,10 +1179,41 @@ def main_single_process(args):
     print(json.dumps(res), flush=True)
 
 
-def result_line(args, world, elapsed, traced, rep, eng, collective, clock=None):
-    """The JSON line's common part (metric, roofline of the dominant kernel, per-kernel table).  ``clock``: {"timed": ..., "traced": ...,
-    "sysfs": ...} from the clock probe (None where it was not run)."""
+def headline(args, world, elapsed, collective):
+    """The JSON line's headline part — all a plain run prints: the metric of the timed region and the configuration it ran."""
     B, H, W, K, Wm = args.batch, args.height, args.width, args.steps, args.warmup
+    return {
+        # BASELINE.json's metric.  ONE meaning for `value` at every N (the bench contract's): the WHOLE-JOB aggregate over n_gpus — the
+        # driver divides by N itself; the per-GPU rate BASELINE.json's metric name speaks of is `per_gpu_frames_per_s` (== value at N = 1)
+        "metric": "interpolated frames/sec/GPU @1080p RIFE4.7 2x" + ("" if world == 1 else f" (value = aggregate over {world} GPUs; per GPU: per_gpu_frames_per_s)"),
+        "value": round(world * B * K / elapsed, 3),
+        "unit": "frames/s" if world == 1 else f"frames/s, whole job = sum over {world} GPUs (weak scaling: {B} pairs/step/GPU)",
+        "per_gpu_frames_per_s": round(B * K / elapsed, 3),
+        "n_gpus": world,
+        "steps": K,
+        "warmup": Wm,
+        "ms_per_step": round(elapsed / K * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"RIFE 4.7 2x, {H}x{W} synthetic frame-pair stream, {B} pairs/step/GPU resident in HBM "
+                        f"(BASELINE.json configs[1]; SURVEY 8d config 2 clip: {clip_frames(B)} frames torch.manual_seed(0) torch.rand); "
+                        f"seeded random-init weights",
+            "pairs_per_step_per_gpu": B,
+            "per_gpu_frames_per_s": round(B * K / elapsed, 3),
+            "new_frame_collective": collective,
+            "target_frames_per_s_per_gpu": 30,
+        },
+    }
+
+
+def result_line(args, world, elapsed, traced, rep, eng, collective, clock=None):
+    """--full: the headline plus the roofline of the dominant kernel and the per-kernel table of the traced pass.  ``clock``:
+    {"timed": ..., "traced": ..., "sysfs": ...} from the clock probe (None where it was not run)."""
+    B, H, W, K = args.batch, args.height, args.width, args.steps
     conv_flop, _ = eng.work_per_task()
     hp, wp = -(-H // 64) * 64, -(-W // 64) * 64
     dom = "resconv_c64"
@@ -1270,31 +1309,8 @@ def result_line(args, world, elapsed, traced, rep, eng, collective, clock=None):
             "realtime_ticks_per_event_us": round(ct["avg_ticks_per_launch"] / (avg_ms * 1e3), 3) if calls and avg_ms else None,
             "sysfs": clock.get("sysfs"),
         }
-    return {
-        # BASELINE.json's metric.  ONE meaning for `value` at every N (the bench contract's): the WHOLE-JOB aggregate over n_gpus — the
-        # driver divides by N itself; the per-GPU rate BASELINE.json's metric name speaks of is `per_gpu_frames_per_s` (== value at N = 1)
-        "metric": "interpolated frames/sec/GPU @1080p RIFE4.7 2x" + ("" if world == 1 else f" (value = aggregate over {world} GPUs; per GPU: per_gpu_frames_per_s)"),
-        "value": round(world * B * K / elapsed, 3),
-        "unit": "frames/s" if world == 1 else f"frames/s, whole job = sum over {world} GPUs (weak scaling: {B} pairs/step/GPU)",
-        "per_gpu_frames_per_s": round(B * K / elapsed, 3),
-        "n_gpus": world,
-        "steps": K,
-        "warmup": Wm,
-        "ms_per_step": round(elapsed / K * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"RIFE 4.7 2x, {H}x{W} synthetic frame-pair stream, {B} pairs/step/GPU resident in HBM "
-                        f"(BASELINE.json configs[1]; SURVEY 8d config 2 clip: {clip_frames(B)} frames torch.manual_seed(0) torch.rand); "
-                        f"seeded random-init weights",
-            "pairs_per_step_per_gpu": B,
-            "per_gpu_frames_per_s": round(B * K / elapsed, 3),
-            "new_frame_collective": collective,
-            "target_frames_per_s_per_gpu": 30,
-        },
+    res = headline(args, world, elapsed, collective)
+    res.update({
         "roofline": {
             "kernel": ("conv_wino_kernel<8> (Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32)" if wino else "conv_mfma2_kernel<s1,3x3> (direct implicit GEMM)")
                       + " as resconv_c64 (block3 ResConv 64->64 @%dx%d, batch %d)" % (hp // 4, wp // 4, B),
@@ -1328,7 +1344,8 @@ def result_line(args, world, elapsed, traced, rep, eng, collective, clock=None):
         "roofline_hbm": roofline_hbm,
         "conv_tflops_whole_net": round(conv_flop * B * K / elapsed / 1e12, 3),
         "kernels": kernels,
-    }
+    })
+    return res
 
 
 def extras_watchdog(res, rank, deadline_s):
@@ -1351,7 +1368,7 @@ def extras_watchdog(res, rank, deadline_s):
     return t
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -1359,6 +1376,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="frame pairs per step per GPU (1..32)")
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the line can carry: parity gate and cpu_baseline, clock, roofline and "
+                         "per-kernel figures, e2e, strong_4k_x4, other_paths (N > 1: the all-gather's cost, the sharded legs); --no-cpu-baseline, "
+                         "--no-parity, --no-e2e, --no-extras and --no-strong leave legs of it out, --peer-copy-leg adds one.  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle's timing (one forward still runs for the parity gate)")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity gate (and with it every oracle forward): profiling passes only")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive node leg")
@@ -1367,7 +1389,7 @@ def main():
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the all-gather of new frames")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling 4K x4 leg (BASELINE configs[3])")
     ap.add_argument("--peer-copy-leg", action="store_true",
-                    help="N>1: also run the extra weak-scaling leg that exchanges frames by IPC-mapped peer copies instead of a collective (opt-in: "
+                    help="N>1, with --full: also run the extra weak-scaling leg that exchanges frames by IPC-mapped peer copies instead of a collective (opt-in: "
                          "it has only ever run with its ranks on one GPU)")
     ap.add_argument("--reserve-cus", type=int, default=16,
                     help="N>1 over RCCL: compute units the persistent kernels leave to the overlapped all-gather's kernel (also caps "
@@ -1382,12 +1404,19 @@ def main():
     ap.add_argument("--device-threads", action="store_true",
                     help="one process driving N devices with host threads (multidev.py) instead of one process per GPU: opt-in for any N")
     ap.add_argument("--dry-run-ranks", type=int, default=0,
-                    help="plumbing check on ONE GPU: run the full N-rank control flow (weight broadcast, reserve trials, gather, strong leg, watchdog) "
-                         "as N gloo ranks that all use device 0; the numbers in the line mean nothing")
+                    help="plumbing check on ONE GPU: run the N-rank control flow (weight broadcast, reserve trials, gather; with --full also the "
+                         "strong leg, the sharded legs and the watchdog) as N gloo ranks that all use device 0; the numbers in the line mean nothing")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frames the last timed step computed (rank 0 / device 0) to DIR/<name>.npy, float32, "
                          "at most 64 MB in all (a fixed, seeded pixel sample when the step's output is larger): see dump_outputs()")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.peer_copy_leg and not args.full:
+        ap.error("--peer-copy-leg adds a leg to --full runs: pass --full as well")
+    return args
+
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.device_threads:
         return main_single_process(args)
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run_ranks > 1):
@@ -1471,11 +1500,11 @@ def main():
     raw_host = torch.rand((n_clip, H, W, 3), generator=g, dtype=torch.float32)
     raw = raw_host.to(dev)
     # The oracle on the pair the parity check will look at — task 0 of the LAST timed step — run BEFORE the GPU leg on the identical
-    # tensors; at N = 1 the same forwards are the cpu_baseline sample.
+    # tensors; at N = 1 the same forwards are the cpu_baseline sample.  --full only.
     par_base = clip_base(B, (K - 1) & 1)
     par_slots = sorted({0, B // 2, B - 1})      # first / middle / last task of the 32-task launch
     cpu_base, oracle_frames = None, None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         try:
             cpu_base, oracle_frames = cpu_baseline(sd, [(raw_host[par_base + j], raw_host[par_base + j + 1]) for j in par_slots],
                                                    timing=(world == 1 and not args.no_cpu_baseline))
@@ -1546,17 +1575,19 @@ def main():
             reserve_trials[cand] = float(t.item()) / 3
         reserve = min(reserve_trials, key=lambda c: (reserve_trials[c], c))
         _lib.check(_lib.load().vfi_set_reserved_cus(reserve), "vfi_set_reserved_cus")
-    # the timed region, with the clock probe installed (workgroup 0 of every Winograd launch stamps two counters: no launch, no sync,
-    # no extra kernel) and a side thread reading sclk / power from sysfs where the box has them
+    # the timed region; --full installs the clock probe around it (workgroup 0 of every Winograd launch stamps two counters: no launch,
+    # no sync, no extra kernel) and runs a side thread reading sclk / power from sysfs where the box has them
     clock = {}
     probe = None
-    try:
-        probe = ClockProbe(dev, K * 40 + 8)
-    except Exception as e:  # noqa: BLE001
-        clock["error"] = f"{type(e).__name__}: {e}"
-    with SysfsSampler(local_rank % ndev) as sampler:
+    if args.full:
+        try:
+            probe = ClockProbe(dev, K * 40 + 8)
+        except Exception as e:  # noqa: BLE001
+            clock["error"] = f"{type(e).__name__}: {e}"
+    with (SysfsSampler(local_rank % ndev) if args.full else contextlib.nullcontext()) as sampler:
         elapsed = timed(K)
-    clock["sysfs"] = sampler.summary()
+    if sampler is not None:
+        clock["sysfs"] = sampler.summary()
     if probe is not None:
         clock["timed"] = clock_summary(probe.finish(), "resconv_c64")
     # tasks 0 / B/2 / B-1 of the LAST timed step's launch
@@ -1568,7 +1599,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=ctl_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             # what the new-frame all-gather costs a step, two ways (both untimed extras, max over ranks): the same K steps WITHOUT the
             # collective (exposed cost = with - without: what overlap does not hide, including the compute units RCCL's kernel takes),
             # and the collective alone, back to back on an idle device (its own duration over xGMI)
@@ -1590,40 +1621,43 @@ def main():
                            "ms_per_step_without_gather": round(no_gather / K * 1e3, 3), "bytes_per_rank_per_step": B * H * W * 3 * 4,
                            "note": "exposed = ms_per_step - the same K steps without the collective; standalone = K all_gather_into_tensor calls back to back on an idle device"}
 
-    # ---- roofline leg: same K steps with per-kernel HIP events recorded on the launch stream (and the clock probe again: the
-    # event durations and the clock then belong to the same launches)
     lib = _lib.load()
-    try:
-        probe = ClockProbe(dev, K * 40 + 8)
-    except Exception:  # noqa: BLE001
-        probe = None
-    lib.vfi_trace_reset()
-    lib.vfi_trace_enable(1)
-    traced = timed(K)
-    lib.vfi_trace_enable(0)
-    rep = _lib.trace_report()
-    lib.vfi_trace_reset()
-    if probe is not None:
-        clock["traced"] = clock_summary(probe.finish(), "resconv_c64")
+    if args.full:
+        # ---- roofline leg: same K steps with per-kernel HIP events recorded on the launch stream (and the clock probe again: the
+        # event durations and the clock then belong to the same launches)
+        try:
+            probe = ClockProbe(dev, K * 40 + 8)
+        except Exception:  # noqa: BLE001
+            probe = None
+        lib.vfi_trace_reset()
+        lib.vfi_trace_enable(1)
+        traced = timed(K)
+        lib.vfi_trace_enable(0)
+        rep = _lib.trace_report()
+        lib.vfi_trace_reset()
+        if probe is not None:
+            clock["traced"] = clock_summary(probe.finish(), "resconv_c64")
     lib.vfi_set_reserved_cus(0)       # the later legs gather after their compute, not beside it
 
     res = None
     if rank == 0:
-        res = result_line(args, world, elapsed, traced, rep, eng,
-                          "none" if world == 1 or args.no_gather else
-                          ("all_gather(RCCL), overlapped" if gathered is not None else "all_gather(gloo, host)"), clock=clock)
-        # ---- in-run parity gate: the timed workload itself against the oracle (per-pixel fp32 |d| <= 1e-3, north_star)
-        if args.no_parity:
-            res["parity"] = {"skipped": "--no-parity"}
-        elif oracle_frames is None:
-            res["parity"] = {"ok": False, "error": (cpu_base or {}).get("error", "no oracle frame")}
+        collective = "none" if world == 1 or args.no_gather else ("all_gather(RCCL), overlapped" if gathered is not None else "all_gather(gloo, host)")
+        if not args.full:
+            res = headline(args, world, elapsed, collective)
         else:
-            per = [parity_of(g_, w_) for g_, w_ in zip(last_frames, oracle_frames)]
-            res["parity"] = {"max_abs": max(p["max_abs"] for p in per), "mean_abs": sum(p["mean_abs"] for p in per) / len(per),
-                             "n_over_1e-3": sum(p["n_over_1e-3"] for p in per), "values": sum(p["values"] for p in per), "tol": 1e-3,
-                             "ok": all(p["ok"] for p in per), "slots": par_slots, "per_slot_max_abs": [p["max_abs"] for p in per]}
-            res["parity"]["what"] = (f"tasks {par_slots} (first / middle / last) of the last timed step's {B}-task launch (pairs = clip frames {par_base}+j, {par_base}+j+1, "
-                                     f"t = 0.5) vs oracle.rife_oracle.ifnet47_forward on the same host tensors, all {H}x{W}x3 values of each")
+            res = result_line(args, world, elapsed, traced, rep, eng, collective, clock=clock)
+            # ---- in-run parity gate: the timed workload itself against the oracle (per-pixel fp32 |d| <= 1e-3, north_star)
+            if args.no_parity:
+                res["parity"] = {"skipped": "--no-parity"}
+            elif oracle_frames is None:
+                res["parity"] = {"ok": False, "error": (cpu_base or {}).get("error", "no oracle frame")}
+            else:
+                per = [parity_of(g_, w_) for g_, w_ in zip(last_frames, oracle_frames)]
+                res["parity"] = {"max_abs": max(p["max_abs"] for p in per), "mean_abs": sum(p["mean_abs"] for p in per) / len(per),
+                                 "n_over_1e-3": sum(p["n_over_1e-3"] for p in per), "values": sum(p["values"] for p in per), "tol": 1e-3,
+                                 "ok": all(p["ok"] for p in per), "slots": par_slots, "per_slot_max_abs": [p["max_abs"] for p in per]}
+                res["parity"]["what"] = (f"tasks {par_slots} (first / middle / last) of the last timed step's {B}-task launch (pairs = clip frames {par_base}+j, {par_base}+j+1, "
+                                         f"t = 0.5) vs oracle.rife_oracle.ifnet47_forward on the same host tensors, all {H}x{W}x3 values of each")
         if cpu_base is not None and "error" not in cpu_base:
             res["cpu_baseline"] = cpu_base
         res["config"]["launch"] = "one process per GPU (torch.distributed)" if world > 1 else "one process, one GPU"
@@ -1644,9 +1678,9 @@ def main():
     # (a collective whose peer died) cannot be recovered from inside the process, so a watchdog prints the headline line as it
     # stands and ends the rank instead of losing it to the launcher's timeout.
     parity_failed = False
-    guard = extras_watchdog(res, rank, args.extras_deadline) if world > 1 else None
+    guard = extras_watchdog(res, rank, args.extras_deadline) if world > 1 and args.full else None
     strong = None
-    if not args.no_strong:       # every rank takes part (strong scaling over the ranks)
+    if args.full and not args.no_strong:       # every rank takes part (strong scaling over the ranks)
         try:
             strong = strong_4k_x4(args, dev, world, rank, args.backend)
         except Exception as e:
@@ -1660,7 +1694,7 @@ def main():
             pc = {"error": f"{type(e).__name__}: {e}"}
         if rank == 0:
             res["weak_peer_copy_gather"] = pc
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         eng.release() if hasattr(eng, "release") else None
         try:
             dist_extras = other_paths_dist(dev, H, W, world, rank, args.backend)
@@ -1673,13 +1707,13 @@ def main():
     if rank == 0:
         if world == 1:
             eng.close()
-            if not args.no_e2e:
+            if args.full and not args.no_e2e:
                 res["e2e"] = e2e_leg(sd, dev, H, W)
                 try:      # a real (long) clip beside SURVEY's 33-frame one
                     res["e2e"]["long_clip"] = e2e_leg(sd, dev, H, W, n_frames=args.e2e_long_frames, reps=3, with_u8=False)
                 except Exception as e:  # noqa: BLE001  (never lose the line to an extra leg)
                     res["e2e"]["long_clip"] = {"error": f"{type(e).__name__}: {e}"}
-            if not args.no_extras:
+            if args.full and not args.no_extras:
                 res["other_paths"] = other_paths(dev, H, W, parity=not args.no_parity)
                 try:
                     res["other_paths"].update(other_nodes(dev, H, W, parity=not args.no_parity))

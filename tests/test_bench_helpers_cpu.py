@@ -3,12 +3,20 @@ import json
 import os
 import sys
 
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from oracle import golden_stats  # noqa: E402
+
+
+def test_plain_run_is_the_default():
+    assert not bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full
+    assert bench.parse_args(["--full", "--no-e2e"]).full
+    with pytest.raises(SystemExit):      # a leg of --full asked for without it is an error, not a silent no-op
+        bench.parse_args(["--gpus", "2", "--peer-copy-leg"])
 
 
 def test_parity_of_is_the_per_pixel_gate():

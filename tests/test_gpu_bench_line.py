@@ -1,7 +1,7 @@
 """-m gpu: bench.py's JSON line carries what the measurement contract asks for — a small configuration so
-that the test takes seconds: `roofline.frac` is a hardware utilisation (<= 1) with the direct-form figure under
+that the test takes seconds: with --full, `roofline.frac` is a hardware utilisation (<= 1) with the direct-form figure under
 `algorithmic_equiv`, the frame pack is in `roofline_hbm`, the strong-scaling 4K x4 leg is present (here at a reduced size), and the
-two-rank launch (gloo on the one GPU) shards that leg's task list unevenly."""
+two-rank launch (gloo on the one GPU) shards that leg's task list unevenly; without it, the line is the headline alone."""
 import json
 import os
 import subprocess
@@ -12,8 +12,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--height", "272", "--width", "480", "--batch", "4", "--steps", "1", "--warmup", "1", "--no-e2e", "--no-cpu-baseline",
-         "--strong-height", "136", "--strong-width", "240", "--strong-frames", "4", "--strong-reps", "1"]
+SIZE = ["--height", "272", "--width", "480", "--batch", "4", "--steps", "1", "--warmup", "1"]
+SMALL = ["--full"] + SIZE + ["--no-e2e", "--no-cpu-baseline", "--strong-height", "136", "--strong-width", "240", "--strong-frames", "4", "--strong-reps", "1"]
 
 
 def _line(out):
@@ -73,6 +73,37 @@ def test_single_gpu_line(hip_lib, tmp_path):
     assert res["steps"] == 1 and res["dumped_outputs"]["files"] == {"frames.npy": [4, 272, 480, 3]}, res.get("dumped_outputs")
     frames = np.load(dump / "frames.npy")
     assert frames.dtype == np.float32 and np.isfinite(frames).all() and 0.0 <= frames.min() and frames.max() <= 1.0
+
+
+def test_plain_line_is_the_headline_only(hip_lib, tmp_path, oracle_threads):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the headline keys — none of the legs --full adds.  The
+    in-run gate is one of those legs, so the dumped frame of task 0 is checked against the oracle here."""
+    import torch
+
+    import bench
+    from cfi_amd import synth
+    from oracle import rife_oracle
+
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SIZE + ["--dump-outputs", str(dump)], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    res = _line(r.stdout)
+    assert res["metric"] == "interpolated frames/sec/GPU @1080p RIFE4.7 2x" and res["unit"] == "frames/s" and res["dtype"] == "f32", res
+    assert res["higher_is_better"] is True and res["n_gpus"] == 1 and res["steps"] == 1 and res["warmup"] == 1
+    assert res["ms_per_step"] > 0 and abs(res["value"] - 4 * 1e3 / res["ms_per_step"]) <= 1e-3 * res["value"], res      # 4 pairs per step
+    legs = {"parity", "cpu_baseline", "clock", "roofline", "roofline_hbm", "kernels", "conv_tflops_whole_net", "strong_4k_x4", "e2e", "other_paths"}
+    assert not legs & set(res) and res["all_gather_ms_per_step"] is None, sorted(res)
+    assert res["dumped_outputs"]["files"] == {"frames.npy": [4, 272, 480, 3]}, res.get("dumped_outputs")
+    frames = torch.from_numpy(np.load(dump / "frames.npy"))
+    # task 0 of the last (only) timed step: clip frames base, base + 1 of the rank-0 clip (torch.rand, generator seeded 0)
+    clip = torch.rand((bench.clip_frames(4), 272, 480, 3), generator=torch.Generator(device="cpu").manual_seed(0), dtype=torch.float32)
+    base = bench.clip_base(4, 0)
+    x0, x1 = (clip[base + j].permute(2, 0, 1).unsqueeze(0).contiguous() for j in (0, 1))
+    with torch.inference_mode():
+        want = rife_oracle.ifnet47_forward(synth.rife47_synth_state_dict(1234), x0, x1, torch.tensor([0.5]).view(1, 1, 1, 1)).clamp(0, 1)[0].permute(1, 2, 0)
+    p = bench.parity_of(frames[0], want)
+    assert p["ok"] and p["n_over_1e-3"] == 0, p
 
 
 def test_two_rank_line_shards_the_strong_leg(hip_lib):
