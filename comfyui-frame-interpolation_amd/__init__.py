@@ -15,6 +15,7 @@ _LAZY = {
     "IFUnet_VFI": ("ifunet", "IFUnet_VFI"),
     "CAIN_VFI": ("cain", "CAIN_VFI"),
     "SepconvVFI": ("sepconv", "SepconvVFI"),
+    "FLAVR_VFI": ("flavr", "FLAVR_VFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -51,6 +52,10 @@ def _node_class_mappings():
         from .sepconv import SepconvVFI
 
         extra["Sepconv VFI"] = SepconvVFI
+    if "flavr_vfi" in extra_nodes():
+        from .flavr import FLAVR_VFI
+
+        extra["FLAVR VFI"] = FLAVR_VFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -65,7 +70,9 @@ def _node_class_mappings():
 
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
 # list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
-EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)")}
+# FLAVR's key is the reference's class name lower-cased, "flavr_vfi"; a bare "flavr" is not a key.
+EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
+               "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)")}
 
 
 def extra_nodes():

@@ -1,0 +1,147 @@
+"""FLAVR VFI node — host-side mirror of the reference's ``FLAVR_VFI`` over the HIP library.
+
+Node shape follows vfi_models/flavr/__init__.py:28-115.  Unlike every pair-at-a-time node, FLAVR reads a window of four frames
+(i .. i + 3) and writes one new frame between frames i + 1 and i + 2; the reference's private loop is restated by ``window_plan``
+(quirks included) and run by ``run_windows``: a sliding window of four device frames, each frame uploaded once.  Each model call is
+one vfi_flavr_forward (csrc/flavr_net.hip: InputPadder(16), window mean, 3D U-Net, un-pad).  No clamp; the multiplier is always 2.
+No pair lanes, no multi-rank sharding and no HIP graph for this node.
+"""
+import ctypes as C
+import typing
+import warnings
+
+import torch
+
+from . import _lib
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
+from .flavr_spec import flavr_shapes, load_file, n_outputs_of
+from .schedule import InterpolationStateList
+
+MODEL_TYPE = "flavr"
+CKPT_NAMES = ["FLAVR_2x.pth", "FLAVR_4x.pth", "FLAVR_8x.pth"]
+NBR_FRAME = 4
+
+
+class FlavrEngine:
+    """Device-resident FLAVR: ``forward(frames)`` = ``unpad(model([pad(f) for f in window])[0])`` for a batch of windows in one call."""
+
+    def __init__(self, state_dict, device=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("FLAVR VFI (HIP): no GPU visible; this node has no CPU fallback")
+        self.lib = _lib.load()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
+        self.n_outputs = n_outputs_of(state_dict)
+        keys = list(flavr_shapes(self.n_outputs).keys())
+        tensors = [state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in keys]
+        ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
+        numels = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
+        self.handle = self.lib.vfi_flavr_create(ptrs, numels, len(keys), self.n_outputs)
+        if not self.handle:
+            raise RuntimeError("vfi_flavr_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.vfi_flavr_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def release_workspace(self):
+        _lib.check(self.lib.vfi_flavr_release_workspace(self.handle), "vfi_flavr_release_workspace")
+
+    def workspace_bytes(self):
+        return int(self.lib.vfi_flavr_workspace_bytes(self.handle)) if getattr(self, "handle", None) else 0
+
+    def forward(self, frames, out=None):
+        """frames: a sequence of 4 N [H,W,C>=3] fp32 contiguous device tensors (window n = frames[4n : 4n+4]; not written) -> [N,H,W,3]."""
+        assert len(frames) > 0 and len(frames) % NBR_FRAME == 0, "frames: four per window"
+        n = len(frames) // NBR_FRAME
+        H, W, Cc = frames[0].shape
+        for f in frames:
+            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        if out is None:
+            out = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.device)
+        p = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
+        _lib.check(self.lib.vfi_flavr_forward(self.handle, p, n, Cc, H, W, out.data_ptr(), _lib.stream_ptr()), "vfi_flavr_forward")
+        return out
+
+
+def window_plan(n_frames, duplicate_first_last_frames=False, states: InterpolationStateList = None):
+    """The reference loop's output (vfi_models/flavr/__init__.py:72-97) as ``("src", frame)`` / ``("new", window)`` entries in order.
+    Window i (frames i .. i + 3) is skipped only when frames i AND i + 1 are skipped.  The leading frames 0, 1 are emitted by window 0
+    and the trailing frame by the last window, so skipping those windows drops them too — as the reference does."""
+    plan = []
+    for i in range(n_frames - 3):
+        if states is not None and states.is_frame_skipped(i) and states.is_frame_skipped(i + 1):
+            continue
+        if i == 0:
+            plan.append(("src", 0))
+            if duplicate_first_last_frames:
+                plan.append(("src", 0))
+            plan.append(("src", 1))
+        plan += [("new", i), ("src", i + 2)]
+        if i == n_frames - 4:
+            plan.append(("src", i + 3))
+            if duplicate_first_last_frames:
+                plan.append(("src", i + 3))
+    return plan
+
+
+def run_windows(engine, frames, plan):
+    """frames [N,H,W,C] host tensor, plan of window_plan -> [len(plan),H,W,3] fp32 host tensor.  A frame goes to the device when the first
+    window that reads it runs and is dropped after the last one."""
+    if not plan:      # (the reference fails in torch.cat of an empty list)
+        raise RuntimeError("FLAVR VFI: every window was skipped - nothing to output")
+    frames = frames[..., :3]
+    H, W = frames.shape[1:3]
+    out = torch.empty((len(plan), H, W, 3), dtype=torch.float32)
+    dev = engine.device
+    held = {}
+    for row, (kind, idx) in enumerate(plan):
+        if kind == "src":
+            out[row] = frames[idx]
+            continue
+        for f in [f for f in held if f < idx]:
+            del held[f]
+        for f in range(idx, idx + NBR_FRAME):
+            if f not in held:
+                held[f] = frames[f].to(dev, torch.float32).contiguous()
+        out[row] = engine.forward([held[f] for f in range(idx, idx + NBR_FRAME)])[0].cpu()
+    return out
+
+
+class FLAVR_VFI:
+    @classmethod
+    def INPUT_TYPES(s):
+        return {
+            "required": {
+                "ckpt_name": (CKPT_NAMES,),
+                "frames": ("IMAGE",),
+                "clear_cache_after_n_frames": ("INT", {"default": 10, "min": 1, "max": 1000}),
+                "multiplier": ("INT", {"default": 2, "min": 2, "max": 2}),
+                "duplicate_first_last_frames": ("BOOLEAN", {"default": False}),
+            },
+            "optional": {"optional_interpolation_states": ("INTERPOLATION_STATES",)},
+        }
+
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "vfi"
+    CATEGORY = "ComfyUI-Frame-Interpolation/VFI"
+
+    def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10, multiplier: typing.SupportsInt = 2,
+            duplicate_first_last_frames: bool = False, optional_interpolation_states: InterpolationStateList = None, **kwargs):
+        if multiplier != 2:
+            warnings.warn("Currently, FLAVR only supports 2x interpolation. The process will continue but please set multiplier=2 afterward")
+        # (vfi_utils.assert_batch_size(frames, batch_size=4, vfi_name="ST-MFNet"): the reference names the wrong model here, kept)
+        assert len(frames) >= NBR_FRAME, (f"VFI model ST-MFNet requires at least 4 frames to work with, only found {frames.shape[0]}. "
+                                          "Please check the frame input using PreviewImage.")
+        plan = window_plan(len(frames), duplicate_first_last_frames, optional_interpolation_states)
+        model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
+        entry = cached_engine(MODEL_TYPE, model_path, lambda: FlavrEngine(load_file(model_path)))
+        with engine_call(entry, tuple(frames.shape[1:3])) as engine:
+            return (run_windows(engine, frames, plan),)

@@ -634,6 +634,53 @@ int vfi_sepconvnet_forward(vfi_sepconvnet_t* net, const float* const* frame0_dev
 int vfi_sepconvnet_release_workspace(vfi_sepconvnet_t* net);
 int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* net);
 
+/* ---- FLAVR (vfi_models/flavr/flavr_arch.py UNet_3D_3D("unet_18", 4 inputs, "concat", "transpose"), resnet_3D.py) ------------------- */
+
+/* In the functions below a tensor with four time slices is addressed as base + pixel * ps + t * ss + channel (ps = pixel stride, ss =
+ * slice stride, in floats, multiples of 4; base 16-byte aligned), which covers the network's bordered [H, W, 6, C] feature maps (base at
+ * slice 1, ps = 6 C, ss = C), halves of concat buffers and plain [H, W, 4, C] tensors alike. */
+
+/* FLAVR frame-in for a window of four [H,W,C] fp32 frames (frames_dev = host array of 4 device pointers; C >= 3, channels 0..2 used; not
+ * written): replicate padding to Hp x Wp = multiples of 16, floor half before (InputPadder(16), flavr_arch.py:200-209); mean_dev[c] = mean
+ * of channel c over the four padded frames (mean_dev[3] = 0); out_dev [Hp, Wp, 4, 4] = (frame_t - mean, 0) time-interleaved.  The mean
+ * is deterministic: 256 fixed slots summed in order.  workspace_dev >= 4 KiB. */
+int vfi_flavr_frame_in(const float* const* frames_dev, int C, int H, int W, float* out_dev, float* mean_dev, float* workspace_dev, int64_t workspace_bytes,
+                       void* stream);
+/* FLAVR stem: relu(Conv3d(3, 64, (3,7,7), stride (1,2,2), padding (1,3,3))(x)) for x_dev [Hp, Wp, 4, 4] (frame-in's layout), w_dev
+ * [64,3,3,7,7] and bias_dev [64] (nullable) on the device; output pixel (y, x) of ceil(Hp/2) x ceil(Wp/2), slice t, channel c at
+ * out_dev[(y * Wo + x) * out_cs + t * 64 + c].  workspace_dev >= 112896 bytes (the repacked weights). */
+int vfi_flavr_stem(const float* x_dev, int Hp, int Wp, const float* w_dev, const float* bias_dev, float* out_dev, int out_cs, float* workspace_dev,
+                   int64_t workspace_bytes, void* stream);
+/* Conv3d(Cin, Cout, 1, stride (1, s, s), bias=False), s = 1 or 2 (BasicBlock.downsample): conv1x1 = a vfi_conv_create_ex(0, w, NULL, Cout,
+ * Cin, 1, 1, ...) object; the input (ps / ss addressing, Hin x Win pixels) is sub-sampled into sub_dev [h, w, 4, Cin] (h = ceil(Hin / s))
+ * and out_dev [h, w, 4, Cout] is the 1x1 layer on the MFMA kernel over it. */
+int vfi_flavr_down1x1(const vfi_conv_t* conv1x1, int Cin, int Cout, const float* in_dev, int64_t in_ps, int64_t in_ss, int Hin, int Win, int stride,
+                      float* sub_dev, float* out_dev, void* stream);
+/* SEGating fused with what follows it: y = sigmoid(b + w . mean_{pixels, t} x) (w_dev [C][C], b_dev [C]; resnet_3D.py:100-116), then
+ * mode 0: out = relu(x * y + res) (BasicBlock, :140-151), mode 1: out = leaky_relu(x * y, 0.2) (decoder, flavr_arch.py:176-188).  x, res
+ * and out in ps / ss addressing over `pixels` pixels; out may alias x.  C % 4 == 0, C <= 1024.  Deterministic: at most 1024 fixed slots
+ * summed in order.  workspace_dev >= (1024 * C + C) floats. */
+int vfi_flavr_gate(const float* x_dev, int64_t x_ps, int64_t x_ss, const float* res_dev, int64_t res_ps, int64_t res_ss, float* out_dev, int64_t out_ps,
+                   int64_t out_ss, int64_t pixels, int C, const float* w_dev, const float* b_dev, int mode, float* workspace_dev, int64_t workspace_bytes,
+                   void* stream);
+/* FLAVR frame-out: Conv2d(64, 3, 7)(ReflectionPad2d(3)(feat)) + bias + mean for the H x W crop at (pad_top, pad_left) of feat_dev
+ * [Hp, Wp, 64] (Hp, Wp >= 4): w_dev [>= 3, 64, 7, 7] (the first three output channels are used), bias_dev [>= 3], mean_dev [>= 3] on the
+ * device, out_dev [H, W, 3].  No clamp.  workspace_dev >= 50176 bytes. */
+int vfi_flavr_frame_out(const float* feat_dev, int Hp, int Wp, const float* w_dev, const float* bias_dev, const float* mean_dev, int pad_top, int pad_left,
+                        int H, int W, float* out_dev, float* workspace_dev, int64_t workspace_bytes, void* stream);
+
+typedef struct vfi_flavr vfi_flavr_t;
+/* The state_dict tensors of FLAVR in flavr_spec.flavr_shapes(n_outputs) order (59 for n_outputs == 1, else 76; fp32 host memory, copied). */
+vfi_flavr_t* vfi_flavr_create(const float* const* tensors, const int64_t* numels, int n_tensors, int n_outputs);
+void vfi_flavr_destroy(vfi_flavr_t* net);
+/* unpad(model([pad(f) for f in window])[0]) for N windows in one call (vfi_models/flavr/__init__.py:67-84): frames_dev = host array of 4 N
+ * device pointers to [H,W,C] fp32 frames (window n = pointers 4 n .. 4 n + 3; C >= 3; not written), out_dev [N,H,W,3].  The windows run
+ * one after another through the same launches as a call with one window, so a window's result does not depend on its batch mates; the
+ * workspace is sized for one window.  Frames whose padded size exceeds 2^21 - 1 pixels (1088 x 1920 fits) are refused before any launch. */
+int vfi_flavr_forward(vfi_flavr_t* net, const float* const* frames_dev, int N, int C, int H, int W, float* out_dev, void* stream);
+int vfi_flavr_release_workspace(vfi_flavr_t* net);
+int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* net);
+
 #ifdef __cplusplus
 }
 #endif
