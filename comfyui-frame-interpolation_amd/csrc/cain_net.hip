@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/vfi_hip.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -220,7 +221,7 @@ int ca_launch(const float* t, const float* x, float* out, int N, long hw, int C,
 
 }  // namespace
 
-struct vfi_cain {
+struct vfi_cain : NetObject {
     vfi_conv_t* head = nullptr;
     vfi_conv_t* tail = nullptr;
     vfi_conv_t* body[GROUPS][BLOCKS][2] = {};
@@ -228,38 +229,25 @@ struct vfi_cain {
     float* ca = nullptr;               // per RCAB: w1 [12][192], b1 [12], w2 [192][12], b2 [192]
     // workspace, for N pairs of h x w feature maps
     int N = 0, h = 0, w = 0;
-    float *in = nullptr, *x0 = nullptr, *g[2] = {}, *cur = nullptr, *t1 = nullptr, *t2 = nullptr, *ws = nullptr, *means = nullptr;
-    int64_t bytes = 0;
+    float *in = nullptr, *x0 = nullptr, *g[2] = {}, *cur = nullptr, *t1 = nullptr, *t2 = nullptr, *cws = nullptr, *means = nullptr;
 };
 
 namespace {
 
 constexpr size_t CA_FLOATS = (size_t)RED * FEAT + RED + FEAT * RED + FEAT;
 
-void free_workspace(vfi_cain* m) {
-    for (float* p : {m->in, m->x0, m->g[0], m->g[1], m->cur, m->t1, m->t2, m->ws, m->means})
-        if (p) (void)hipFree(p);
-    m->in = m->x0 = m->g[0] = m->g[1] = m->cur = m->t1 = m->t2 = m->ws = m->means = nullptr;
-    m->N = m->h = m->w = 0;
-    m->bytes = 0;
-}
-
 int ensure_workspace(vfi_cain* m, int N, int h, int w) {
-    if (m->N >= N && m->h == h && m->w == w) return 0;
-    free_workspace(m);
+    if (m->ws.live() && m->N >= N && m->h == h && m->w == w) return 0;
+    if (m->ws.release()) return -1;
     const size_t px = (size_t)N * h * w;
     float** feats[] = {&m->x0, &m->g[0], &m->g[1], &m->cur, &m->t1, &m->t2};
-    auto get = [&](float** p, size_t floats) -> int {
-        VFI_CHECK_HIP(hipMalloc((void**)p, floats * sizeof(float)));
-        m->bytes += (int64_t)(floats * sizeof(float));
-        return 0;
-    };
+    auto get = [&](float** p, size_t floats) { return m->ws.alloc(p, floats, Workspace::kNoFill, nullptr); };
     if (get(&m->in, px * 2 * FEAT)) return -1;
     for (float** f : feats)
         if (get(f, px * FEAT)) return -1;
     // channel-attention partials + scales, and the frame-in row partials (2 frames x MEAN_SLOTS x 3 per pair)
     const size_t ws = std::max((size_t)N * (CA_SLOTS + 1) * FEAT, (size_t)MEAN_SLOTS * 3);
-    if (get(&m->ws, ws) || get(&m->means, (size_t)N * 6)) return -1;
+    if (get(&m->cws, ws) || get(&m->means, (size_t)N * 6)) return -1;
     m->N = N, m->h = h, m->w = w;
     return 0;
 }
@@ -279,34 +267,22 @@ vfi_cain_t* vfi_cain_create(const float* const* tensors, const int64_t* numels, 
         return nullptr;
     }
     vfi_cain* m = new vfi_cain();
-    int k = 0;
-    bool ok = true;
-    auto take = [&](int64_t n) -> const float* {
-        if (!ok) return nullptr;
-        if (numels[k] != n || !tensors[k]) {
-            set_error("vfi_cain_create: tensor %d has %lld elements, expected %lld", k, (long long)numels[k], (long long)n);
-            ok = false;
-            return nullptr;
-        }
-        return tensors[k++];
-    };
+    TensorCursor cur(tensors, numels, n_tensors, "vfi_cain_create");
     auto make = [&](vfi_conv_t** L, int cin, int pad_mode) {
-        const float* w = take((int64_t)FEAT * cin * 9);
-        const float* b = take(FEAT);
-        if (!ok) return;
-        *L = vfi_conv_create_ex(0, w, b, FEAT, cin, 3, 1, pad_mode, nullptr, cin, nullptr);
-        if (!*L) ok = false;
+        const float* w = cur.take((int64_t)FEAT * cin * 9);
+        const float* b = cur.take(FEAT);
+        if (cur.ok()) *L = m->add_layer(vfi_conv_create_ex(0, w, b, FEAT, cin, 3, 1, pad_mode, nullptr, cin, nullptr));
     };
     std::vector<float> ca((size_t)GROUPS * BLOCKS * CA_FLOATS);
     make(&m->head, 2 * FEAT, 0);                               // conv3x3: zero padding (common.py:247-256)
-    for (int gi = 0; gi < GROUPS && ok; ++gi) {
-        for (int bi = 0; bi < BLOCKS && ok; ++bi) {
+    for (int gi = 0; gi < GROUPS && cur.ok(); ++gi) {
+        for (int bi = 0; bi < BLOCKS && cur.ok(); ++bi) {
             make(&m->body[gi][bi][0], FEAT, 2);                // ConvNorm: ReflectionPad2d(1) + Conv2d (common.py:26-45)
             make(&m->body[gi][bi][1], FEAT, 2);
             float* dst = ca.data() + (size_t)(gi * BLOCKS + bi) * CA_FLOATS;
             const int64_t sizes[4] = {(int64_t)RED * FEAT, RED, (int64_t)FEAT * RED, FEAT};
-            for (int i = 0; i < 4 && ok; ++i) {
-                const float* s = take(sizes[i]);
+            for (int i = 0; i < 4; ++i) {
+                const float* s = cur.take(sizes[i]);
                 if (s) memcpy(dst, s, sizes[i] * sizeof(float));
                 dst += sizes[i];
             }
@@ -314,40 +290,22 @@ vfi_cain_t* vfi_cain_create(const float* const* tensors, const int64_t* numels, 
         make(&m->gconv[gi], FEAT, 2);
     }
     make(&m->tail, FEAT, 0);
-    if (ok && (hipMalloc((void**)&m->ca, ca.size() * sizeof(float)) != hipSuccess ||
-               hipMemcpy(m->ca, ca.data(), ca.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("vfi_cain_create: device allocation/upload failed");
-        ok = false;
-    }
-    if (!ok) {
+    if (cur.finish()) m->ca = m->upload(ca.data(), ca.size());
+    if (!cur.ok() || m->failed) {
         vfi_cain_destroy(m);
         return nullptr;
     }
     return m;
 }
 
-void vfi_cain_destroy(vfi_cain_t* m) {
-    if (!m) return;
-    free_workspace(m);
-    vfi_conv_destroy(m->head);
-    vfi_conv_destroy(m->tail);
-    for (int gi = 0; gi < GROUPS; ++gi) {
-        vfi_conv_destroy(m->gconv[gi]);
-        for (int bi = 0; bi < BLOCKS; ++bi)
-            for (int j = 0; j < 2; ++j) vfi_conv_destroy(m->body[gi][bi][j]);
-    }
-    if (m->ca) (void)hipFree(m->ca);
-    delete m;
-}
+void vfi_cain_destroy(vfi_cain_t* m) { delete m; }
 
 int vfi_cain_release_workspace(vfi_cain_t* m) {
     VFI_REQUIRE(m, "vfi_cain_release_workspace: null object");
-    VFI_CHECK_HIP(hipDeviceSynchronize());      // kernels of the last forward may still read the buffers
-    free_workspace(m);
-    return 0;
+    return m->ws.release();
 }
 
-int64_t vfi_cain_workspace_bytes(const vfi_cain_t* m) { return m ? m->bytes : 0; }
+int64_t vfi_cain_workspace_bytes(const vfi_cain_t* m) { return m ? m->ws.bytes() : 0; }
 
 int vfi_cain_frame_in(const float* frame_dev, int C, int H, int W, float* out_dev, int out_cs, float* mean_dev, float* workspace_dev,
                       int64_t workspace_bytes, void* stream) {
@@ -412,7 +370,7 @@ int vfi_cain_forward(vfi_cain_t* m, const float* const* frame0_dev, const float*
     for (int n = 0; n < N; ++n)
         for (int f = 0; f < 2; ++f)
             if (int rc = vfi_cain_frame_in(f ? frame1_dev[n] : frame0_dev[n], C, H, W, m->in + (size_t)n * hw * 2 * FEAT + f * FEAT, 2 * FEAT,
-                                           m->means + n * 6 + f * 3, m->ws, (int64_t)MEAN_SLOTS * 3 * 4, st))
+                                           m->means + n * 6 + f * 3, m->cws, (int64_t)MEAN_SLOTS * 3 * 4, st))
                 return rc;
     if (conv(m->head, m->in, 2 * FEAT, m, N, m->x0, 0, nullptr, st)) return -1;
     const float* gin = m->x0;
@@ -423,7 +381,7 @@ int vfi_cain_forward(vfi_cain_t* m, const float* const* frame0_dev, const float*
             if (conv(m->body[gi][bi][0], x, FEAT, m, N, m->t1, 1, nullptr, st) || conv(m->body[gi][bi][1], m->t1, FEAT, m, N, m->t2, 0, nullptr, st))
                 return -1;
             const float* ca = m->ca + (size_t)(gi * BLOCKS + bi) * CA_FLOATS;
-            if (ca_launch(m->t2, x, m->cur, N, hw, FEAT, ca, ca + RED * FEAT, ca + RED * FEAT + RED, ca + 2 * RED * FEAT + RED, RED, m->ws, st))
+            if (ca_launch(m->t2, x, m->cur, N, hw, FEAT, ca, ca + RED * FEAT, ca + RED * FEAT + RED, ca + 2 * RED * FEAT + RED, RED, m->cws, st))
                 return -1;
             x = m->cur;
         }

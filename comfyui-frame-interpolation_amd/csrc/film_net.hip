@@ -9,14 +9,11 @@
 // a channel-window offset, physical channel positions are translated once through chan_map at weight-pack time.
 // (Round 1 issued the same sequence from Python, ~330 ctypes calls per pair; the Python FilmEngine now wraps this object.)
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/vfi_hip.h"
 #include "../../include/vfi_hip_test.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -32,11 +29,6 @@ int feat_channels(int level) {   // 64, 192, 448, 960, 960, ...
     for (int j = 0; j <= std::min(level, SUB - 1); ++j) s += FILTERS << j;
     return s;
 }
-
-struct Ten {   // [h][w][c] fp32, zero-initialised at allocation (padded channel positions must hold finite values)
-    float* p = nullptr;
-    int h = 0, w = 0, c = 0;
-};
 
 struct Layer {
     vfi_conv_t* h = nullptr;
@@ -58,7 +50,7 @@ std::vector<int> aligned_map(int F) {
 
 }  // namespace
 
-struct vfi_film {
+struct vfi_film : NetObject {
     Layer ext[SUB][2];
     Layer pred[4][5];          // [min(level, 3)][conv]
     Layer fuse[4][3];
@@ -66,7 +58,7 @@ struct vfi_film {
     int fuse_nf[4] = {0, 0, 0, 0};
     Layer out_conv;
     int cal[FUS] = {0, 0, 0, 0, 0};
-    // workspace for the current frame size
+    // workspace for the current frame size (every Ten [1][h][w][c], zero-initialised: padded channel positions must hold finite values)
     int H = 0, W = 0;
     int hw[PYR][2];
     Ten img[2][PYR], tw[2][PYR], flow[2][PYR], vres[2][PYR], vup[2][PYR], al[FUS];      // vres / vup: per flow direction (r6: the two run side by side)
@@ -75,36 +67,16 @@ struct vfi_film {
     bool two_streams = true;       // vfi_film_two_streams
     hipStream_t side = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::map<std::tuple<std::string, int, int, int>, Ten> scratch;
-    std::vector<float*> owned;
 };
 
 namespace {
 
-int alloc_ten(vfi_film* n, Ten& t, int h, int w, int c, hipStream_t st = nullptr) {
-    t.h = h, t.w = w, t.c = c;
-    const size_t bytes = (size_t)h * w * c * sizeof(float);
-    VFI_CHECK_HIP(hipMalloc((void**)&t.p, bytes));
-    n->owned.push_back(t.p);
-    // zero fill ordered with the forward's kernels: a NULL-stream memset is not ordered against a non-blocking side stream (torch's)
-    // and could clear a lazily allocated scratch tensor AFTER its first producer ran
-    VFI_CHECK_HIP(hipMemsetAsync(t.p, 0, bytes, st));
-    if (!st) VFI_CHECK_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-void free_workspace(vfi_film* n) {
-    for (float* p : n->owned) (void)hipFree(p);
-    n->owned.clear();
-    n->scratch.clear();
-    n->H = n->W = 0;
-}
+int alloc_ten(vfi_film* n, Ten& t, int h, int w, int c) { return n->ws.ten(t, 1, h, w, c, nullptr); }
 
 int ensure_workspace(vfi_film* n, int H, int W) {
-    if (n->H == H && n->W == W) return 0;
+    if (n->ws.live() && n->H == H && n->W == W) return 0;
     VFI_REQUIRE(H >= 64 && W >= 64, "vfi_film_forward: FILM needs 7 pyramid levels (>= 64 px per side), got %dx%d", H, W);
-    VFI_CHECK_HIP(hipDeviceSynchronize());
-    free_workspace(n);
+    if (n->ws.release()) return -1;
     n->hw[0][0] = H, n->hw[0][1] = W;
     for (int l = 1; l < PYR; ++l) n->hw[l][0] = n->hw[l - 1][0] / 2, n->hw[l][1] = n->hw[l - 1][1] / 2;
     for (int l = 0; l < PYR; ++l) {
@@ -120,17 +92,7 @@ int ensure_workspace(vfi_film* n, int H, int W) {
     return 0;
 }
 
-int tmp(vfi_film* n, const char* name, int h, int w, int c, Ten** out) {
-    auto key = std::make_tuple(std::string(name), h, w, c);
-    auto it = n->scratch.find(key);
-    if (it == n->scratch.end()) {
-        Ten t;
-        if (alloc_ten(n, t, h, w, c)) return -1;
-        it = n->scratch.emplace(key, t).first;
-    }
-    *out = &it->second;
-    return 0;
-}
+int tmp(vfi_film* n, const char* name, int h, int w, int c, Ten** out) { return n->ws.tmp(name, 1, h, w, c, out); }
 
 int conv(const Layer& L, const Ten& src, int src_off, const Ten& dst, int dst_off, int h, int w, int act, hipStream_t st) {
     return vfi_conv_forward(L.h, src.p + src_off, src.c, dst.p + dst_off, dst.c, 1, h, w, act, 0.2f, st);
@@ -212,22 +174,18 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
         return nullptr;
     }
     vfi_film* net = new vfi_film();
-    int k = 0;
-    bool ok = true;
-    auto make = [&](Layer& L, int cout, int cin, int kk, const std::vector<int>* cmap, int cin_phys) {
-        if (!ok) return;
-        const int64_t wn = (int64_t)cout * cin * kk * kk;
-        if (k + 1 >= n_tensors || numels[k] != wn || numels[k + 1] != cout) {
-            set_error("vfi_film_create: tensor %d has %lld elements, expected %lld (weight of a %d->%d %dx%d conv)", k,
-                      (long long)numels[k], (long long)wn, cin, cout, kk, kk);
-            ok = false;
-            return;
-        }
+    TensorCursor cur(tensors, numels, n_tensors, "vfi_film_create");
+    // up2: the same weights once more in the "up-sample x2 first" form
+    auto make = [&](Layer& L, int cout, int cin, int kk, const std::vector<int>* cmap, int cin_phys, Layer* up2 = nullptr) {
+        const float* w = cur.take((int64_t)cout * cin * kk * kk);
+        const float* b = cur.take(cout);
+        if (!cur.ok()) return;
         L.cout = cout;
         L.cin_phys = cin_phys > 0 ? cin_phys : r8(cin);
-        L.h = vfi_conv_create(tensors[k], tensors[k + 1], cout, cin, kk, kk, cmap ? cmap->data() : nullptr, L.cin_phys);
-        k += 2;
-        if (!L.h) ok = false;
+        L.h = net->add_layer(vfi_conv_create(w, b, cout, cin, kk, kk, cmap ? cmap->data() : nullptr, L.cin_phys));
+        if (!up2) return;
+        up2->cout = cout, up2->cin_phys = L.cin_phys;
+        up2->h = net->add_layer(vfi_conv_create_up2x2(w, b, cout, cin, cmap ? cmap->data() : nullptr, L.cin_phys));
     };
     // extract.extract_sublevels.convs.{i}.{0,1}.0
     int cin = 3;
@@ -258,19 +216,9 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
         net->fuse_nf[f] = nf;
         if (f == 0) {
             const std::vector<int> m = aligned_map(feat_channels(4));
-            make(net->fuse[f][0], nf, below, 2, &m, net->cal[4]);
-            if (ok) {
-                net->fuse_up2[f].cout = nf, net->fuse_up2[f].cin_phys = net->cal[4];
-                net->fuse_up2[f].h = vfi_conv_create_up2x2(tensors[k - 2], tensors[k - 1], nf, below, m.data(), net->cal[4]);
-                if (!net->fuse_up2[f].h) ok = false;
-            }
+            make(net->fuse[f][0], nf, below, 2, &m, net->cal[4], &net->fuse_up2[f]);
         } else {
-            make(net->fuse[f][0], nf, below, 2, nullptr, 0);
-            if (ok) {
-                net->fuse_up2[f].cout = nf, net->fuse_up2[f].cin_phys = r8(below);
-                net->fuse_up2[f].h = vfi_conv_create_up2x2(tensors[k - 2], tensors[k - 1], nf, below, nullptr, r8(below));
-                if (!net->fuse_up2[f].h) ok = false;
-            }
+            make(net->fuse[f][0], nf, below, 2, nullptr, 0, &net->fuse_up2[f]);
         }
         std::vector<int> m = aligned_map(feat_channels(lvl));
         for (int c = 0; c < nf; ++c) m.push_back(net->cal[lvl] + c);
@@ -278,8 +226,7 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
         make(net->fuse[f][1], nf, skip + nf, 3, &m, net->cal[lvl] + nf);
         make(net->fuse[f][2], nf, nf, 3, nullptr, 0);
     }
-    if (!ok || k != n_tensors) {
-        if (ok) set_error("vfi_film_create: consumed %d of %d tensors", k, n_tensors);
+    if (!cur.finish() || net->failed) {
         vfi_film_destroy(net);
         return nullptr;
     }
@@ -288,19 +235,10 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
 
 void vfi_film_destroy(vfi_film_t* net) {
     if (!net) return;
-    for (auto& st : net->ext)
-        for (Layer& L : st) vfi_conv_destroy(L.h);
-    for (auto& p : net->pred)
-        for (Layer& L : p) vfi_conv_destroy(L.h);
-    for (auto& f : net->fuse)
-        for (Layer& L : f) vfi_conv_destroy(L.h);
-    for (Layer& L : net->fuse_up2) vfi_conv_destroy(L.h);
-    vfi_conv_destroy(net->out_conv.h);
     if (net->side) {
         stream_give_back(net->side);      // (drained there; kept for the next object: a node that rebuilds its model per call creates no streams per call)
         for (hipEvent_t e : net->ev) (void)hipEventDestroy(e);
     }
-    free_workspace(net);
     delete net;
 }
 
@@ -313,9 +251,7 @@ int vfi_film_two_streams(vfi_film_t* net, int on) {
 
 int vfi_film_release_workspace(vfi_film_t* net) {
     VFI_REQUIRE(net, "vfi_film_release_workspace: null handle");
-    VFI_CHECK_HIP(hipDeviceSynchronize());
-    free_workspace(net);
-    return 0;
+    return net->ws.release();
 }
 
 int vfi_film_forward(vfi_film_t* net, const float* x0_dev, const float* x1_dev, int C, int H, int W, float* out_dev, int clamp,
@@ -392,7 +328,7 @@ int vfi_film_forward(vfi_film_t* net, const float* x0_dev, const float* x1_dev, 
 #ifdef VFI_TEST_TAPS
 // test tap (include/vfi_hip_test.h, libvfi_hip_test.so only): the synthesised flow pyramid of the LAST forward, direction d (0 forward, 1 backward), level l
 int64_t vfi_film_debug_read_flow(vfi_film_t* net, int d, int level, float* host_buf, int64_t cap) {
-    if (!net || net->H == 0 || d < 0 || d > 1 || level < 0 || level >= PYR) {
+    if (!net || !net->ws.live() || d < 0 || d > 1 || level < 0 || level >= PYR) {
         set_error("vfi_film_debug_read_flow: nothing to read (d=%d level=%d)", d, level);
         return -1;
     }

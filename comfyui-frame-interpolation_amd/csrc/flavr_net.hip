@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/vfi_hip.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -352,7 +353,7 @@ struct Block {
 
 }  // namespace
 
-struct vfi_flavr {
+struct vfi_flavr : NetObject {
     int n_outputs = 1;
     float *stem_wp = nullptr, *stem_b = nullptr;       // packed stem weights, bias (null for n_outputs == 1)
     Block blk[8];                                      // layer1.0, layer1.1, ..., layer4.1
@@ -370,37 +371,15 @@ struct vfi_flavr {
     float* cat[4] = {};                                // (dx_0 | x_0) [P/4, 6, 128], (dx_1 | x_1) [P/4, 6, 128], (dx_2 | x_2) [P/16, 6, 256], (dx_3 | x_3) [P/64, 6, 512]
     float *sub = nullptr, *dsout = nullptr;            // sub-sampled input / output of a downsample convolution, [pixels, 4, C]
     float *fin = nullptr, *fused = nullptr;            // last up-convolution [P, 4 * 64], feature_fuse [P, 64]
-    int64_t bytes = 0;
 };
 
 namespace {
 
-std::vector<float**> workspace_pointers(vfi_flavr* m) {
-    std::vector<float**> ps = {&m->x, &m->mean, &m->scratch, &m->sub, &m->dsout, &m->fin, &m->fused};
-    for (int i = 0; i < 3; ++i) ps.push_back(&m->e2[i]), ps.push_back(&m->e4[i]), ps.push_back(&m->e8[i]), ps.push_back(&m->f8[i]);
-    for (int i = 0; i < 4; ++i) ps.push_back(&m->cat[i]);
-    return ps;
-}
-
-void free_workspace(vfi_flavr* m) {
-    for (float** p : workspace_pointers(m)) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    m->Hp = m->Wp = 0;
-    m->bytes = 0;
-}
-
 int ensure_workspace(vfi_flavr* m, int Hp, int Wp, hipStream_t st) {
-    if (m->Hp == Hp && m->Wp == Wp) return 0;
-    free_workspace(m);
+    if (m->ws.live() && m->Hp == Hp && m->Wp == Wp) return 0;
+    if (m->ws.release()) return -1;
     // bordered buffers are zeroed once: their border slices are never written afterwards
-    auto get = [&](float** p, size_t floats, bool zero) -> int {
-        VFI_CHECK_HIP(hipMalloc((void**)p, floats * sizeof(float)));
-        m->bytes += (int64_t)(floats * sizeof(float));
-        if (zero) VFI_CHECK_HIP(hipMemsetAsync(*p, 0, floats * sizeof(float), st));
-        return 0;
-    };
+    auto get = [&](float** p, size_t floats, bool zero) { return m->ws.alloc(p, floats, zero ? Workspace::kZero : Workspace::kNoFill, st); };
     const size_t P = (size_t)Hp * Wp, P2 = P / 4, P4 = P / 16, P8 = P / 64;
     bool bad = get(&m->x, P * T * 4, false) || get(&m->mean, 4, false) || get(&m->scratch, (size_t)GATE_SLOTS * 512 + 1024, false) ||
                get(&m->sub, std::max(P4 * T * 64, P8 * T * 256), false) || get(&m->dsout, std::max(P4 * T * 128, P8 * T * 512), false) ||
@@ -410,10 +389,7 @@ int ensure_workspace(vfi_flavr* m, int Hp, int Wp, hipStream_t st) {
               get(&m->f8[i], P8 * TS * 512, true);
     bad = bad || get(&m->cat[0], P2 * TS * 128, true) || get(&m->cat[1], P2 * TS * 128, true) || get(&m->cat[2], P4 * TS * 256, true) ||
           get(&m->cat[3], P8 * TS * 512, true);
-    if (bad) {
-        free_workspace(m);
-        return -1;
-    }
+    if (bad) return -1;
     m->Hp = Hp, m->Wp = Wp;
     return 0;
 }
@@ -493,10 +469,6 @@ int forward_window(vfi_flavr* m, const float* const* frames, int C, int H, int W
     return out_launch(m->fused, Hp, Wp, m->out_wp, m->out_b, m->mean, (Hp - H) / 2, (Wp - W) / 2, H, W, out, st);
 }
 
-bool upload(float** dst, const float* src, size_t n) {
-    return hipMalloc((void**)dst, n * sizeof(float)) == hipSuccess && hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-}
-
 // the largest padded frame: the last up-convolution's [Hp, Wp, 4 * 64] output must stay below the convolution kernels' 2^31-byte image limit
 // (every other tensor is smaller: the widest bordered one, [Hp/2, Wp/2, 6 * 128], is 3/4 of it)
 bool size_ok(int Hp, int Wp) { return (long)Hp * Wp * T * 64 * 4 < 0x7fffffffL; }
@@ -567,67 +539,60 @@ vfi_flavr_t* vfi_flavr_create(const float* const* tensors, const int64_t* numels
     }
     vfi_flavr* m = new vfi_flavr();
     m->n_outputs = n_outputs;
-    int k = 0;
-    bool ok = true;
-    auto take = [&](int64_t n) -> const float* {
-        if (!ok) return nullptr;
-        if (numels[k] != n || !tensors[k]) {
-            set_error("vfi_flavr_create: tensor %d has %lld elements, expected %lld", k, (long long)numels[k], (long long)n);
-            ok = false;
-            return nullptr;
-        }
-        return tensors[k++];
-    };
+    TensorCursor cur(tensors, numels, n_tensors, "vfi_flavr_create");
     std::vector<float> w2;
     // Conv3d [cout, cin, 3, 3, 3] -> [cout, 3 cin (dt-major), 3, 3]
     auto conv3 = [&](vfi_conv_t** L, int cout, int cin, int stride, bool bias) {
-        const float* w = take((int64_t)cout * cin * 27);
-        const float* b = bias ? take(cout) : nullptr;
-        if (!ok) return;
+        const float* w = cur.take((int64_t)cout * cin * 27);
+        const float* b = bias ? cur.take(cout) : nullptr;
+        if (!cur.ok()) return;
         w2.resize((size_t)cout * cin * 27);
         for (int co = 0; co < cout; ++co)
             for (int ci = 0; ci < cin; ++ci)
                 for (int dt = 0; dt < 3; ++dt)
                     memcpy(&w2[(((size_t)co * 3 + dt) * cin + ci) * 9], &w[(((size_t)co * cin + ci) * 3 + dt) * 9], 9 * sizeof(float));
-        *L = vfi_conv_create_ex(0, w2.data(), b, cout, 3 * cin, 3, stride, 0, nullptr, 3 * cin, nullptr);
-        if (!*L) ok = false;
+        *L = m->add_layer(vfi_conv_create_ex(0, w2.data(), b, cout, 3 * cin, 3, stride, 0, nullptr, 3 * cin, nullptr));
     };
     // ConvTranspose3d [cin, cout, 3, 4, 4] -> ConvTranspose2d [3 cin, cout, 4, 4], window slice j = temporal tap 2 - j
     auto deconv = [&](vfi_conv_t** L, int cin, int cout) {
-        const float* w = take((int64_t)cin * cout * 48);
-        const float* b = take(cout);
-        if (!ok) return;
+        const float* w = cur.take((int64_t)cin * cout * 48);
+        const float* b = cur.take(cout);
+        if (!cur.ok()) return;
         w2.resize((size_t)cin * cout * 48);
         for (int j = 0; j < 3; ++j)
             for (int ci = 0; ci < cin; ++ci)
                 for (int co = 0; co < cout; ++co)
                     memcpy(&w2[(((size_t)j * cin + ci) * cout + co) * 16], &w[(((size_t)ci * cout + co) * 3 + (2 - j)) * 16], 16 * sizeof(float));
-        *L = vfi_conv_create_ex(1, w2.data(), b, cout, 3 * cin, 4, 2, 0, nullptr, 3 * cin, nullptr);
-        if (!*L) ok = false;
+        *L = m->add_layer(vfi_conv_create_ex(1, w2.data(), b, cout, 3 * cin, 4, 2, 0, nullptr, 3 * cin, nullptr));
+    };
+    auto conv1x1 = [&](vfi_conv_t** L, int cout, int cin) {
+        const float* w = cur.take((int64_t)cout * cin);
+        if (cur.ok()) *L = m->add_layer(vfi_conv_create_ex(0, w, nullptr, cout, cin, 1, 1, 0, nullptr, cin, nullptr));
     };
     auto gate = [&](Gate& g, int c) {
-        const float* w = take((int64_t)c * c);
-        const float* b = take(c);
-        if (ok && !(upload(&g.w, w, (size_t)c * c) && upload(&g.b, b, c))) set_error("vfi_flavr_create: device allocation/upload failed"), ok = false;
+        const float* w = cur.take((int64_t)c * c);
+        const float* b = cur.take(c);
+        if (cur.ok()) g.w = m->upload(w, (size_t)c * c), g.b = m->upload(b, c);
+    };
+    // stem / outconv weights: re-laid out on the device by their pack kernel (the raw copy stays among the object's parameter blocks)
+    auto packed = [&](const float* w, size_t raw_floats, void (*pack)(const float*, float*), size_t floats) -> float* {
+        float* raw = m->upload(w, raw_floats);
+        float* wp = m->upload(nullptr, floats);
+        if (!raw || !wp) return nullptr;
+        pack<<<blocks(floats), 256>>>(raw, wp);
+        if (hipDeviceSynchronize() != hipSuccess) set_error("vfi_flavr_create: weight pack kernel failed"), m->failed = true;
+        return wp;
     };
     {
-        const float* w = take(ST_WFLOATS);
-        const float* b = eb ? take(64) : nullptr;
-        float* raw = nullptr;
-        if (ok) {
-            ok = upload(&raw, w, ST_WFLOATS) && hipMalloc((void**)&m->stem_wp, ST_WFLOATS * sizeof(float)) == hipSuccess && (!b || upload(&m->stem_b, b, 64));
-            if (ok) {
-                flavr_stem_pack_kernel<<<blocks(ST_WFLOATS), 256>>>(raw, m->stem_wp);
-                ok = hipDeviceSynchronize() == hipSuccess;
-            }
-            if (!ok) set_error("vfi_flavr_create: device allocation/upload failed (stem)");
-        }
-        if (raw) (void)hipFree(raw);
+        const float* w = cur.take(ST_WFLOATS);
+        const float* b = eb ? cur.take(64) : nullptr;
+        if (cur.ok()) m->stem_wp = packed(w, ST_WFLOATS, flavr_stem_pack_kernel, ST_WFLOATS);
+        if (cur.ok() && b) m->stem_b = m->upload(b, 64);
     }
     const int planes[4] = {64, 128, 256, 512};
     int inplanes = 64;
-    for (int l = 0; l < 4 && ok; ++l)
-        for (int b = 0; b < 2 && ok; ++b) {
+    for (int l = 0; l < 4 && cur.ok(); ++l)
+        for (int b = 0; b < 2 && cur.ok(); ++b) {
             Block& B = m->blk[l * 2 + b];
             B.c = planes[l];
             B.cin = b == 0 ? inplanes : planes[l];
@@ -635,75 +600,35 @@ vfi_flavr_t* vfi_flavr_create(const float* const* tensors, const int64_t* numels
             conv3(&B.c1, B.c, B.cin, B.stride, eb);
             conv3(&B.c2, B.c, B.c, 1, eb);
             gate(B.g, B.c);
-            if (b == 0 && B.cin != B.c) {
-                const float* w = take((int64_t)B.c * B.cin);
-                if (ok) {
-                    B.ds = vfi_conv_create_ex(0, w, nullptr, B.c, B.cin, 1, 1, 0, nullptr, B.cin, nullptr);
-                    if (!B.ds) ok = false;
-                }
-            }
+            if (b == 0 && B.cin != B.c) conv1x1(&B.ds, B.c, B.cin);
             inplanes = planes[l];
         }
-    if (ok) conv3(&m->dec[0], 256, 512, 1, true), gate(m->dg[0], 256);
-    if (ok) deconv(&m->dec[1], 512, 128), gate(m->dg[1], 128);
-    if (ok) deconv(&m->dec[2], 256, 64), gate(m->dg[2], 64);
-    if (ok) conv3(&m->dec[3], 64, 128, 1, true), gate(m->dg[3], 64);
-    if (ok) deconv(&m->dec[4], 128, 64), gate(m->dg[4], 64);
-    if (ok) {
-        const float* w = take(64 * T * 64);
-        if (ok) {
-            m->fuse = vfi_conv_create_ex(0, w, nullptr, 64, T * 64, 1, 1, 0, nullptr, T * 64, nullptr);
-            if (!m->fuse) ok = false;
-        }
+    conv3(&m->dec[0], 256, 512, 1, true), gate(m->dg[0], 256);
+    deconv(&m->dec[1], 512, 128), gate(m->dg[1], 128);
+    deconv(&m->dec[2], 256, 64), gate(m->dg[2], 64);
+    conv3(&m->dec[3], 64, 128, 1, true), gate(m->dg[3], 64);
+    deconv(&m->dec[4], 128, 64), gate(m->dg[4], 64);
+    conv1x1(&m->fuse, 64, T * 64);
+    {      // outconv.1: only output 0's three channels are computed (the node takes model(...)[0])
+        const float* w = cur.take((int64_t)3 * n_outputs * 64 * 49);
+        const float* b = cur.take(3 * n_outputs);
+        if (cur.ok()) m->out_wp = packed(w, 3 * 64 * 49, flavr_out_pack_kernel, FO_WFLOATS), m->out_b = m->upload(b, 3);
     }
-    if (ok) {      // outconv.1: only output 0's three channels are computed (the node takes model(...)[0])
-        const float* w = take((int64_t)3 * n_outputs * 64 * 49);
-        const float* b = take(3 * n_outputs);
-        float* raw = nullptr;
-        if (ok) {
-            ok = upload(&raw, w, 3 * 64 * 49) && hipMalloc((void**)&m->out_wp, FO_WFLOATS * sizeof(float)) == hipSuccess && upload(&m->out_b, b, 3);
-            if (ok) {
-                flavr_out_pack_kernel<<<blocks(FO_WFLOATS), 256>>>(raw, m->out_wp);
-                ok = hipDeviceSynchronize() == hipSuccess;
-            }
-            if (!ok) set_error("vfi_flavr_create: device allocation/upload failed (outconv)");
-        }
-        if (raw) (void)hipFree(raw);
-    }
-    if (ok && k != want) {
-        set_error("vfi_flavr_create: consumed %d of %d tensors", k, want);
-        ok = false;
-    }
-    if (!ok) {
+    if (!cur.finish() || m->failed) {
         vfi_flavr_destroy(m);
         return nullptr;
     }
     return m;
 }
 
-void vfi_flavr_destroy(vfi_flavr_t* m) {
-    if (!m) return;
-    free_workspace(m);
-    std::vector<float*> ps = {m->stem_wp, m->stem_b, m->out_wp, m->out_b};
-    for (Block& B : m->blk) {
-        vfi_conv_destroy(B.c1), vfi_conv_destroy(B.c2), vfi_conv_destroy(B.ds);
-        ps.push_back(B.g.w), ps.push_back(B.g.b);
-    }
-    for (int i = 0; i < 5; ++i) vfi_conv_destroy(m->dec[i]), ps.push_back(m->dg[i].w), ps.push_back(m->dg[i].b);
-    vfi_conv_destroy(m->fuse);
-    for (float* p : ps)
-        if (p) (void)hipFree(p);
-    delete m;
-}
+void vfi_flavr_destroy(vfi_flavr_t* m) { delete m; }
 
 int vfi_flavr_release_workspace(vfi_flavr_t* m) {
     VFI_REQUIRE(m, "vfi_flavr_release_workspace: null object");
-    VFI_CHECK_HIP(hipDeviceSynchronize());      // kernels of the last forward may still read the buffers
-    free_workspace(m);
-    return 0;
+    return m->ws.release();
 }
 
-int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* m) { return m ? m->bytes : 0; }
+int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* m) { return m ? m->ws.bytes() : 0; }
 
 int vfi_flavr_forward(vfi_flavr_t* m, const float* const* frames_dev, int N, int C, int H, int W, float* out_dev, void* stream) {
     VFI_REQUIRE(m && frames_dev && out_dev && N > 0 && C >= 3 && H > 0 && W > 0, "vfi_flavr_forward: bad arguments");

@@ -14,13 +14,11 @@
 // the Python M2MEngine now wraps this object.
 #include <algorithm>
 #include <cstring>
-#include <map>
-#include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/vfi_hip.h"
 #include "../../include/vfi_hip_test.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -31,11 +29,7 @@ constexpr int RATIO = 4;       // M2M_PWC.forward default ratio (the node never 
 constexpr int DEC_CS = 120;    // decoder input window: [feature 32 | cost volume 81 | flow 2 | pad] (115 -> x8)
 constexpr int FLOW_OFF = 113;
 constexpr int CC = 16;         // M2M_arch.py:586
-
-struct Ten {   // [n][h][w][c] fp32, zero-initialised
-    float* p = nullptr;
-    int n = 0, h = 0, w = 0, c = 0;
-};
+constexpr int NORM_WS = 16384;
 
 struct Layer {
     vfi_conv_t* h = nullptr;
@@ -45,72 +39,40 @@ struct Layer {
 
 }  // namespace
 
-struct vfi_m2m {
+struct vfi_m2m : NetObject {
     Layer ext[3][3], dec[5][6], pyr[4][2], down[4][2], up[4], head, cube[3];
     float alpha = 0.f;
-    std::vector<vfi_conv_t*> all;
-    // workspace
+    // workspace (every Ten zero-initialised)
     int H = 0, W = 0, Hp = 0, Wp = 0;
     bool prepared = false;
     Ten d0, imh, decb[5], flow[5], enc[4], fl[5], s3, pc, ph, pw, cc, ch, cw, xf, r, tf, e, sin, sfl, sout, img4;
     float* tile_ranges = nullptr;      // [8][tiles][4]: per 32x32 tile the range of every refined flow field (vfi_m2m_photo_tiles)
     float* smax = nullptr;             // [8]: max |tf_s|
     float* stats = nullptr;
-    void* ws = nullptr;
+    float* nws = nullptr;              // vfi_m2m_normalize's workspace, NORM_WS bytes
     // r6 A/B form (option m2m_side, off): the image-pyramid convolutions of the refinement network depend on the normalised frames only,
     // not on the flow, and can run on this side stream beside the PWC flow network (fork / join by events).  Bit-identical, and measured
     // neutral for one pair (7.00-7.04 vs 7.0-7.1 ms) and 8 % slower under three pair lanes (lanes.py already fill the coarse levels' holes)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int dech[5][2], ench[4][2];
-    std::map<std::tuple<std::string, int, int, int>, Ten> scratch;
-    std::vector<void*> owned;
-    int64_t owned_bytes = 0;           // vfi_m2m_workspace_bytes (the tensors; a few KB of control words are not counted)
 };
 
 namespace {
 
-int alloc_ten(vfi_m2m* m, Ten& t, int n, int h, int w, int c, hipStream_t st = nullptr) {
-    t.n = n, t.h = h, t.w = w, t.c = c;
-    const size_t bytes = (size_t)n * h * w * c * sizeof(float);
-    VFI_CHECK_HIP(hipMalloc((void**)&t.p, bytes));
-    m->owned.push_back(t.p);
-    m->owned_bytes += (int64_t)bytes;
-    // zero fill ordered with the forward's kernels: a NULL-stream memset is not ordered against a non-blocking side stream (torch's)
-    // and could clear a lazily allocated scratch tensor AFTER its first producer ran
-    VFI_CHECK_HIP(hipMemsetAsync(t.p, 0, bytes, st));
-    if (!st) VFI_CHECK_HIP(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-void free_workspace(vfi_m2m* m) {
-    for (void* p : m->owned) (void)hipFree(p);
-    m->owned.clear();
-    m->owned_bytes = 0;
-    m->scratch.clear();
-    m->stats = nullptr;
-    m->tile_ranges = m->smax = nullptr;
-    m->sin = m->sfl = m->sout = Ten();
-    m->ws = nullptr;
-    m->H = m->W = 0;
-    m->prepared = false;
-}
+int alloc_ten(vfi_m2m* m, Ten& t, int n, int h, int w, int c, hipStream_t st = nullptr) { return m->ws.ten(t, n, h, w, c, st); }
 
 int ensure_workspace(vfi_m2m* m, int H, int W) {
-    if (m->H == H && m->W == W) return 0;
-    VFI_CHECK_HIP(hipDeviceSynchronize());
-    free_workspace(m);
+    if (m->ws.live() && m->H == H && m->W == W) return 0;
+    if (m->ws.release()) return -1;
+    m->prepared = false;
+    m->sin = m->sfl = m->sout = Ten();
     const int mult = RATIO * 16;
     const int Hp = (H + mult - 1) / mult * mult, Wp = (W + mult - 1) / mult * mult;
     m->Hp = Hp, m->Wp = Wp;
     const int h = Hp / 2, w = Wp / 2;
     if (alloc_ten(m, m->d0, 2, Hp, Wp, 8)) return -1;                 // [flow 2 | normalised image 3 | warped partner image 3]
-    VFI_CHECK_HIP(hipMalloc((void**)&m->stats, 2 * sizeof(float)));
-    m->owned.push_back(m->stats);
-    VFI_CHECK_HIP(hipMemset(m->stats, 0, 2 * sizeof(float)));
-    VFI_CHECK_HIP(hipMalloc(&m->ws, 16384));
-    m->owned.push_back(m->ws);
-    VFI_CHECK_HIP(hipMemset(m->ws, 0, 16384));
+    if (m->ws.alloc(&m->stats, 2, Workspace::kZero, nullptr) || m->ws.alloc(&m->nws, NORM_WS / 4, Workspace::kZero, nullptr)) return -1;
     if (alloc_ten(m, m->imh, 2, h, w, 8)) return -1;                  // half-resolution images for the flow network
     for (int l = 0; l < 5; ++l) {
         m->dech[l][0] = h >> (l + 1), m->dech[l][1] = w >> (l + 1);
@@ -128,30 +90,13 @@ int ensure_workspace(vfi_m2m* m, int H, int W) {
         alloc_ten(m, m->cw, 2, 1, e3w, 16) || alloc_ten(m, m->xf, 2, Hp, Wp, 16) || alloc_ten(m, m->r, 2, Hp, Wp, 12) ||
         alloc_ten(m, m->tf, 8, Hp, Wp, 2) || alloc_ten(m, m->e, 8, Hp, Wp, 1) || alloc_ten(m, m->img4, 2, Hp, Wp, 4))
         return -1;
-    {
-        const size_t tiles = (size_t)((Hp + 31) / 32) * ((Wp + 31) / 32);
-        VFI_CHECK_HIP(hipMalloc((void**)&m->tile_ranges, 8 * tiles * 4 * sizeof(float)));
-        m->owned.push_back(m->tile_ranges);
-        VFI_CHECK_HIP(hipMalloc((void**)&m->smax, 8 * sizeof(float)));
-        m->owned.push_back(m->smax);
-        VFI_CHECK_HIP(hipMemset(m->smax, 0, 8 * sizeof(float)));
-        VFI_CHECK_HIP(hipStreamSynchronize(nullptr));      // (the fills above are not ordered against the caller's non-blocking stream)
-    }
+    const size_t tiles = (size_t)((Hp + 31) / 32) * ((Wp + 31) / 32);
+    if (m->ws.alloc(&m->tile_ranges, 8 * tiles * 4, Workspace::kNoFill, nullptr) || m->ws.alloc(&m->smax, 8, Workspace::kZero, nullptr)) return -1;
     m->H = H, m->W = W;
     return 0;
 }
 
-int tmp(vfi_m2m* m, const char* name, int h, int w, int c, Ten** out) {
-    auto key = std::make_tuple(std::string(name), h, w, c);
-    auto it = m->scratch.find(key);
-    if (it == m->scratch.end()) {
-        Ten t;
-        if (alloc_ten(m, t, 2, h, w, c)) return -1;
-        it = m->scratch.emplace(key, t).first;
-    }
-    *out = &it->second;
-    return 0;
-}
+int tmp(vfi_m2m* m, const char* name, int h, int w, int c, Ten** out) { return m->ws.tmp(name, 2, h, w, c, out); }
 
 // out[..., doff : doff + cout] = act(layer(src[..., soff : soff + cin_phys]) (+ res))
 int run(const Layer& L, const Ten& src, int soff, const Ten& dst, int doff, int act, float slope, hipStream_t st, const Ten* res = nullptr,
@@ -202,89 +147,73 @@ vfi_m2m_t* vfi_m2m_create(const float* const* tensors, const int64_t* numels, in
         return nullptr;
     }
     vfi_m2m* m = new vfi_m2m();
-    int k = 0;
-    bool ok = true;
-    auto take = [&](int64_t want) -> const float* {
-        if (!ok) return nullptr;
-        if (k >= n_tensors || numels[k] != want) {
-            set_error("vfi_m2m_create: tensor %d has %lld elements, expected %lld", k, (long long)(k < n_tensors ? numels[k] : -1), (long long)want);
-            ok = false;
-            return nullptr;
-        }
-        return tensors[k++];
-    };
+    TensorCursor cur(tensors, numels, n_tensors, "vfi_m2m_create");
     auto make = [&](Layer& L, int kind, const float* w, const float* b, int cout, int cin, int kk, int stride, int pad_mode,
                     const std::vector<int>* cmap, int cin_phys, const float* prelu) {
-        if (!ok) return;
+        if (!cur.ok()) return;
         L.kind = kind, L.stride = stride;
-        L.h = vfi_conv_create_ex(kind, w, b, cout, cin, kk, stride, pad_mode, cmap ? cmap->data() : nullptr, cin_phys > 0 ? cin_phys : (cin + 7) / 8 * 8,
-                                 prelu);
-        if (!L.h) ok = false;
-        else m->all.push_back(L.h);
+        L.h = m->add_layer(vfi_conv_create_ex(kind, w, b, cout, cin, kk, stride, pad_mode, cmap ? cmap->data() : nullptr,
+                                              cin_phys > 0 ? cin_phys : (cin + 7) / 8 * 8, prelu));
     };
-    const float* a = take(1);
-    if (a) m->alpha = a[0];
+    m->alpha = cur.scalar();
     // PWC extractor: 3 x (sconv(2)-prelu, conv(3,replpad)-prelu, conv(3,replpad)-prelu), M2M_arch.py:415-446
     const int ext_cin[3] = {3, 32, 32};
-    for (int s = 0; s < 3 && ok; ++s) {
-        const float* w = take((int64_t)32 * ext_cin[s] * 4);
-        const float* b = take(32);
-        const float* sl = take(1);
+    for (int s = 0; s < 3 && cur.ok(); ++s) {
+        const float* w = cur.take((int64_t)32 * ext_cin[s] * 4);
+        const float* b = cur.take(32);
         make(m->ext[s][0], 0, w, b, 32, ext_cin[s], 2, 2, 0, nullptr, 0, nullptr);
-        if (sl) m->ext[s][0].slope = sl[0];
-        for (int i = 1; i <= 2 && ok; ++i) {
-            w = take((int64_t)32 * 32 * 9);
-            b = take(32);
-            sl = take(1);
+        m->ext[s][0].slope = cur.scalar();
+        for (int i = 1; i <= 2 && cur.ok(); ++i) {
+            w = cur.take((int64_t)32 * 32 * 9);
+            b = cur.take(32);
             make(m->ext[s][i], 0, w, b, 32, 32, 3, 1, 1, nullptr, 0, nullptr);
-            if (sl) m->ext[s][i].slope = sl[0];
+            m->ext[s][i].slope = cur.scalar();
         }
     }
     // PWC decoders, checkpoint order netFiv, netFou, netThr, netTwo, netOne = levels 4..0 (:449-503)
-    for (int p = 0; p < 5 && ok; ++p) {
+    for (int p = 0; p < 5 && cur.ok(); ++p) {
         const int lvl = 4 - p, cin0 = lvl == 4 ? 113 : 115;
-        (void)take(1);   // netCostacti: PReLU on the cost volume, which is >= 0 — the identity
+        (void)cur.take(1);   // netCostacti: PReLU on the cost volume, which is >= 0 — the identity
         const int chans[7] = {cin0, 128, 128, 96, 64, 32, 2};
-        for (int i = 0; i < 6 && ok; ++i) {
-            const float* w = take((int64_t)chans[i + 1] * chans[i] * 9);
-            const float* b = take(chans[i + 1]);
-            const float* sl = i < 5 ? take(1) : nullptr;
+        for (int i = 0; i < 6 && cur.ok(); ++i) {
+            const float* w = cur.take((int64_t)chans[i + 1] * chans[i] * 9);
+            const float* b = cur.take(chans[i + 1]);
             make(m->dec[lvl][i], 0, w, b, chans[i + 1], chans[i], 3, 1, 1, nullptr, i == 0 ? DEC_CS : 0, nullptr);
-            m->dec[lvl][i].slope = sl ? sl[0] : 0.f;
+            m->dec[lvl][i].slope = i < 5 ? cur.scalar() : 0.f;
         }
     }
     // conv() helper: Conv2d(3, stride, 1) + PReLU(cout), :589-602
     auto cp = [&](Layer& L, int cin, int cout, int stride, const std::vector<int>* cmap, int cin_phys) {
-        const float* w = take((int64_t)cout * cin * 9);
-        const float* b = take(cout);
-        const float* pr = take(cout);
+        const float* w = cur.take((int64_t)cout * cin * 9);
+        const float* b = cur.take(cout);
+        const float* pr = cur.take(cout);
         make(L, 0, w, b, cout, cin, 3, stride, 0, cmap, cin_phys, pr);
     };
     const int pyr_c[5] = {3, CC, 2 * CC, 4 * CC, 8 * CC};
     const std::vector<int> img_map = {2, 3, 4};   // the image channels of d0 = [flow 2 | image 3 | ...]
-    for (int i = 0; i < 4 && ok; ++i) {
+    for (int i = 0; i < 4 && cur.ok(); ++i) {
         cp(m->pyr[i][0], pyr_c[i], pyr_c[i + 1], 2, i == 0 ? &img_map : nullptr, i == 0 ? 8 : 0);
         cp(m->pyr[i][1], pyr_c[i + 1], pyr_c[i + 1], 1, nullptr, 0);
     }
     const int down_ci[4] = {8, 6 * CC, 12 * CC, 24 * CC}, down_co[4] = {2 * CC, 4 * CC, 8 * CC, 16 * CC};
-    for (int i = 0; i < 4 && ok; ++i) {
+    for (int i = 0; i < 4 && cur.ok(); ++i) {
         cp(m->down[i][0], down_ci[i], down_co[i], 2, nullptr, 0);
         cp(m->down[i][1], down_co[i], down_co[i], 1, nullptr, 0);
     }
     const int up_ci[4] = {48 * CC, 16 * CC, 8 * CC, 4 * CC}, up_co[4] = {8 * CC, 4 * CC, 2 * CC, CC};
-    for (int i = 0; i < 4 && ok; ++i) {
-        const float* w = take((int64_t)up_ci[i] * up_co[i] * 16);
-        const float* b = take(up_co[i]);
-        const float* pr = take(up_co[i]);
+    for (int i = 0; i < 4 && cur.ok(); ++i) {
+        const float* w = cur.take((int64_t)up_ci[i] * up_co[i] * 16);
+        const float* b = cur.take(up_co[i]);
+        const float* pr = cur.take(up_co[i]);
         make(m->up[i], 1, w, b, up_co[i], up_ci[i], 4, 2, 0, nullptr, 0, pr);
     }
     // conv (8 flow residuals) and conv_m (mask logit) read the same tensor: one layer with 9 outputs (:838-846)
     {
-        const float* w8 = take((int64_t)8 * CC * 9);
-        const float* b8 = take(8);
-        const float* w1 = take((int64_t)1 * CC * 9);
-        const float* b1 = take(1);
-        if (ok) {
+        const float* w8 = cur.take((int64_t)8 * CC * 9);
+        const float* b8 = cur.take(8);
+        const float* w1 = cur.take((int64_t)1 * CC * 9);
+        const float* b1 = cur.take(1);
+        if (cur.ok()) {
             std::vector<float> w(9 * CC * 9), b(9);
             memcpy(w.data(), w8, sizeof(float) * 8 * CC * 9);
             memcpy(w.data() + 8 * CC * 9, w1, sizeof(float) * CC * 9);
@@ -294,13 +223,12 @@ vfi_m2m_t* vfi_m2m_create(const float* const* tensors, const int64_t* numels, in
         }
     }
     const int cube_co[3] = {16 * 16 * CC, 16, 16};
-    for (int i = 0; i < 3 && ok; ++i) {
-        const float* w = take((int64_t)cube_co[i] * 16 * CC);
-        const float* b = take(cube_co[i]);
+    for (int i = 0; i < 3 && cur.ok(); ++i) {
+        const float* w = cur.take((int64_t)cube_co[i] * 16 * CC);
+        const float* b = cur.take(cube_co[i]);
         make(m->cube[i], 0, w, b, cube_co[i], 16 * CC, 1, 1, 0, nullptr, 0, nullptr);
     }
-    if (!ok || k != n_tensors) {
-        if (ok) set_error("vfi_m2m_create: consumed %d of %d tensors", k, n_tensors);
+    if (!cur.finish() || m->failed) {
         vfi_m2m_destroy(m);
         return nullptr;
     }
@@ -315,18 +243,14 @@ void vfi_m2m_destroy(vfi_m2m_t* m) {
         (void)hipEventDestroy(m->ev_join);
         (void)hipStreamDestroy(m->side);
     }
-    for (vfi_conv_t* c : m->all) vfi_conv_destroy(c);
-    free_workspace(m);
     delete m;
 }
 
-int64_t vfi_m2m_workspace_bytes(vfi_m2m_t* m) { return m ? m->owned_bytes : 0; }
+int64_t vfi_m2m_workspace_bytes(vfi_m2m_t* m) { return m ? m->ws.bytes() : 0; }
 
 int vfi_m2m_release_workspace(vfi_m2m_t* m) {
     VFI_REQUIRE(m, "vfi_m2m_release_workspace: null handle");
-    VFI_CHECK_HIP(hipDeviceSynchronize());
-    free_workspace(m);
-    return 0;
+    return m->ws.release();
 }
 
 int vfi_m2m_prepare(vfi_m2m_t* m, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, void* stream) {
@@ -335,7 +259,7 @@ int vfi_m2m_prepare(vfi_m2m_t* m, const float* frame0_dev, const float* frame1_d
     hipStream_t st = (hipStream_t)stream;
     const int Hp = m->Hp, Wp = m->Wp;
     m->prepared = false;
-    if (vfi_m2m_normalize(frame0_dev, frame1_dev, C, H, W, Hp, Wp, m->d0.p, 8, 2, m->stats, m->ws, 16384, st)) return -1;
+    if (vfi_m2m_normalize(frame0_dev, frame1_dev, C, H, W, Hp, Wp, m->d0.p, 8, 2, m->stats, m->nws, NORM_WS, st)) return -1;
     if (vfi_m2m_image4(m->d0.p, 8, m->img4.p, Hp, Wp, st)) return -1;
     // fork: the c features (image pyramid through pyr[l][0..1], EncDec.forward :722-735) read channels 2..4 of d0 = the normalised frames,
     // which exist now.  (Channels 0..1 and 5..7 of d0 are written later on `st` — the flow, the warped partner — while the side stream may
@@ -423,7 +347,7 @@ int vfi_m2m_prepare(vfi_m2m_t* m, const float* frame0_dev, const float* frame1_d
 
 int vfi_m2m_render(vfi_m2m_t* m, float t, float* out_dev, void* stream) {
     VFI_REQUIRE(m && out_dev, "vfi_m2m_render: bad arguments");
-    VFI_REQUIRE(m->prepared, "vfi_m2m_render: no prepared frame pair (call vfi_m2m_prepare first)");
+    VFI_REQUIRE(m->prepared && m->ws.live(), "vfi_m2m_render: no prepared frame pair (call vfi_m2m_prepare first)");
     hipStream_t st = (hipStream_t)stream;
     const int Hp = m->Hp, Wp = m->Wp;
     // one kernel: splat inputs, the 8 summation splats and forwarp_mframe_mask's combine per 32x32 tile of the frame (m2m_render.hip)
@@ -440,7 +364,7 @@ int vfi_m2m_render(vfi_m2m_t* m, float t, float* out_dev, void* stream) {
 // test tap (include/vfi_hip_test.h, libvfi_hip_test.so only): internal tensors of the LAST prepare — what 0: PWC flows at 1/4 of the padded size
 // [2,Hp/4,Wp/4,2]; 1: d0 [2,Hp,Wp,8] (refined-flow base | normalised image | warped partner); 2: r [2,Hp,Wp,12] (8 residuals | mask)
 int64_t vfi_m2m_debug_read(vfi_m2m_t* m, int what, float* host_buf, int64_t cap) {
-    if (!m || !m->prepared || what < 0 || what > 2) {
+    if (!m || !m->prepared || !m->ws.live() || what < 0 || what > 2) {
         set_error("vfi_m2m_debug_read: nothing prepared / bad selector %d", what);
         return -1;
     }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/vfi_hip.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -208,7 +209,7 @@ int pair_out_launch(const float* f0, const float* f1, int C, int H, int W, const
 
 }  // namespace
 
-struct vfi_sepconvnet {
+struct vfi_sepconvnet : NetObject {
     vfi_conv_t* in = nullptr;                         // netInput of both frames: block-diagonal 8 -> 32
     vfi_conv_t* enc[5][2] = {};                       // rows 1..4: sconv3 s2, conv3
     vfi_conv_t* hor[5][2] = {};                       // rows 1..4
@@ -225,30 +226,14 @@ struct vfi_sepconvnet {
     float* row[5][2] = {};
     int cur[5] = {};
     float *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *heads = nullptr;
-    int64_t bytes = 0;
 };
 
 namespace {
 
-void free_workspace(vfi_sepconvnet* m) {
-    std::vector<float*> ps = {m->nrm, m->side, m->stats, m->nws, m->x1, m->x2, m->x3, m->heads};
-    for (int r = 0; r < 5; ++r) ps.push_back(m->row[r][0]), ps.push_back(m->row[r][1]);
-    for (float* p : ps)
-        if (p) (void)hipFree(p);
-    m->nrm = m->side = m->stats = m->nws = m->x1 = m->x2 = m->x3 = m->heads = nullptr;
-    memset(m->row, 0, sizeof(m->row));
-    m->Hp = m->Wp = 0;
-    m->bytes = 0;
-}
-
 int ensure_workspace(vfi_sepconvnet* m, int Hp, int Wp) {
-    if (m->Hp == Hp && m->Wp == Wp) return 0;
-    free_workspace(m);
-    auto get = [&](float** p, size_t floats) -> int {
-        VFI_CHECK_HIP(hipMalloc((void**)p, floats * sizeof(float)));
-        m->bytes += (int64_t)(floats * sizeof(float));
-        return 0;
-    };
+    if (m->ws.live() && m->Hp == Hp && m->Wp == Wp) return 0;
+    if (m->ws.release()) return -1;
+    auto get = [&](float** p, size_t floats) { return m->ws.alloc(p, floats, Workspace::kNoFill, nullptr); };
     const size_t P = (size_t)Hp * Wp;
     m->h[0] = Hp, m->w[0] = Wp;
     for (int r = 1; r < 5; ++r) m->h[r] = (m->h[r - 1] + 1) / 2, m->w[r] = (m->w[r - 1] + 1) / 2;
@@ -384,32 +369,21 @@ vfi_sepconvnet_t* vfi_sepconvnet_create(const float* const* tensors, const int64
         return nullptr;
     }
     vfi_sepconvnet* m = new vfi_sepconvnet();
-    int k = 0;
-    bool ok = true;
-    auto take = [&](int64_t n) -> const float* {
-        if (!ok) return nullptr;
-        if (numels[k] != n || !tensors[k]) {
-            set_error("vfi_sepconvnet_create: tensor %d has %lld elements, expected %lld", k, (long long)numels[k], (long long)n);
-            ok = false;
-            return nullptr;
-        }
-        return tensors[k++];
-    };
-    auto slope = [&]() -> float {
-        const float* s = take(1);
-        return s ? s[0] : 0.f;
+    TensorCursor cur(tensors, numels, n_tensors, "vfi_sepconvnet_create");
+    auto layer = [&](const float* w, const float* b, int cout, int cin, int stride, const float* prelu) {
+        return m->add_layer(vfi_conv_create_ex(0, w, b, cout, cin, 3, stride, 0, nullptr, cin, prelu));
     };
     auto make = [&](vfi_conv_t** L, int cout, int cin, int stride) {
-        const float* w = take((int64_t)cout * cin * 9);
-        const float* b = take(cout);
-        if (!ok) return;
-        *L = vfi_conv_create_ex(0, w, b, cout, cin, 3, stride, 0, nullptr, cin, nullptr);
-        if (!*L || (stride == 2 && vfi_conv_accept_odd(*L, 1))) ok = false;     // the encoder's rows reach odd sizes (135 at 1080p)
+        const float* w = cur.take((int64_t)cout * cin * 9);
+        const float* b = cur.take(cout);
+        if (!cur.ok()) return;
+        *L = layer(w, b, cout, cin, stride, nullptr);
+        if (*L && stride == 2 && vfi_conv_accept_odd(*L, 1)) m->failed = true;     // the encoder's rows reach odd sizes (135 at 1080p)
     };
     {   // netInput 3 -> 16 on each frame = one 8 -> 32 layer over (frame 0 rgb, 0, frame 1 rgb, 0)
-        const float* w = take(16 * 3 * 9);
-        const float* b = take(16);
-        if (ok) {
+        const float* w = cur.take(16 * 3 * 9);
+        const float* b = cur.take(16);
+        if (cur.ok()) {
             std::vector<float> w8((size_t)32 * 8 * 9, 0.f), b8(32);
             for (int f = 0; f < 2; ++f)
                 for (int co = 0; co < 16; ++co) {
@@ -417,82 +391,62 @@ vfi_sepconvnet_t* vfi_sepconvnet_create(const float* const* tensors, const int64
                     for (int ci = 0; ci < 3; ++ci)
                         for (int t = 0; t < 9; ++t) w8[((size_t)(f * 16 + co) * 8 + f * 4 + ci) * 9 + t] = w[((size_t)co * 3 + ci) * 9 + t];
                 }
-            m->in = vfi_conv_create_ex(0, w8.data(), b8.data(), 32, 8, 3, 1, 0, nullptr, 8, nullptr);
-            if (!m->in) ok = false;
+            m->in = layer(w8.data(), b8.data(), 32, 8, 1, nullptr);
         }
     }
-    for (int r = 1; r < 5 && ok; ++r) {     // netEncode.0.netVer.r: prelu, sconv, prelu, conv
-        m->enc_s[r][0] = slope();
+    for (int r = 1; r < 5 && cur.ok(); ++r) {     // netEncode.0.netVer.r: prelu, sconv, prelu, conv
+        m->enc_s[r][0] = cur.scalar();
         make(&m->enc[r][0], CH[r], CH[r - 1], 2);
-        m->enc_s[r][1] = slope();
+        m->enc_s[r][1] = cur.scalar();
         make(&m->enc[r][1], CH[r], CH[r], 1);
     }
-    for (int i = 0; i < 4 && ok; ++i) {     // netDecode.0.netHor.i = row 4 - i
+    for (int i = 0; i < 4 && cur.ok(); ++i) {     // netDecode.0.netHor.i = row 4 - i
         const int r = 4 - i;
-        m->hor_s[r][0] = slope();
+        m->hor_s[r][0] = cur.scalar();
         make(&m->hor[r][0], CH[r], CH[r], 1);
-        m->hor_s[r][1] = slope();
+        m->hor_s[r][1] = cur.scalar();
         make(&m->hor[r][1], CH[r], CH[r], 1);
     }
-    for (int i = 1; i < 4 && ok; ++i) {     // netDecode.0.netVer.i = row 4 - i from row 5 - i
+    for (int i = 1; i < 4 && cur.ok(); ++i) {     // netDecode.0.netVer.i = row 4 - i from row 5 - i
         const int r = 4 - i;
-        m->ver_s[r][0] = slope();
+        m->ver_s[r][0] = cur.scalar();
         make(&m->ver[r][0], CH[r], CH[r + 1], 1);
-        m->ver_s[r][1] = slope();
+        m->ver_s[r][1] = cur.scalar();
         make(&m->ver[r][1], CH[r], CH[r], 1);
     }
     {   // heads (netVerone, netVertwo, netHorone, netHortwo): conv 64 -> 64, prelu, conv 64 -> 51
         std::vector<float> w1((size_t)256 * 64 * 9), b1(256), s1(256);
-        for (int hd = 0; hd < 4 && ok; ++hd) {
-            const float* w = take(64 * 64 * 9);
-            const float* b = take(64);
-            const float s = slope();
-            const float* w2 = take((int64_t)K * 64 * 9);
-            const float* b2 = take(K);
-            if (!ok) break;
+        for (int hd = 0; hd < 4; ++hd) {
+            const float* w = cur.take(64 * 64 * 9);
+            const float* b = cur.take(64);
+            const float s = cur.scalar();
+            const float* w2 = cur.take((int64_t)K * 64 * 9);
+            const float* b2 = cur.take(K);
+            if (!cur.ok()) break;
             memcpy(w1.data() + (size_t)hd * 64 * 64 * 9, w, 64 * 64 * 9 * sizeof(float));
             memcpy(b1.data() + hd * 64, b, 64 * sizeof(float));
             std::fill(s1.begin() + hd * 64, s1.begin() + hd * 64 + 64, s);
-            m->head2[hd] = vfi_conv_create_ex(0, w2, b2, K, 64, 3, 1, 0, nullptr, 64, nullptr);
-            m->head1s[hd] = vfi_conv_create_ex(0, w, b, 64, 64, 3, 1, 0, nullptr, 64, nullptr);
+            m->head2[hd] = layer(w2, b2, K, 64, 1, nullptr);
+            m->head1s[hd] = layer(w, b, 64, 64, 1, nullptr);
             m->head_s[hd] = s;
-            if (!m->head2[hd] || !m->head1s[hd]) ok = false;
         }
-        if (ok) {
-            m->head1 = vfi_conv_create_ex(0, w1.data(), b1.data(), 256, 64, 3, 1, 0, nullptr, 64, s1.data());
-            if (!m->head1) ok = false;
-        }
+        if (cur.ok()) m->head1 = layer(w1.data(), b1.data(), 256, 64, 1, s1.data());
     }
-    if (ok && k != want) {
-        set_error("vfi_sepconvnet_create: consumed %d of %d tensors", k, want);
-        ok = false;
-    }
-    if (!ok) {
+    if (!cur.finish() || m->failed) {
         vfi_sepconvnet_destroy(m);
         return nullptr;
     }
     return m;
 }
 
-void vfi_sepconvnet_destroy(vfi_sepconvnet_t* m) {
-    if (!m) return;
-    free_workspace(m);
-    vfi_conv_destroy(m->in);
-    for (int r = 0; r < 5; ++r)
-        for (int j = 0; j < 2; ++j) vfi_conv_destroy(m->enc[r][j]), vfi_conv_destroy(m->hor[r][j]), vfi_conv_destroy(m->ver[r][j]);
-    vfi_conv_destroy(m->head1);
-    for (int k = 0; k < 4; ++k) vfi_conv_destroy(m->head2[k]), vfi_conv_destroy(m->head1s[k]);
-    delete m;
-}
+void vfi_sepconvnet_destroy(vfi_sepconvnet_t* m) { delete m; }
 
 int vfi_sepconvnet_release_workspace(vfi_sepconvnet_t* m) {
     VFI_REQUIRE(m, "vfi_sepconvnet_release_workspace: null object");
-    VFI_CHECK_HIP(hipDeviceSynchronize());      // kernels of the last forward may still read the buffers
-    free_workspace(m);
-    return 0;
+    return m->ws.release();
 }
 
-int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* m) { return m ? m->bytes : 0; }
+int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* m) { return m ? m->ws.bytes() : 0; }
 
 int vfi_sepconvnet_forward(vfi_sepconvnet_t* m, const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W,
                            float* out_dev, void* stream) {

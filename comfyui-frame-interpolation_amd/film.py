@@ -17,7 +17,6 @@ tensors (physical channel positions are translated once, at weight-pack time, th
 torch only allocates device buffers and moves frames (plumbing).
 """
 import bisect
-import ctypes as C
 import typing
 
 import numpy as np
@@ -27,40 +26,22 @@ from . import _lib
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film_spec import check_state_dict, film_shapes
 from .lanes import lane_set
+from .netengine import NetEngine
 from .nodeloop import run_plan
 from .schedule import InterpolationStateList, film_output_plan
 
 MODEL_TYPE = "film"
 
 
-class FilmEngine:
+class FilmEngine(NetEngine):
     """Device-resident FILM interpolator (one frame pair per call, like the reference node): the C-side object
     vfi_film_create / vfi_film_forward / vfi_film_destroy (csrc/film_net.hip) — weights packed once, workspace owned by the
     library, the whole launch sequence of a pair issued by one call."""
 
-    def __init__(self, state_dict, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("FILM VFI (HIP): no GPU visible; this node has no CPU fallback")
-        self.lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
-        check_state_dict(state_dict)
-        keys = list(film_shapes().keys())
-        tensors = [state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in keys]
-        ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
-        numels = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
-        self.handle = self.lib.vfi_film_create(ptrs, numels, len(keys))
-        if not self.handle:
-            raise RuntimeError("vfi_film_create failed: " + _lib.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.vfi_film_destroy(self.handle)
-            self.handle = None
-
-    def release_workspace(self):
-        """Drop the activations (15 GB at 1080p); the packed weights stay on the device."""
-        _lib.check(self.lib.vfi_film_release_workspace(self.handle), "vfi_film_release_workspace")
+    PREFIX, LABEL = "vfi_film", "FILM"
+    shapes = staticmethod(film_shapes)
+    check_state_dict = staticmethod(check_state_dict)
+    # no workspace_bytes: the object does not report it, so ckpt.end_call releases the workspace (15 GB at 1080p) after every call
 
     def two_streams(self, on):
         """vfi_film_forward forks half of the network onto the object's side stream (default) / stays on the caller's stream (what the
@@ -83,8 +64,7 @@ class FilmEngine:
         for x in (x0, x1):
             assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape[:2]) == (H, W) and x.shape[2] == x0.shape[2]
         out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.vfi_film_forward(self.handle, x0.data_ptr(), x1.data_ptr(), x0.shape[2], H, W, out.data_ptr(), int(bool(clamp)),
-                                             _lib.stream_ptr()), "vfi_film_forward")
+        self._call("forward", x0.data_ptr(), x1.data_ptr(), x0.shape[2], H, W, out.data_ptr(), int(bool(clamp)), _lib.stream_ptr())
         return out
 
 

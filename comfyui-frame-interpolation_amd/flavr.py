@@ -6,7 +6,6 @@ Node shape follows vfi_models/flavr/__init__.py:28-115.  Unlike every pair-at-a-
 one vfi_flavr_forward (csrc/flavr_net.hip: InputPadder(16), window mean, 3D U-Net, un-pad).  No clamp; the multiplier is always 2.
 No pair lanes, no multi-rank sharding and no HIP graph for this node.
 """
-import ctypes as C
 import typing
 import warnings
 
@@ -15,6 +14,7 @@ import torch
 from . import _lib
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .flavr_spec import flavr_shapes, load_file, n_outputs_of
+from .netengine import NetEngine, WorkspaceBytes, frame_ptrs
 from .schedule import InterpolationStateList
 
 MODEL_TYPE = "flavr"
@@ -22,52 +22,26 @@ CKPT_NAMES = ["FLAVR_2x.pth", "FLAVR_4x.pth", "FLAVR_8x.pth"]
 NBR_FRAME = 4
 
 
-class FlavrEngine:
+class FlavrEngine(WorkspaceBytes, NetEngine):
     """Device-resident FLAVR: ``forward(frames)`` = ``unpad(model([pad(f) for f in window])[0])`` for a batch of windows in one call."""
 
+    PREFIX, LABEL = "vfi_flavr", "FLAVR"
+
     def __init__(self, state_dict, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("FLAVR VFI (HIP): no GPU visible; this node has no CPU fallback")
-        self.lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
         self.n_outputs = n_outputs_of(state_dict)
-        keys = list(flavr_shapes(self.n_outputs).keys())
-        tensors = [state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in keys]
-        ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
-        numels = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
-        self.handle = self.lib.vfi_flavr_create(ptrs, numels, len(keys), self.n_outputs)
-        if not self.handle:
-            raise RuntimeError("vfi_flavr_create failed: " + _lib.last_error())
+        super().__init__(state_dict, device, self.n_outputs)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.vfi_flavr_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def release_workspace(self):
-        _lib.check(self.lib.vfi_flavr_release_workspace(self.handle), "vfi_flavr_release_workspace")
-
-    def workspace_bytes(self):
-        return int(self.lib.vfi_flavr_workspace_bytes(self.handle)) if getattr(self, "handle", None) else 0
+    def shapes(self):
+        return flavr_shapes(self.n_outputs)
 
     def forward(self, frames, out=None):
         """frames: a sequence of 4 N [H,W,C>=3] fp32 contiguous device tensors (window n = frames[4n : 4n+4]; not written) -> [N,H,W,3]."""
         assert len(frames) > 0 and len(frames) % NBR_FRAME == 0, "frames: four per window"
         n = len(frames) // NBR_FRAME
-        H, W, Cc = frames[0].shape
-        for f in frames:
-            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        p, (H, W, Cc) = frame_ptrs(frames)
         if out is None:
             out = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.device)
-        p = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
-        _lib.check(self.lib.vfi_flavr_forward(self.handle, p, n, Cc, H, W, out.data_ptr(), _lib.stream_ptr()), "vfi_flavr_forward")
+        self._call("forward", p, n, Cc, H, W, out.data_ptr(), _lib.stream_ptr())
         return out
 
 

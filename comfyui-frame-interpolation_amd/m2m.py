@@ -20,7 +20,6 @@ Unlike the reference (which re-runs the whole network for every timestep, vfi_ut
 part is timestep independent (M2M_arch.py:936-958) and runs ONCE per pair (``prepare``); only the splat runs per
 timestep (``render``).  Results are identical; multiplier m costs 1 network pass + (m-1) splats.
 """
-import ctypes as C
 import typing
 
 import torch
@@ -30,51 +29,26 @@ from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .lanes import lane_set
 from .m2m_spec import check_state_dict, m2m_shapes
 from . import nodeloop
+from .netengine import NetEngine, WorkspaceBytes
 from .schedule import InterpolationStateList, generic_output_plan
 
 MODEL_TYPE = "m2m"
 RATIO = 4        # M2M_PWC.forward default ratio (the node never overrides it, vfi_models/m2m/__init__.py:51-55)
 
 
-class M2MEngine:
+class M2MEngine(WorkspaceBytes, NetEngine):
     """Device-resident M2M interpolator: ``prepare(frame0, frame1)`` once per pair, ``render(t)`` per timestep — the C-side
     object vfi_m2m_create / vfi_m2m_prepare / vfi_m2m_render / vfi_m2m_destroy (csrc/m2m_object.hip): weights packed once,
     workspace owned by the library, the ~110 launches of a pair issued by one call."""
 
-    def __init__(self, state_dict, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("M2M VFI (HIP): no GPU visible; this node has no CPU fallback")
-        self.lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
-        check_state_dict(state_dict)
-        keys = list(m2m_shapes().keys())
-        tensors = [state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in keys]
-        ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
-        numels = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
-        self.handle = self.lib.vfi_m2m_create(ptrs, numels, len(keys))
-        if not self.handle:
-            raise RuntimeError("vfi_m2m_create failed: " + _lib.last_error())
-        self.hw = None
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.vfi_m2m_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, LABEL = "vfi_m2m", "M2M"
+    shapes = staticmethod(m2m_shapes)
+    check_state_dict = staticmethod(check_state_dict)
+    hw = None           # (H, W) of the prepared pair
 
     def release_workspace(self):
-        """Drop the activations; the packed weights stay on the device."""
-        _lib.check(self.lib.vfi_m2m_release_workspace(self.handle), "vfi_m2m_release_workspace")
+        super().release_workspace()
         self.hw = None
-
-    def workspace_bytes(self):
-        return int(self.lib.vfi_m2m_workspace_bytes(self.handle)) if getattr(self, "handle", None) else 0
 
     def prepare(self, frame0, frame1):
         """frame0/frame1: [H,W,C>=3] fp32 device tensors.  Runs everything that does not depend on the timestep (the frames are
@@ -82,7 +56,7 @@ class M2MEngine:
         H, W, Cc = frame0.shape
         assert frame1.shape == frame0.shape and Cc >= 3 and frame0.is_contiguous() and frame1.is_contiguous()
         assert frame0.is_cuda and frame0.dtype == torch.float32
-        _lib.check(self.lib.vfi_m2m_prepare(self.handle, frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, _lib.stream_ptr()), "vfi_m2m_prepare")
+        self._call("prepare", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, _lib.stream_ptr())
         self.hw = (H, W)
 
     def render(self, t, out=None):
@@ -91,7 +65,7 @@ class M2MEngine:
         H, W = self.hw
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.vfi_m2m_render(self.handle, float(t), out.data_ptr(), _lib.stream_ptr()), "vfi_m2m_render")
+        self._call("render", float(t), out.data_ptr(), _lib.stream_ptr())
         return out
 
     def forward(self, frame0, frame1, t):
