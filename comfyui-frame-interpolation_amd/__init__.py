@@ -16,6 +16,7 @@ _LAZY = {
     "CAIN_VFI": ("cain", "CAIN_VFI"),
     "SepconvVFI": ("sepconv", "SepconvVFI"),
     "FLAVR_VFI": ("flavr", "FLAVR_VFI"),
+    "AMT_VFI": ("amt", "AMT_VFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -56,6 +57,10 @@ def _node_class_mappings():
         from .flavr import FLAVR_VFI
 
         extra["FLAVR VFI"] = FLAVR_VFI
+    if "amt_vfi" in extra_nodes():
+        from .amt import AMT_VFI
+
+        extra["AMT VFI"] = AMT_VFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -70,9 +75,9 @@ def _node_class_mappings():
 
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
 # list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
-# FLAVR's key is the reference's class name lower-cased, "flavr_vfi"; a bare "flavr" is not a key.
+# FLAVR's and AMT's keys are the reference's class names lower-cased, "flavr_vfi" / "amt_vfi"; a bare "flavr" or "amt" is not a key.
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
-               "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)")}
+               "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)")}
 
 
 def extra_nodes():

@@ -66,6 +66,20 @@ def load_file_from_github_release(model_type, ckpt_name):
                     + "\n\n".join(errors))
 
 
+def load_file_from_direct_url(model_type, url):
+    """vfi_utils.load_file_from_direct_url (vfi_utils.py:139-143): <ckpts_path>/<model_type>/<basename of url>, fetched from url when missing"""
+    model_dir = get_ckpt_container_path(model_type)
+    cached = os.path.join(model_dir, os.path.basename(url))
+    if os.path.exists(cached):
+        return cached
+    from torch.hub import download_url_to_file
+
+    os.makedirs(model_dir, exist_ok=True)
+    print(f'Downloading: "{url}" to {cached}\n')
+    download_url_to_file(url, cached, hash_prefix=None, progress=True)
+    return cached
+
+
 # ---- engine cache -------------------------------------------------------------------------------------------------
 # The reference caches its RIFE module across node executions (rife/__init__.py:29-31) but rebuilds FILM and M2M on
 # every call.  Building an engine means re-packing and uploading every weight (~0.15 s for FILM's 138 MB), so the HIP

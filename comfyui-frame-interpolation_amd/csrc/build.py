@@ -30,7 +30,9 @@ EXTRA_FLAGS = {"conv_wino.hip": ["-fno-slp-vectorize"],
                "m2m_net.hip": ["-ffp-contract=off"],
                # the one-kernel M2M render sums in * w products exactly as the reference's atomicAdd(out, in * w): no mul + add may become an
                # fma (a function-scope `#pragma clang fp contract(off)` did not survive inlining: 94 v_fmac_f32 in the first build)
-               "m2m_render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
+               "m2m_render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
+               # the lookup's coordinates are coord + flow * scale with two roundings, as torch computes them; dots and convolutions call fmaf
+               "amt_net.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

@@ -682,6 +682,51 @@ int vfi_flavr_forward(vfi_flavr_t* net, const float* const* frames_dev, int N, i
 int vfi_flavr_release_workspace(vfi_flavr_t* net);
 int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* net);
 
+/* ---- AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L): the kernels beside the layer objects ------------------------------------------- */
+
+/* The target side of the correlation pyramid without the volume: corr[q][p] = <f0[q], f1[p]> / sqrt(D) is linear in f1, so
+ * avg_pool2d(corr[q]) = <f0[q], avg_pool2d(f1)> (BidirCorrBlock.__init__, :1083-1097).  f_dev [h,w,D] -> pooled_dev = levels 1..3
+ * back to back, [h>>l][w>>l][D] each (odd sizes floored as avg_pool2d does): ((h>>1)(w>>1) + (h>>2)(w>>2) + (h>>3)(w>>3)) D floats.
+ * D % 4 == 0; h, w >= 16 (below, the coarsest level is one pixel wide and the reference is all-NaN). */
+int vfi_amt_pool_features(const float* f_dev, int h, int w, int D, float* pooled_dev, void* stream);
+/* One direction of BidirCorrBlock.__call__ (:1099-1131) for radius 3 and 4 levels: for query pixel q with c = (x, y) + flow[q] * scale
+ * (two fp32 roundings, as `coord + flow * t_scale`, :1200), out[q, lvl * 49 + a * 7 + b] = bilinear_zero_pad(<fq[q], ft_lvl[.]> / sqrt(D),
+ * x = c.x / 2^lvl + (a - 3), y = c.y / 2^lvl + (b - 3)): the first window index moves x (the reference adds its (dy, dx) deltas to (x, y)
+ * coordinates, :1112-1120).  fq_dev, ft_dev [h,w,D]; ft_pooled_dev from vfi_amt_pool_features(ft_dev); flow_dev [h,w,flow_cs] = (x, y)
+ * first; out_dev [h,w,out_cs], 196 channels written (the other direction goes to out_dev + 196 with fq / ft exchanged).  Nothing of
+ * size (h w)^2 exists.  D % 4 == 0, D <= 256; h, w >= 16. */
+int vfi_amt_corr_lookup(const float* fq_dev, const float* ft_dev, const float* ft_pooled_dev, const float* flow_dev, int flow_cs, float scale,
+                        int h, int w, int D, float* out_dev, int out_cs, void* stream);
+/* Conv2d(Cin, Cout, 7, stride 1, padding 3) + bias (nullable) + activation (0 none, 1 leaky relu(slope), 3 PReLU(prelu_dev[Cout])) for thin
+ * layers, Cin, Cout <= 96: convf1 of the update blocks (:977, :1031) and AMT-L's comb_block (:1322-1326).  in [N,H,W,in_cs], out
+ * [N,H,W,out_cs].  w_dev: [7][7][Cin4][CoutP] zero-padded, Cin4 = Cin rounded up to 4, CoutP = Cout rounded up to 4 (Cout <= 4) or 16. */
+int vfi_conv7x7(const float* in_dev, int in_cs, const float* w_dev, const float* bias_dev, const float* prelu_dev, float slope, int act,
+                int Cin, int Cout, float* out_dev, int out_cs, int N, int H, int W, void* stream);
+/* multi_flow_combine up to comb_block's input (:883-900): out[.., 3 i + c] = sigmoid(mask_i) * warp(img0, flow0_i)[c] + (1 - sigmoid(mask_i))
+ * * warp(img1, flow1_i)[c] + mean + res_i[c] for the num_flows flow pairs; warp as amt_arch.warp (:26-34: border, align_corners=True).
+ * img{0,1} [Hp,Wp,img_cs] mean-removed, fin [Hp,Wp,fin_cs] = flow0 (2 n) | flow1 (2 n) | mask logits (n) | res (3 n), mean_dev[0]. */
+int vfi_amt_combine_warps(const float* img0_dev, const float* img1_dev, int img_cs, const float* fin_dev, int fin_cs, const float* mean_dev,
+                          int num_flows, float* out_dev, int out_cs, int Hp, int Wp, void* stream);
+/* The tail (:901, :1273, InputPadder.unpad): out [H,W,3] = clamp(mean over flows of warps + comb, 0, 1) cropped at (pad_top, pad_left) */
+int vfi_amt_combine_out(const float* warps_dev, int warps_cs, const float* comb_dev, int comb_cs, int num_flows, float* out_dev, int Hp,
+                        int Wp, int pad_top, int pad_left, int H, int W, void* stream);
+
+typedef struct vfi_amt vfi_amt_t;
+/* The state_dict tensors of AMT-S (variant 0: 213) or AMT-L (variant 1: 207) in amt_spec.amt_shapes(variant) order (fp32 host memory, copied).
+ * Replaces AMT_S.__init__ / AMT_L.__init__ + load_state_dict (vfi_models/amt/amt_arch.py:1153-1188, :1297-1332; amt/__init__.py:61-66). */
+vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, int n_tensors, int variant);
+void vfi_amt_destroy(vfi_amt_t* net);
+/* clamp(unpad(model(pad(frame0), pad(frame1), embt = t)), 0, 1) for ONE pair and n_t timesteps ts_host[0 .. n_t) in (0, 1) (amt_arch.py:1205-1285,
+ * :1349-1429; amt/__init__.py:88-97): frames [H,W,C>=3] fp32 (not written), out_dev [n_t,H,W,3].  Once per call: the centred replicate pad to
+ * multiples of 16, mean_, the feature encoder on both frames, both pyramid encoders, the pooled feature maps.  Per timestep: decoders, lookups,
+ * update blocks, multi_flow_combine, clamp, un-pad; a timestep's result does not depend on the others of its call.  No correlation volume is
+ * built.  Frames whose padded side is below 128 (the reference is all-NaN there) or whose padded size exceeds 2^23 - 1 pixels are refused
+ * before any launch. */
+int vfi_amt_forward(vfi_amt_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ts_host, int n_t,
+                    float* out_dev, void* stream);
+int vfi_amt_release_workspace(vfi_amt_t* net);
+int64_t vfi_amt_workspace_bytes(const vfi_amt_t* net);
+
 #ifdef __cplusplus
 }
 #endif
