@@ -36,7 +36,7 @@ c_int_p = C.POINTER(C.c_int)
 c_i64_p = C.POINTER(C.c_longlong)
 
 # name -> (restype, argtypes); PROTOTYPES mirrors include/vfi_hip.h one to one, TEST_PROTOTYPES include/vfi_hip_test.h
-TEST_NAMES = ("vfi_conv3x3_naive", "vfi_test_conv_algo", "vfi_test_pack_wino3x3", "vfi_test_pack_deconv3x3", "vfi_test_set_option", "vfi_test_variant_override", "vfi_test_wino_probe_read", "vfi_rife_debug_keep", "vfi_rife_debug_read", "vfi_test_film_schedule", "vfi_test_linspace01", "vfi_film_debug_read_flow", "vfi_m2m_debug_read")
+TEST_NAMES = ("vfi_conv3x3_naive", "vfi_test_conv_algo", "vfi_test_pack_wino3x3", "vfi_test_pack_deconv3x3", "vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_wino_probe_read", "vfi_rife_debug_keep", "vfi_rife_debug_read", "vfi_test_film_schedule", "vfi_test_linspace01", "vfi_film_debug_read_flow", "vfi_m2m_debug_read")
 PROTOTYPES = {
     "vfi_init": (C.c_int, [C.c_int]),
     "vfi_last_error": (C.c_char_p, []),
@@ -56,6 +56,7 @@ PROTOTYPES = {
     "vfi_test_pack_deconv3x3": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
     "vfi_test_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "vfi_test_variant_override": (C.c_int, [C.c_char_p]),
+    "vfi_test_last_conv_launch": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
     "vfi_test_wino_probe_read": (C.c_int, [C.POINTER(C.c_uint32)]),
     "vfi_deconv4x4_ps2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p]),

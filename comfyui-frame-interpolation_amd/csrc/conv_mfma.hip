@@ -329,6 +329,7 @@ static int launch_t(ConvArgs a, hipStream_t s, const char* name) {
                 name, a.Cout_p, WN * NT * 32);
     dim3 grid(a.N * a.tiles_x * a.tiles_y, GROUPED ? a.Cout_p / 32 : a.Cout_p / (WN * NT * 32));
     TraceScope ts(name, s);
+    conv_record_launch(kConvFamilyGen1, 0, a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2, a.out_mode, 1, grid.x, grid.x);
     if (a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2)
         hipLaunchKernelGGL((conv_mfma_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, true>), grid, dim3(256), 0, s, a);
     else
@@ -422,6 +423,7 @@ int conv_launch(const ConvArgs& a, int stride, bool grouped, int variant, hipStr
                 "conv: bad channel padding Cin_p=%d Cout_p=%d in_cs=%d", a.Cin_p, a.Cout_p, a.in_cs);
     VFI_REQUIRE(((uintptr_t)a.in & 15) == 0 && ((uintptr_t)a.w & 15) == 0, "conv: unaligned pointers");
     const char* nm = trace_name ? trace_name : v.name;
+    conv_record_variant(variant);
     if (variant >= kConv2Base) return conv2_launch(a, variant - kConv2Base, s, nm);
     switch (variant) {
         case 0: return launch_t<1, 9, 2, 2, 4, 1, 16, false>(a, s, nm);

@@ -595,6 +595,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         p.out = ws, p.out_cs = a.Cout_p, p.bias = zeros, p.beta = nullptr, p.res = nullptr, p.res_cs = 0;
         p.act = 0, p.post_scale = 0.f, p.post_shift = 0.f, p.Cout = a.Cout_p;
         p.ksplit = ks, p.split_stride = (long)slice;
+        conv_record_launch(kConvFamilyGen2, 0, MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, ks, T, T);
         {
             TraceScope ts(name, s);
             // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_mode implies EXT)
@@ -611,6 +612,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     if (gx > T || (long)T * ny < 4L * cus * occ) gx = T;
     if (MASKED) gx = T;      // N blocks carry 1, 2, 2 or 4 taps: one workgroup per tile, the dispatcher balances them
     dim3 grid(gx, ny);
+    conv_record_launch(kConvFamilyGen2, 0, MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, 1, gx, T);
     TraceScope ts(name, s);
     hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>), grid, dim3(256), G::LDS_BYTES, s, a);
     VFI_CHECK_HIP(hipGetLastError());

@@ -809,6 +809,7 @@ static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     grid = round_up(grid, 8);
     p.xcd_map = option(kOptWinoXcd) ? 1 : 0;
     p.clk_tag = clock_probe_tag(name);
+    conv_record_launch(kConvFamilyWino, RTX, MODE, SHUF, 1, grid, items);
     TraceScope ts(name, s);
     hipLaunchKernelGGL((conv_wino_kernel<RTX, MODE, SHUF, PROBE>), dim3(grid), dim3(256), G::LDS_BYTES, s, p);
     VFI_CHECK_HIP(hipGetLastError());

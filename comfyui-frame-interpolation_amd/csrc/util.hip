@@ -67,6 +67,28 @@ int variant_override(const char* trace_name) {
     auto it = g_variant_override.find(trace_name);
     return it == g_variant_override.end() ? -1 : it->second;
 }
+// ---- the last convolution launch of this thread (vfi_common.h) ----
+#ifdef VFI_TEST_TAPS
+static thread_local int32_t g_conv_rec[8] = {0, -1, 0, 0, 0, 0, 0, 0};      // family, variant, form, store, ks, grid.x, work, launches so far
+static thread_local int g_conv_rec_variant = -1;
+void conv_record_variant(int variant) { g_conv_rec_variant = variant; }
+void conv_record_launch(int family, int wino_region, int form, int store, int ks, long grid_x, long work) {
+    g_conv_rec[0] = family;
+    g_conv_rec[1] = family == kConvFamilyWino ? wino_region : g_conv_rec_variant;
+    g_conv_rec[2] = form, g_conv_rec[3] = store, g_conv_rec[4] = ks;
+    g_conv_rec[5] = (int32_t)grid_x, g_conv_rec[6] = (int32_t)work;
+    g_conv_rec[7] += 1;
+    g_conv_rec_variant = -1;
+}
+int conv_record_read(int32_t* out, int cap) {
+    const int n = cap < 8 ? cap : 8;
+    for (int i = 0; i < n; ++i) out[i] = g_conv_rec[i];
+    return n;
+}
+#else
+void conv_record_variant(int) {}
+void conv_record_launch(int, int, int, int, int, long, long) {}
+#endif
 #ifdef VFI_TEST_TAPS
 static void variant_override_set(const char* spec) {      // "conv0a_b3=42,resconv_c128=36"; empty / null clears
     std::lock_guard<std::mutex> lk(g_opt_mu);
@@ -295,6 +317,10 @@ int vfi_test_set_option(const char* name, int64_t value) { return option_set(nam
 int vfi_test_variant_override(const char* spec) {
     variant_override_set(spec);
     return 0;
+}
+int vfi_test_last_conv_launch(int32_t* out, int cap) {
+    VFI_REQUIRE(out && cap > 0, "vfi_test_last_conv_launch: no buffer");
+    return conv_record_read(out, cap);
 }
 #endif
 

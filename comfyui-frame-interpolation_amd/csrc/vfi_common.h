@@ -85,6 +85,14 @@ hipStream_t stream_apart_from(hipStream_t st);
 void stream_give_back(hipStream_t side);      // to the idle list stream_apart_from draws its candidates from (never destroyed)
 int option_set(const char* name, long value);      // 0, or -2 for an unknown name
 int variant_override(const char* trace_name);      // tile variant forced for a trace name (vfi_test_variant_override), -1 = none
+// What the calling thread's last convolution launch was (vfi_test_last_conv_launch): written by the host-side launchers launch_t,
+// launch2_e and wino_launch_t.  Stores under VFI_TEST_TAPS only; in the product library both are empty functions.
+//   family 1 / 2 = first / second generation direct kernel, 3 = Winograd;  form: direct 0 plain, 1 EXT, 2 MASKED; Winograd MODE;
+//   store: out_mode (direct) / SHUF (Winograd);  ks: split-K slices (1 = unsplit);  work: tiles (direct) / work items (Winograd)
+enum { kConvFamilyGen1 = 1, kConvFamilyGen2 = 2, kConvFamilyWino = 3 };
+void conv_record_variant(int variant);      // conv_launch: the direct variant id in the common numbering, kept for the launcher's record
+void conv_record_launch(int family, int wino_region, int form, int store, int ks, long grid_x, long work);   // wino_region: 8 / 16, direct: 0
+int conv_record_read(int32_t* out, int cap);
 
 // Compute units the persistent kernels may size their grids for: the device's count minus what vfi_set_reserved_cus holds back for a
 // collective kernel running beside them (a resident RCCL kernel takes whole CUs from one-workgroup-per-CU kernels, whose displaced

@@ -49,6 +49,17 @@ int vfi_test_set_option(const char* name, int64_t value);
 int vfi_test_wino_probe_read(uint32_t* out32);
 /* Force direct-conv tile variants by trace name: "conv0a_b3=42,resconv_c128=36"; NULL / "" clears (tools/variant_sweep.sh). */
 int vfi_test_variant_override(const char* spec);
+/* What the calling thread's most recent convolution launch was (any launch made through the direct kernels' or the Winograd kernel's
+ * launcher: layer objects, vfi_conv3x3, the networks): up to 8 int32 to `out` —
+ *   [0] kernel family: 1 first-generation direct (csrc/conv_mfma.hip), 2 second-generation direct (conv_mfma2.hip), 3 Winograd; 0 = none yet
+ *   [1] direct: tile variant id in the common numbering (0.. / 32..); Winograd: region shape 8 (16x8 pixels) / 16 (32x4)
+ *   [2] direct: 0 plain, 1 EXT, 2 MASKED instantiation; Winograd: the epilogue MODE (0, 1, 10 .. 15)
+ *   [3] the store form: out_mode (direct) / SHUF (Winograd)
+ *   [4] split-K slices (1 = unsplit; > 1: the epilogue ran in the reduce kernel)
+ *   [5] grid.x   [6] tiles (direct) / work items (Winograd): grid.x < [6] is a persistent launch
+ *   [7] launches this thread has made so far.
+ * Host only, touches no kernel.  Returns the number of ints written or < 0. */
+int vfi_test_last_conv_launch(int32_t* out, int cap);
 
 /* Debug taps for parity tests: copy internal tensors of the LAST interpolate call to host.
  * what: 0 = flow after stage `stage` [B,Hp,Wp,4];  1 = stage input X of `stage`, planar4 [B,Cx/4,Hs,Ws,4];

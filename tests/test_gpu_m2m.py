@@ -64,7 +64,7 @@ LAYERS = [
     (0, 1, 1, 0, 4, 256, 16, 2, 9, 1),        # cube conv_H
     (0, 3, 1, 0, 1, 1920, 256, 1, 16, 30),    # FILM's coarsest flow-estimator conv: 32 workgroups -> split-K over 16 (conv_mfma2.hip)
     (0, 3, 1, 0, 1, 1920, 256, 1, 33, 60),    # ... split over fewer
-    (0, 1, 1, 0, 5, 1024, 128, 1, 17, 30),    # 1x1 + GELU, split-K: the epilogue runs in the reduce kernel
+    (0, 1, 1, 0, 5, 1024, 128, 1, 17, 30),    # 1x1 + GELU, long K (d1t1_m2n2w22k32); not split: TAPS * Cin_p / 576 caps ks at 1 (split + GELU in the reduce kernel: test_gpu_conv_exact.py)
     (0, 3, 2, 0, 3, 768, 128, 1, 18, 30),     # stride 2 + per-channel PReLU, split-K
     (0, 1, 1, 0, 5, 256, 1024, 2, 34, 60),    # GMFlow's FFN: Linear(2c, 8c) + nn.GELU() in the epilogue (interior tiles)
     (0, 1, 1, 0, 5, 256, 1024, 1, 5, 7),      # ... and border tiles

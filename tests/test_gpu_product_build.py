@@ -19,7 +19,7 @@ import torch
 from cfi_amd import _lib, synth
 lib = _lib.load()
 assert not _lib.is_test_build()
-for tap in ("vfi_test_set_option", "vfi_test_variant_override", "vfi_test_conv_algo", "vfi_rife_debug_read", "vfi_m2m_debug_read"):
+for tap in ("vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_conv_algo", "vfi_rife_debug_read", "vfi_m2m_debug_read"):
     assert not hasattr(lib, tap), tap
 loaded = [l.split()[-1] for l in open("/proc/self/maps") if "libvfi_hip" in l]
 assert loaded and all(p.endswith("libvfi_hip.so") for p in loaded), loaded
