@@ -56,6 +56,7 @@ int vfi_conv3x3(const float* in_dev, const float* weight_host, const float* bias
     conv3x3_taps(a);
     int v = variant;
     a.Cin_p = round_up(Cin, 8);
+    a.cin_live = Cin;
     const bool wino = v == 100 || v == 101;      // Winograd F(2x2,3x3) form (conv_wino.hip): 16x8 / 32x4 pixel regions
     VFI_REQUIRE(!wino || stride == 1, "vfi_conv3x3: the Winograd variants are stride 1");
     if (v < 0) v = conv_pick_variant(a, stride, false);

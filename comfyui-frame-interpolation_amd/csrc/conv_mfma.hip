@@ -384,7 +384,8 @@ int conv_pick_variant(const ConvArgs& a, int stride, bool grouped) {
     const bool n2 = a.Cout_p % 64 == 0;
     (void)cus;
     if (stride == 2) {
-        if (n2) return kConv2Base + 7;   // d2_m1n2
+        // d2_m1n2; with 4 live channels in the last chunk its live-K form (same bits, a sixth of RIFE's 20 -> 24 conv0.0 MFMAs less)
+        if (n2) return kConv2Base + (a.cin_live == a.Cin_p - 4 && !a.split_ok && !a.pad_mode && a.act < 3 && a.post_scale == 0.f && !a.out_mode ? 30 : 7);
         if (n3) return kConv2Base + 9;   // d2_m1n3 (r6: 0.924 -> 0.832 ms on RIFE's conv0b_b2 against the first-generation s2_m1n3, same bits)
         return 10;                       // s2_m1n1
     }

@@ -64,12 +64,18 @@ struct Conv2Geom {
 // (y + a, x + b), a <= py, b <= px, with the 2x2 weights summed over the taps that land on the same input pixel — 1 + 2 + 2 + 4 = 9 tap
 // blocks instead of 16, no up-sampled tensor.  The four parities are 4 * Cout output channels; an N block belongs to one parity, walks only
 // that parity's taps (a.tapmask[blockIdx.y]) and stores its pixels interleaved into the [2H, 2W] output.
-template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false>
+// TAIL4 (stride-2 3x3, 8-channel chunks): the layer's last chunk holds 4 live input channels and 4 of padding (RIFE's conv0.0 from
+// block 1 on: 20 -> 24) whose weights are zero.  A K-step of that chunk then runs 2 MFMA rounds instead of 4: lane half h supplies
+// floats [h] and [2 + h] of the pixel's chunk and of the weight row, i.e. the channel pairs (0|1), (2|3) — the live terms of the
+// plain form's (0|4), (1|5), (2|6), (3|7) in the same order, without its four fma(x, 0, acc).  DMA, LDS image and epilogue are the
+// plain form's.
+template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false>
 __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource / LDS-DMA builtins do not exist in the host pass
     using G = Conv2Geom<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED>;
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(!GROUPED || (WN == 4 && NT == 1 && TAPS == 4), "grouped: one 2x2 tap group per wave column");
+    static_assert(!TAIL4 || (STRIDE == 2 && TAPS == 9 && CK == 8 && !GROUPED && !MASKED), "live-K tail: stride-2 3x3, 8-channel chunks");
     constexpr int KW = G::KW, SUBX = G::SUBX, TWO = G::TWO, THO = G::THO, TWI = G::TWI;
     constexpr int Q = G::Q, C8 = G::C8, BN = G::BN;
 
@@ -270,6 +276,36 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
                 if (ntl == 1) run(std::integral_constant<int, 1>{});
                 else if (ntl == 2) run(std::integral_constant<int, 2>{});
                 else run(std::integral_constant<int, 4>{});
+            } else if (TAIL4 && k0 + k + 1 == a.Cin_p / CK) {
+                // the layer's last chunk: 4 live channels.  The plain loop below with 2 rounds per K-step (one K-step per tap: CK == 8).
+                auto frag_t = [&](int t, f32x4(&fa)[MT], f32x4(&fb)[NT]) {
+                    const int toff = ((t / KW) * TWI + (t % KW)) * CK - 3 * half;      // the half's 4-float step taken back to 1
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) fa[mt][0] = sb[abase[mt] + toff], fa[mt][1] = sb[abase[mt] + toff + 2];
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        const int boff = bbase - 3 * half + (t * BN + nt * 32) * 8;
+                        fb[nt][0] = sb[boff], fb[nt][1] = sb[boff + 2];
+                    }
+                };
+                frag_t(0, av[0], bv[0]);
+#pragma unroll
+                for (int st = 0; st < NS; ++st) {
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt)
+                                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[st & 1][mt][j], bv[st & 1][nt][j], acc[mt][nt], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (j == 0 && st + 1 < NS) {
+                            frag_t(st + 1, av[(st + 1) & 1], bv[(st + 1) & 1]);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                }
             } else {
             frag(0, av[0], bv[0]);
 #pragma unroll
@@ -525,7 +561,7 @@ static int split_reduce(const ConvArgs& a, const float* ws, int ks, size_t slice
     return 0;
 }
 
-template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false>
+template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false>
 static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     using G = Conv2Geom<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED>;
     a.ksplit = 0, a.split_stride = 0;      // launcher-owned fields (callers do not set them)
@@ -535,6 +571,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     VFI_REQUIRE(a.Cout_p % G::BN == 0, "conv2 %s: Cout_p=%d not a multiple of the N tile %d", name, a.Cout_p, G::BN);
     VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
     VFI_REQUIRE(!a.in_plane || a.in_plane >= a.Hin * a.Win * 4, "conv2 %s: bad plane stride", name);
+    VFI_REQUIRE(!TAIL4 || a.cin_live == a.Cin_p - 4, "conv2 %s: the live-K tail needs 4 live channels in the last chunk (Cin %d of %d)", name, a.cin_live, a.Cin_p);
     // resident workgroups per CU of this instantiation and the CU count, PER DEVICE: one process may drive several
     // devices from several threads (multidev.py), and hipFuncSetAttribute applies to the current device only
     static std::atomic<int> occ_of[kMaxDevices];
@@ -545,11 +582,11 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     int occ = occ_of[dev].load(std::memory_order_acquire);
     if (!occ) {
         VFI_CHECK_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>),
+            reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>),
             hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
         int o = 0;
         VFI_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &o, reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>), 256,
+            &o, reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), 256,
             G::LDS_BYTES));
         hipDeviceProp_t p;
         VFI_CHECK_HIP(hipGetDeviceProperties(&p, dev));
@@ -599,7 +636,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         {
             TraceScope ts(name, s);
             // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_mode implies EXT)
-            hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>), dim3(T, ny, ks), dim3(256), G::LDS_BYTES, s, p);
+            hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), dim3(T, ny, ks), dim3(256), G::LDS_BYTES, s, p);
             VFI_CHECK_HIP(hipGetLastError());
         }
         return split_reduce(a, ws, ks, slice, s);
@@ -614,7 +651,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     dim3 grid(gx, ny);
     conv_record_launch(kConvFamilyGen2, 0, MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, 1, gx, T);
     TraceScope ts(name, s);
-    hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED>), grid, dim3(256), G::LDS_BYTES, s, a);
+    hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), grid, dim3(256), G::LDS_BYTES, s, a);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -624,6 +661,13 @@ static int launch2_masked(const ConvArgs& a, hipStream_t s, const char* name) {
     VFI_REQUIRE(a.tapmask && a.par_cout > 0 && a.par_cout % (WN * NT * 32) == 0 && a.Cout_p == 4 * a.par_cout && a.act <= 1 && !a.res && !a.beta && !a.in_plane,
                 "conv2 %s: masked (up-sample x2 + 2x2) form needs 4 parity groups of a multiple of %d channels, act none / LeakyReLU", name, WN * NT * 32);
     return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, false, true>(a, s, name);
+}
+
+// stride-2 3x3 with the live-K tail (TAIL4): RIFE's conv0.0 layers only — plain feature set, never split
+template <int MT, int NT>
+static int launch2_tail(const ConvArgs& a, hipStream_t s, const char* name) {
+    VFI_REQUIRE(!(a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode), "conv2 %s: the live-K tail variants have the plain feature set only", name);
+    return launch2_e<2, 9, MT, NT, 4, 1, 8, false, false, false, true>(a, s, name);
 }
 
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED>
@@ -667,8 +711,15 @@ static const ConvVariant kVariants2[] = {
     {"d1t4_m1n2k16_up2", 1, 4, 1, 2, 4, 1, 16, 0},  // 60
     {"d1_m1n1", 1, 9, 1, 1, 4, 1, 8, 0},            // 61: 3x3, 16x8 px x 32 ch — coarse pyramid levels (r6): twice the workgroups, half the serial K loop
 };
-int conv2_num_variants() { return (int)(sizeof(kVariants2) / sizeof(kVariants2[0])); }
-const ConvVariant& conv2_variant(int i) { return kVariants2[i]; }
+// Live-K twins of tiles above, numbered on from them: the same tile and K order for layers whose last chunk has 4 live input channels
+// (Cin % 8 == 4); that chunk runs 2 MFMA rounds per K-step (TAIL4), same bits.  A table of their own: every row of kVariants2 has its
+// exact-sum cases in tests/conv_exact_cases.py, a twin is compared with its tile bit for bit (tests/test_gpu_rife_live_k.py).
+static const ConvVariant kLiveTwins2[] = {
+    {"d2_m1n2_live4", 2, 9, 1, 2, 4, 1, 8, 0},      // 62: twin of 39
+};
+constexpr int kNumVariants2 = (int)(sizeof(kVariants2) / sizeof(kVariants2[0]));
+int conv2_num_variants() { return kNumVariants2 + (int)(sizeof(kLiveTwins2) / sizeof(kLiveTwins2[0])); }
+const ConvVariant& conv2_variant(int i) { return i < kNumVariants2 ? kVariants2[i] : kLiveTwins2[i - kNumVariants2]; }
 
 int conv2_launch(const ConvArgs& a, int idx, hipStream_t s, const char* nm) {
     switch (idx) {
@@ -702,6 +753,7 @@ int conv2_launch(const ConvArgs& a, int idx, hipStream_t s, const char* nm) {
         case 27: return launch2_masked<1, 4, 2, 2, 4, 1, 16>(a, s, nm);
         case 28: return launch2_masked<1, 4, 1, 2, 4, 1, 16>(a, s, nm);
         case 29: return launch2_t<1, 9, 1, 1, 4, 1, 8, false>(a, s, nm);
+        case 30: return launch2_tail<1, 2>(a, s, nm);
     }
     set_error("conv2: bad variant %d", idx);
     return -3;

@@ -103,6 +103,12 @@ struct vfi_rife {
     int up[kMaxBlocks] = {1, 1, 1, 1, 1};      // 1/scale for fractional block scales 0.5 / 0.25 (scale_factor 2 / 4)
     // workspace
     DevBuf Ppool, E, F, F2, M, X, A0, A1, A2, T;   // F2: the flow's second buffer for the fused last transition
+    // Block-0 staging images, one per slot beside its pack (rife_ops.hip: enc_stage0_cells), written by the fused frame pack kernels.
+    // s0_valid[slot]: the slot's last load wrote it (a load through the three-kernel path does not: that slot's pairs are gathered).
+    DevBuf S0pool;
+    std::vector<unsigned char> s0_valid;
+    size_t stage0_stride() const { return (size_t)(Hp / 8) * (Wp / 8) * 8; }
+    bool fused_pack() const { return n_mid == 0 && CM == 16 && CF == 4 && !enc_act && NF == 1; }
     DevBuf X1, T1;  // frame-resolution staging around blocks that run above the frame resolution
     DevBuf Fdbg[kMaxBlocks], Xdbg[kMaxBlocks];
     bool keep = false;
@@ -339,7 +345,7 @@ void vfi_rife_destroy(vfi_rife_t* net) {
     }
     net->E2.release();
     for (DevBuf* d : {&net->enc_w0, &net->enc_b0, &net->enc_w1, &net->enc_b1, &net->Ppool, &net->E, &net->F, &net->F2, &net->M,
-                      &net->X, &net->A0, &net->A1, &net->A2, &net->T, &net->X1, &net->T1, &net->FEAT})
+                      &net->X, &net->A0, &net->A1, &net->A2, &net->T, &net->X1, &net->T1, &net->FEAT, &net->S0pool})
         d->release();
     if (net->arena) (void)hipFree(net->arena);
     delete net;
@@ -411,6 +417,8 @@ int vfi_rife_configure(vfi_rife_t* net, int H, int W, int max_batch, int n_slots
         return -1;
     if (any_up && (net->X1.ensure(B * full * net->CX(1)) || net->T1.ensure(B * full * 4 * net->tplanes()))) return -1;
     if (net->NX && net->FEAT.ensure(B * full * 8)) return -1;
+    net->s0_valid.assign(n_slots, 0);
+    if (net->fused_pack() && net->S0pool.ensure(net->stage0_stride() * n_slots)) return -1;
     return 0;
 }
 
@@ -429,6 +437,7 @@ static void fill_args(ConvArgs& a, const ConvLayer& L, const float* in, int in_c
     a.Wout = Win / stride;
     a.out_cs = out_cs;
     a.Cin_p = L.Cin_p;
+    a.cin_live = L.Cin;
     a.Cout_p = L.Cout_p;
     a.Cout = L.Cout;
 }
@@ -442,8 +451,14 @@ static int load_frame_impl(vfi_rife_t* net, int slot, const float* f32, const un
     // arch 4.7 (encode = Conv(3,16,s2) -> Deconv(16,4), no activation, no mid convs): the whole pack in one launch, the half-resolution
     // tensor E never reaches HBM.  Option fuse_encode = 0 keeps the three kernels (A/B measurements, the bit-identity test).
     const bool fuse_encode = option(kOptFuseEncode) != 0;
-    if (fuse_encode && net->n_mid == 0 && net->CM == 16 && net->CF == 4 && !net->enc_act && net->NF == 1)
-        return encode47_fused_launch(f32, u8, P, net->enc_w0.p, net->enc_b0.p, net->enc_w1.p, net->enc_b1.p, net->H, net->W, C, Hp, Wp, st);
+    net->s0_valid[slot] = 0;
+    if (fuse_encode && net->fused_pack()) {
+        if (encode47_fused_launch(f32, u8, P, net->S0pool.p + (size_t)slot * net->stage0_stride(), net->enc_w0.p, net->enc_b0.p, net->enc_w1.p, net->enc_b1.p,
+                                  net->H, net->W, C, Hp, Wp, st))
+            return -1;
+        net->s0_valid[slot] = 1;
+        return 0;
+    }
     if (u8 ? prep_frame_u8_launch(u8, P, net->H, net->W, C, Hp, Wp, st) : prep_frame_launch(f32, P, net->H, net->W, C, Hp, Wp, st))
         return -1;
     if (encode_conv_launch(P, net->E.p, net->enc_w0.p, net->enc_b0.p, net->CM, net->enc_act, Hp, Wp, st)) return -1;
@@ -485,18 +500,24 @@ int vfi_rife_load_frames(vfi_rife_t* net, int n, const int* slots, const void* c
         VFI_REQUIRE(slots[i] >= 0 && slots[i] < net->n_slots && frames_dev[i], "vfi_rife_load_frames: bad slot %d / null frame at %d", slots[i], i);
         for (int j = 0; j < i; ++j) VFI_REQUIRE(slots[j] != slots[i], "vfi_rife_load_frames: slot %d listed twice", slots[i]);
     }
-    const bool fused = option(kOptFuseEncode) != 0 && option(kOptEncodeBatched) != 0 && net->n_mid == 0 && net->CM == 16 && net->CF == 4 &&
-                       !net->enc_act && net->NF == 1;
+    const bool fused = option(kOptFuseEncode) != 0 && option(kOptEncodeBatched) != 0 && net->fused_pack();
     if (!fused || n < 2) {
         for (int i = 0; i < n; ++i)
             if (int rc = load_frame_impl(net, slots[i], is_u8 ? nullptr : (const float*)frames_dev[i], is_u8 ? (const unsigned char*)frames_dev[i] : nullptr, C, stream))
                 return rc;
         return 0;
     }
-    std::vector<float*> packs(n);
-    for (int i = 0; i < n; ++i) packs[i] = net->Ppool.p + (size_t)slots[i] * net->pack_stride();
-    return encode47_batch_launch(n, frames_dev, is_u8 != 0, packs.data(), net->enc_w0.p, net->enc_b0.p, net->enc_w1.p, net->enc_b1.p, net->H, net->W, C,
-                                 net->Hp, net->Wp, (hipStream_t)stream);
+    std::vector<float*> packs(n), stages(n);
+    for (int i = 0; i < n; ++i) {
+        packs[i] = net->Ppool.p + (size_t)slots[i] * net->pack_stride();
+        stages[i] = net->S0pool.p + (size_t)slots[i] * net->stage0_stride();
+        net->s0_valid[slots[i]] = 0;
+    }
+    if (encode47_batch_launch(n, frames_dev, is_u8 != 0, packs.data(), stages.data(), net->enc_w0.p, net->enc_b0.p, net->enc_w1.p, net->enc_b1.p, net->H,
+                              net->W, C, net->Hp, net->Wp, (hipStream_t)stream))
+        return -1;
+    for (int i = 0; i < n; ++i) net->s0_valid[slots[i]] = 1;
+    return 0;
 }
 
 int vfi_f32_to_u8(const float* in_dev, uint8_t* out_dev, int64_t n, void* stream) {
@@ -543,7 +564,12 @@ int vfi_rife_interpolate(vfi_rife_t* net, int B, const int* slot0, const int* sl
         // X of this block: block 0 has no flow yet; later blocks get X from the fused transition kernel of the
         // previous iteration when the scale list allows it (standard [8,4,2,1]), else from stage_in.
         const bool x_ready = i > 0 && (fused_prev || a0_ready);
-        if (!x_ready &&
+        // Block 0 at the standard scale list: X from the slots' staging images (one gather per frame at load, not one per pair here)
+        bool staged0 = i == 0 && option(kOptStage0) != 0 && s == 8 && u == 1 && net->fused_pack() && CX == 16;
+        for (int b = 0; b < B && staged0; ++b) staged0 = net->s0_valid[tasks.slot0[b]] && net->s0_valid[tasks.slot1[b]];
+        if (staged0) {
+            if (stage_in0_staged_launch(net->S0pool.p, net->stage0_stride(), tasks, B, net->X.p, Hp, Wp, st)) return -1;
+        } else if (!x_ready &&
             stage_in_launch(net->Ppool.p, net->pack_stride(), tasks, B, Fcur, net->M.p, i > 0 ? feat : nullptr,
                             u > 1 ? net->X1.p : net->X.p, Hp, Wp, s, CX, NF, i > 0, st))
             return -1;

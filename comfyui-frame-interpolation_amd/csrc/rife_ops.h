@@ -13,11 +13,14 @@ struct RifeTasks {
 
 int warp_border_launch(const float* in, const float* flow, float* out, int N, int H, int W, int C, hipStream_t s);
 int prep_frame_launch(const float* src, float* P, int H, int W, int C, int Hp, int Wp, hipStream_t s);
-// arch 4.7: prep + encode.0 + encode.1 in one launch (exactly one of f32 / u8 non-null)
-int encode47_fused_launch(const float* f32, const unsigned char* u8, float* P, const float* w0, const float* b0, const float* w1, const float* b1,
-                          int H, int W, int C, int Hp, int Wp, hipStream_t s);
-int encode47_batch_launch(int n, const void* const* srcs, bool u8, float* const* packs, const float* w0, const float* b0, const float* w1,
+// arch 4.7: prep + encode.0 + encode.1 in one launch (exactly one of f32 / u8 non-null).  S / stages (nullable): the frame's block-0
+// staging image, planar4 [2][Hp/8][Wp/8][4] = the 2x2 centre mean of every 8x8 cell of the pack (rgb | features), written beside it
+int encode47_fused_launch(const float* f32, const unsigned char* u8, float* P, float* S, const float* w0, const float* b0, const float* w1,
                           const float* b1, int H, int W, int C, int Hp, int Wp, hipStream_t s);
+int encode47_batch_launch(int n, const void* const* srcs, bool u8, float* const* packs, float* const* stages, const float* w0, const float* b0,
+                          const float* w1, const float* b1, int H, int W, int C, int Hp, int Wp, hipStream_t s);
+// block 0's X (16 channels, block scale 8, NF = 1) assembled from the two slots' staging images: what stage_in_launch gives there
+int stage_in0_staged_launch(const float* Spool, size_t stage_stride, const RifeTasks& tasks, int B, float* X, int Hp, int Wp, hipStream_t st);
 int prep_frame_u8_launch(const unsigned char* src, float* P, int H, int W, int C, int Hp, int Wp, hipStream_t s);
 int f32_to_u8_launch(const float* in, unsigned char* out, long n, hipStream_t s);
 // Head: first conv 3 -> CM (stride 2, optional LeakyReLU) into E [Hp/2][Wp/2][CM]; last layer CM -> CF transposed conv

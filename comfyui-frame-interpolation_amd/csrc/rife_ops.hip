@@ -245,10 +245,46 @@ constexpr int ENC_T = 32;                      // output tile
 constexpr int ENC_TE = ENC_T / 2 + 2;          // E tile (18)
 constexpr int ENC_TI = 2 * ENC_TE + 1;         // source tile (37)
 
+
+// Block 0's input at the standard scale list (block scale 8, stage_in_kernel<false, 2, ...>) is the 1/8 down-resize of
+// cat(img0, img1, f0, f1, t): per FRAME the 2x2 centre mean of every 8x8 cell of its pack.  The frame pack kernels leave that mean
+// beside the pack, in a staging image S = planar4 [2][Hp/8][Wp/8][4] (plane 0 rgb, plane 1 features), so that a frame's cells are
+// gathered once per load and not once per pair it takes part in.  A 32x32 tile holds 4x4 whole cells.  Called at the end of phase 2
+// by every thread that reached it: thread (lx, ly) holds the feature quad acc[2 py + px] of pixels (2 ly + py, 2 lx + px); a cell's
+// centre pixels 8e + 3, 8e + 4 are (ly = 4e + 1, py = 1) and (ly = 4e + 2, py = 0), likewise in x — one wave holds all four.
+// stage_in_kernel's expressions: 0.5 left + 0.5 right, then 0.5 top + 0.5 bottom.
+__device__ __forceinline__ void enc_stage0_cells(const float4* __restrict__ sI, const float (&acc)[4][4], float* __restrict__ S, int Y0, int X0,
+                                                 int Hp, int Wp, int tid) {
+    const int lx = tid & 15, ly = tid >> 4;
+    const bool top = (ly & 3) == 1;
+    float f[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float left = top ? acc[3][c] : acc[1][c];
+        const float right = __shfl_down(top ? acc[2][c] : acc[0][c], 1);      // of thread lx + 1
+        const float row = __fadd_rn(0.5f * left, 0.5f * right);
+        f[c] = __fadd_rn(0.5f * row, 0.5f * __shfl_down(row, 16));              // bottom row: thread ly + 1
+    }
+    const int Hs = Hp / 8, Ws = Wp / 8;
+    const int cy = Y0 / 8 + (ly >> 2), cx = X0 / 8 + (lx >> 2);
+    if (top && (lx & 3) == 1 && cy < Hs && cx < Ws) {
+        const float4* q = sI + (8 * (ly >> 2) + 6) * ENC_TI + 8 * (lx >> 2) + 6;      // pixel (Y0 + 8e + 3, X0 + 8d + 3): source-tile offset 3
+        const float4 a = q[0], b = q[1], c = q[ENC_TI], d = q[ENC_TI + 1];
+        float4 r0, r1, r;
+        r0.x = __fadd_rn(0.5f * a.x, 0.5f * b.x), r1.x = __fadd_rn(0.5f * c.x, 0.5f * d.x), r.x = __fadd_rn(0.5f * r0.x, 0.5f * r1.x);
+        r0.y = __fadd_rn(0.5f * a.y, 0.5f * b.y), r1.y = __fadd_rn(0.5f * c.y, 0.5f * d.y), r.y = __fadd_rn(0.5f * r0.y, 0.5f * r1.y);
+        r0.z = __fadd_rn(0.5f * a.z, 0.5f * b.z), r1.z = __fadd_rn(0.5f * c.z, 0.5f * d.z), r.z = __fadd_rn(0.5f * r0.z, 0.5f * r1.z);
+        r.w = 0.f;
+        float4* so = (float4*)S + (size_t)cy * Ws + cx;
+        so[0] = r;
+        so[(size_t)Hs * Ws] = make_float4(f[0], f[1], f[2], f[3]);
+    }
+}
+
 template <typename SRC>
-__global__ __launch_bounds__(256) void encode47_fused_kernel(const SRC* __restrict__ src, float* __restrict__ P, const float* __restrict__ w0,
-                                                             const float* __restrict__ b0, const float* __restrict__ w1, const float* __restrict__ b1,
-                                                             int H, int W, int C, int Hp, int Wp, int tiles_x) {
+__global__ __launch_bounds__(256) void encode47_fused_kernel(const SRC* __restrict__ src, float* __restrict__ P, float* __restrict__ S,
+                                                             const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
+                                                             const float* __restrict__ b1, int H, int W, int C, int Hp, int Wp, int tiles_x) {
     constexpr int CM = 16, CF = 4;
     __shared__ __attribute__((aligned(16))) float4 sI[ENC_TI * ENC_TI];
     __shared__ __attribute__((aligned(16))) float sE[ENC_TE * ENC_TE * CM];
@@ -346,17 +382,19 @@ __global__ __launch_bounds__(256) void encode47_fused_kernel(const SRC* __restri
             const int Y = 2 * y + (g >> 1), X = 2 * x + (g & 1);
             *(float4*)(P + (size_t)Hp * Wp * 4 + ((size_t)Y * Wp + X) * 4) = make_float4(acc[g][0], acc[g][1], acc[g][2], acc[g][3]);
         }
+        if (S) enc_stage0_cells(sI, acc, S, Y0, X0, Hp, Wp, tid);
     }
 }
 
-int encode47_fused_launch(const float* f32, const unsigned char* u8, float* P, const float* w0, const float* b0, const float* w1, const float* b1,
-                          int H, int W, int C, int Hp, int Wp, hipStream_t s) {
+int encode47_fused_launch(const float* f32, const unsigned char* u8, float* P, float* S, const float* w0, const float* b0, const float* w1,
+                          const float* b1, int H, int W, int C, int Hp, int Wp, hipStream_t s) {
+    VFI_REQUIRE(!S || (Hp % ENC_T == 0 && Wp % ENC_T == 0), "encode47: staging image needs whole tiles (%dx%d)", Hp, Wp);
     const int tiles_x = cdiv(Wp, ENC_T), tiles_y = cdiv(Hp, ENC_T);
     TraceScope ts("encode_fused", s);
     if (u8)
-        hipLaunchKernelGGL(encode47_fused_kernel<unsigned char>, dim3(tiles_x * tiles_y), dim3(256), 0, s, u8, P, w0, b0, w1, b1, H, W, C, Hp, Wp, tiles_x);
+        hipLaunchKernelGGL(encode47_fused_kernel<unsigned char>, dim3(tiles_x * tiles_y), dim3(256), 0, s, u8, P, S, w0, b0, w1, b1, H, W, C, Hp, Wp, tiles_x);
     else
-        hipLaunchKernelGGL(encode47_fused_kernel<float>, dim3(tiles_x * tiles_y), dim3(256), 0, s, f32, P, w0, b0, w1, b1, H, W, C, Hp, Wp, tiles_x);
+        hipLaunchKernelGGL(encode47_fused_kernel<float>, dim3(tiles_x * tiles_y), dim3(256), 0, s, f32, P, S, w0, b0, w1, b1, H, W, C, Hp, Wp, tiles_x);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -376,6 +414,7 @@ constexpr int ENC_MAXF = 64;                   // frames per launch (kernel-argu
 struct EncodeBatch {
     const void* src[ENC_MAXF];
     float* P[ENC_MAXF];
+    float* S[ENC_MAXF];      // block-0 staging image of the frame (enc_stage0_cells), nullptr = none
 };
 constexpr int ENC_NPRE = (ENC_TI * ENC_TI + 255) / 256;      // source pixels per thread and tile (6)
 
@@ -427,6 +466,7 @@ __global__ __launch_bounds__(256) void encode47_batch_kernel(const EncodeBatch f
         int f, Y0, X0;
         decode(item, f, Y0, X0);
         float* const P = fb.P[f];
+        float* const S = fb.S[f];
         const int iy0 = Y0 - 3, ix0 = X0 - 3;
         // ---- phase 0: registers -> LDS (clamped / scaled), plane 0 of the tile -> HBM
 #pragma unroll
@@ -526,6 +566,7 @@ __global__ __launch_bounds__(256) void encode47_batch_kernel(const EncodeBatch f
                     const int Y = 2 * y + (g >> 1), X = 2 * x + (g & 1);
                     *(float4*)(P + (size_t)Hp * Wp * 4 + ((size_t)Y * Wp + X) * 4) = make_float4(acc[g][0], acc[g][1], acc[g][2], acc[g][3]);
                 }
+                if (S) enc_stage0_cells(sI, acc, S, Y0, X0, Hp, Wp, tid);      // (with S the tiles are whole: every thread of the wave is here)
             }
         }
         enc_lds_barrier();      // sE (and sI) are rewritten by the next item
@@ -533,8 +574,9 @@ __global__ __launch_bounds__(256) void encode47_batch_kernel(const EncodeBatch f
 }
 
 // n frames (<= ENC_MAXF per launch; longer lists go out in several launches): srcs[i] -> packs[i]
-int encode47_batch_launch(int n, const void* const* srcs, bool u8, float* const* packs, const float* w0, const float* b0, const float* w1,
-                          const float* b1, int H, int W, int C, int Hp, int Wp, hipStream_t s) {
+int encode47_batch_launch(int n, const void* const* srcs, bool u8, float* const* packs, float* const* stages, const float* w0, const float* b0,
+                          const float* w1, const float* b1, int H, int W, int C, int Hp, int Wp, hipStream_t s) {
+    VFI_REQUIRE(!stages || (Hp % ENC_T == 0 && Wp % ENC_T == 0), "encode47: staging images need whole tiles (%dx%d)", Hp, Wp);
     const int tiles_x = cdiv(Wp, ENC_T), tiles_y = cdiv(Hp, ENC_T);
     int dev = 0;
     VFI_CHECK_HIP(hipGetDevice(&dev));
@@ -548,7 +590,7 @@ int encode47_batch_launch(int n, const void* const* srcs, bool u8, float* const*
     for (int base = 0; base < n; base += ENC_MAXF) {
         const int m = n - base < ENC_MAXF ? n - base : ENC_MAXF;
         EncodeBatch fb = {};
-        for (int i = 0; i < m; ++i) fb.src[i] = srcs[base + i], fb.P[i] = packs[base + i];
+        for (int i = 0; i < m; ++i) fb.src[i] = srcs[base + i], fb.P[i] = packs[base + i], fb.S[i] = stages ? stages[base + i] : nullptr;
         const int per = tiles_x * tiles_y, items = per * m;
         const int grid = items < 3 * launch_cus(cus) ? items : 3 * launch_cus(cus);      // 42.6 KB of LDS: three workgroups per CU
         TraceScope ts("encode_batch", s);
@@ -719,6 +761,35 @@ int stage_in_launch(const float* Ppool, size_t pack_stride, const RifeTasks& tas
     }
 #undef VFI_SI2
 #undef VFI_SI
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// Block 0's X from the per-frame staging images (enc_stage0_cells): the two frames' cell means side by side in the channel order of
+// cat_inputs<1>, the timestep through the same two averaging steps as every other channel, channel 15 zero.  Same values as
+// stage_in_kernel<false, 2, 1, 0> at s = 8, bit for bit; 64 B in and 64 B out per cell, coalesced.
+__global__ __launch_bounds__(256) void stage_in0_staged_kernel(const float* __restrict__ Spool, size_t stage_stride, RifeTasks tasks,
+                                                               float* __restrict__ Xo, int cells) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= cells) return;
+    const int b = blockIdx.y;
+    const float4* S0 = (const float4*)(Spool + (size_t)tasks.slot0[b] * stage_stride);
+    const float4* S1 = (const float4*)(Spool + (size_t)tasks.slot1[b] * stage_stride);
+    const float4 a = S0[idx], fa = S0[cells + idx], c = S1[idx], fc = S1[cells + idx];
+    const float t = tasks.t[b];
+    const float trow = __fadd_rn(0.5f * t, 0.5f * t);
+    const float tr = __fadd_rn(0.5f * trow, 0.5f * trow);
+    float4* op = (float4*)Xo + (size_t)b * 4 * cells + idx;
+    op[0] = make_float4(a.x, a.y, a.z, c.x);
+    op[(size_t)cells] = make_float4(c.y, c.z, fa.x, fa.y);
+    op[(size_t)2 * cells] = make_float4(fa.z, fa.w, fc.x, fc.y);
+    op[(size_t)3 * cells] = make_float4(fc.z, fc.w, tr, 0.f);
+}
+
+int stage_in0_staged_launch(const float* Spool, size_t stage_stride, const RifeTasks& tasks, int B, float* X, int Hp, int Wp, hipStream_t st) {
+    const int cells = (Hp / 8) * (Wp / 8);
+    TraceScope ts("stage_in0", st);
+    hipLaunchKernelGGL(stage_in0_staged_kernel, dim3(cdiv(cells, 256), B), dim3(256), 0, st, Spool, stage_stride, tasks, X, cells);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1147,9 +1218,10 @@ int stage_trans_launch(const float* Ppool, size_t pack_stride, const RifeTasks& 
 constexpr int F0_TWO = 16, F0_THO = 8;                    // output tile (pixels of the stride-2 convolution)
 constexpr int F0_TWI = 2 * F0_TWO + 1, F0_THI = 2 * F0_THO + 1;   // 33 x 17 input patch incl. the 1-pixel halo (top / left)
 constexpr int F0_NPIX = F0_TWI * F0_THI;                  // 561
-// LDS pixel stride = the 20 real channels (S/4 odd: conflict-free b128 reads).  The third 8-channel K chunk reads channels
-// 16..23 of a pixel, i.e. 4 floats of the NEXT pixel for lanes 32-63: finite values that meet the zero weights of the padded
-// input channels 20..23 (the last pixel's over-read lands in the weight image that follows the patch in LDS).
+// LDS pixel stride = the 20 real channels (S/4 odd: conflict-free b128 reads).  The third 8-channel K group holds 4 live
+// channels (16..19): the LIVE form multiplies them as two K-steps, lane half h supplying channels 16 + h and 18 + h.  (The FULL
+// form, kept as the bit-identity reference behind option fuse0a = 2, multiplies the group as four steps (16|20) .. (19|23):
+// its lanes 32-63 read 4 floats of the NEXT pixel, finite values that meet the zero weights of the padded channels.)
 constexpr int F0_S = 20;
 constexpr int F0_XF = F0_NPIX * F0_S;                     // floats of the patch
 constexpr int F0_WF = 27 * 32 * 8;                        // floats of the layer's packed weights [tap][Cin/8][32][8]
@@ -1159,6 +1231,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // 8 waves: phase A has one patch pixel per thread (+ the 49 halo pixels on a second, overlapped round); in phase B wave w
 // multiplies sub-tile (w & 3) over one half of the 27 K-steps (w >> 2), the halves are added through LDS.
+template <bool LIVE>
 __global__ __launch_bounds__(F0_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void trans1_conv0a_kernel(const float* __restrict__ Ppool, size_t pack_stride, RifeTasks tasks,
                                                                    const float* __restrict__ T, const float* __restrict__ Fin,
                                                                    float* __restrict__ Fout, const float* __restrict__ wpk,
@@ -1243,6 +1316,10 @@ __global__ __launch_bounds__(F0_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             asm volatile("" : "+v"(ab), "+v"(bb));
             const char* const ap = (const char*)lds + ab;
             const char* const bp = (const char*)wl + bb;
+            // the live tail of a tap (channels 16..19): lane half h reads floats [16 + h] and [18 + h] of the pixel and of the
+            // weight row — the same bases with the half's 4-float step taken back to 1
+            const char* const ap1 = ap - half * 12;
+            const char* const bp1 = bp - half * 12;
             auto steps = [&](auto KH) {
                 constexpr int kh = decltype(KH)::value;
 #pragma unroll
@@ -1251,10 +1328,17 @@ __global__ __launch_bounds__(F0_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
                     if (st < 27) {
                         const int t = st / 3, c8 = st - 3 * t;
                         const int toff = ((t / 3) * F0_TWI + (t % 3)) * F0_S;
-                        const f32x4_t av = *(const f32x4_t*)(ap + (toff + c8 * 8) * 4);
-                        const f32x4_t bv = *(const f32x4_t*)(bp + st * 1024);
+                        if (LIVE && c8 == 2) {   // K order 16, 17, 18, 19 as in the FULL form, whose other four terms are x * 0
+                            const float a0 = *(const float*)(ap1 + (toff + 16) * 4), a1 = *(const float*)(ap1 + (toff + 18) * 4);
+                            const float b0 = *(const float*)(bp1 + st * 1024), b1 = *(const float*)(bp1 + st * 1024 + 8);
+                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
+                        } else {
+                            const f32x4_t av = *(const f32x4_t*)(ap + (toff + c8 * 8) * 4);
+                            const f32x4_t bv = *(const f32x4_t*)(bp + st * 1024);
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
+                            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
+                        }
                     }
                     if (k & 1) __builtin_amdgcn_sched_barrier(0);    // at most two steps' fragments in flight
                 }
@@ -1301,15 +1385,22 @@ int trans1_conv0a_launch(const float* Ppool, size_t pack_stride, const RifeTasks
         cus_of[dev].store(cus, std::memory_order_relaxed);
     }
     // 72.5 KB of LDS (patch 44.9 + weights 27.6) and 512 threads: two workgroups per CU, each walks its share of the tiles
-    static bool attr_set[kMaxDevices] = {};
-    if (!attr_set[dev]) {
-        VFI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trans1_conv0a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (F0_XF + F0_WF) * 4));
-        attr_set[dev] = true;
+    // option fuse0a = 2: the FULL form (24 input channels multiplied, 108 MFMAs per sub-tile), the reference of the LIVE one (90)
+    const bool live = option(kOptFuse0a) != 2;
+    const void* const fn = live ? reinterpret_cast<const void*>(&trans1_conv0a_kernel<true>) : reinterpret_cast<const void*>(&trans1_conv0a_kernel<false>);
+    static bool attr_set[2][kMaxDevices] = {};
+    if (!attr_set[live][dev]) {
+        VFI_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (F0_XF + F0_WF) * 4));
+        attr_set[live][dev] = true;
     }
     const int grid = std::min(n_tiles, 2 * launch_cus(cus));
     TraceScope ts("trans1_conv0a", st);
-    hipLaunchKernelGGL(trans1_conv0a_kernel, dim3(grid), dim3(F0_THREADS), (F0_XF + F0_WF) * 4, st, Ppool, pack_stride, tasks, T, Fin, Fout, wpk, bias, A0, Hp, Wp,
-                       n_tiles, tiles_x, tiles_y, slope);
+    if (live)
+        hipLaunchKernelGGL(trans1_conv0a_kernel<true>, dim3(grid), dim3(F0_THREADS), (F0_XF + F0_WF) * 4, st, Ppool, pack_stride, tasks, T, Fin, Fout, wpk, bias, A0,
+                           Hp, Wp, n_tiles, tiles_x, tiles_y, slope);
+    else
+        hipLaunchKernelGGL(trans1_conv0a_kernel<false>, dim3(grid), dim3(F0_THREADS), (F0_XF + F0_WF) * 4, st, Ppool, pack_stride, tasks, T, Fin, Fout, wpk, bias, A0,
+                           Hp, Wp, n_tiles, tiles_x, tiles_y, slope);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -60,7 +60,7 @@ int wino_probe_read(unsigned* out32);                                         //
 enum Option {
     kOptStageQuad,       // bit mask of the next-block scales (2, 4, 8) whose transition takes the quad kernel (default 14 = all)
     kOptFuseEncode,      // 1: RIFE 4.7 frame pack in one launch (default), 0: prep + encode.0 + encode.1 as three kernels
-    kOptFuse0a,          // 1: block 2->3 transition fused with block 3's conv0.0 (default), 0: separate
+    kOptFuse0a,          // 1: block 2->3 transition fused with block 3's conv0.0 (default), 0: separate, 2: fused, all 24 padded input channels multiplied
     kOptM2n2Px,          // pixel count from which wide direct-conv layers take the m2n2 tile (default -1 = never)
     kOptGroupedVariant,  // forced tile variant of the grouped (transposed) convolution (default -1 = heuristic)
     kOptSplitK,          // 1: split-K allowed for layer objects (default), 0: never
@@ -77,6 +77,7 @@ enum Option {
     kOptWinoProbe,       // 1..4: the hot Winograd instantiation takes its cycle-ledger form (conv_wino.hip: g_wino_probe_out; default 0)
     kOptSepconvSplitHeads,  // 1: SepConv++'s four head first-convs as four 64 -> 64 layers, each reading up2(row1) (default 0: one 64 -> 256 layer)
     kOptSepconvPlanar,      // 1: SepConv++'s heads transposed to planar before the output stage (default), 0: the output stage reads them NHWC
+    kOptStage0,             // 1: RIFE block 0's input assembled from the per-frame staging images the frame pack kernels write (default), 0: gathered from the packs per pair
     kOptCount
 };
 long option(Option o);
@@ -148,6 +149,8 @@ struct ConvArgs {
     int par_cout;                  //   its parity; par_cout = channels per parity group (4 groups: Cout_p == 4 * par_cout), output [2 Hout, 2 Wout] interleaved
     int ksplit;            // set by the launcher: > 1 = split-K launch, blockIdx.z owns a K range and the slice
     long split_stride;     //   out + blockIdx.z * split_stride (floats) of the partial-sum workspace
+    int cin_live;          // the layer's real input channels where the caller knows them (0 = not given: all Cin_p are multiplied); last, so
+                           //   that the kernels' argument offsets of the fields above are what they were
 };
 
 struct ConvVariant {

@@ -1,6 +1,8 @@
 """GPU tool: the RIFE 4.7 step of bench.py (1080p, 32 pairs) with direct-conv tile variants forced by trace name
 (include/vfi_hip_test.h: vfi_test_variant_override) — per-kernel HIP-event milliseconds for each override set.
-    python tools/rife_variant_ab.py "conv0b_b3=40" "conv0b_b3=40,conv0b_b2=40" ..."""
+    python tools/rife_variant_ab.py "conv0b_b3=40" "conv0b_b3=40,conv0b_b2=40" ...
+A spec "opt:NAME=VALUE" sets a library A/B option instead (it stays set for the specs after it), e.g. the forms the live-K kernels
+replace: "conv0a_b1=39,conv0a_b2=39" (plain stride-2 tile), "opt:fuse0a=2" (trans1_conv0a with all 24 input channels multiplied)."""
 import os
 import sys
 
@@ -25,7 +27,7 @@ g = torch.Generator(device="cpu").manual_seed(0)
 raw = torch.rand((B + 1, H, W, 3), generator=g).cuda()
 out = torch.empty((B, H, W, 3), device="cuda")
 slot0, slot1, ts = list(range(B)), list(range(1, B + 1)), [0.5] * B
-names = ("conv0a_b0", "conv0b_b0", "conv0a_b1", "conv0b_b1", "conv0a_b2", "conv0b_b2", "conv0b_b3", "trans1_conv0a", "encode_batch", "stage_trans4", "stage_trans2", "final_blend")
+names = ("conv0a_b0", "conv0b_b0", "conv0a_b1", "conv0b_b1", "conv0a_b2", "conv0b_b2", "conv0b_b3", "trans1_conv0a", "encode_batch", "stage_in0", "stage_trans4", "stage_trans2", "final_blend")
 
 
 def step():
