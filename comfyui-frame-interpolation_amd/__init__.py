@@ -76,6 +76,7 @@ def _node_class_mappings():
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
 # list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
 # FLAVR's and AMT's keys are the reference's class names lower-cased, "flavr_vfi" / "amt_vfi"; a bare "flavr" or "amt" is not a key.
+# AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled).
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
                "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)")}
 

@@ -3,8 +3,10 @@ vfi_models/amt/__init__.py:61-66).
 
 Key names / shapes follow ``AMT_S`` (vfi_models/amt/amt_arch.py:1153-1188) and ``AMT_L`` (:1297-1332); order = torch state_dict order.
 ``InstanceNorm2d`` has no parameters and no buffers (affine=False, no running statistics), so the feature encoder contributes
-convolutions only.  AMT-G (``amt-g.pth``: 84/96/112/128 pyramid channels, ``update*_high`` blocks with their own lookups) has another
-forward and is not served: it is told apart by name and refused."""
+convolutions only.  AMT-G (``amt-g.pth``, ``AMT_G`` :1441-1590: 84/96/112/128 pyramid channels, ``LargeEncoder``, five update blocks — the
+``update*_high`` blocks re-read the ``_low`` blocks' lookup output, resized) is AMT-L's forward with other tables plus those two blocks.  It
+is told apart by name and served only when config.yaml's ``amt_g`` key is on (``amt_g_enabled()``): its real checkpoint has not been run
+here.  With the key off it is refused as before."""
 from collections import OrderedDict
 
 VARIANTS = ("S", "L")
@@ -15,7 +17,13 @@ CONFIG = {
               hidden=76, flow_dim=20, corr_dim=64, corr_dim2=None, fc_dim=68),
     "L": dict(channels=(48, 64, 72, 128), skip=48, num_flows=5, feat_dim=128, comb_k=7, stem_k=7,
               hidden=128, flow_dim=48, corr_dim=256, corr_dim2=160, fc_dim=124),
+    "G": dict(channels=(84, 96, 112, 128), skip=84, num_flows=5, feat_dim=128, comb_k=7, stem_k=7,
+              hidden=192, flow_dim=64, corr_dim=256, corr_dim2=192, fc_dim=188),
 }
+# the update blocks in registration order (torch state-dict order) -> the pyramid level whose channel count is their cdim
+UPDATE_BLOCKS = {"S": (("update4", 2), ("update3", 1), ("update2", 0)), "L": (("update4", 2), ("update3", 1), ("update2", 0)),
+                 "G": (("update4", 2), ("update3_low", 1), ("update2_low", 0), ("update3_high", 1), ("update2_high", 0))}
+G_BLOCK_PREFIXES = ("update3_high.", "update2_high.", "update3_low.", "update2_low.")
 CORR_LEVELS, CORR_RADIUS = 4, 3
 COR_PLANES = CORR_LEVELS * (2 * CORR_RADIUS + 1) ** 2       # 196 per direction
 
@@ -31,7 +39,7 @@ def amt_shapes(variant):
         conv(name + ".0", cout, cin, k)
         d[name + ".1.weight"] = (cout,)
 
-    # feature encoder (SmallEncoder :515-587 / BasicEncoder :589-663)
+    # feature encoder (SmallEncoder :515-587 / BasicEncoder :589-663 / LargeEncoder :665-741)
     if variant == "S":
         conv("feat_encoder.conv1", 32, 3, 7)
         cin = 32
@@ -48,15 +56,18 @@ def amt_shapes(variant):
     else:
         conv("feat_encoder.conv1", 64, 3, 7)
         cin = 64
-        for i, c in enumerate((64, 72, 128)):
+        # G: a fourth, stride-1 stage layer3_2 (no downsample)
+        stages = (("layer1", 64, 1), ("layer2", 72, 2), ("layer3", 128, 2)) if variant == "L" else (
+            ("layer1", 64, 1), ("layer2", 112, 2), ("layer3", 160, 2), ("layer3_2", 160, 1))
+        for lname, c, stride in stages:
             for b in range(2):
-                p = f"feat_encoder.layer{i + 1}.{b}."
+                p = f"feat_encoder.{lname}.{b}."
                 conv(p + "conv1", c, cin if b == 0 else c, 3)
                 conv(p + "conv2", c, c, 3)
-                if b == 0 and i > 0:
+                if b == 0 and stride == 2:
                     conv(p + "downsample.0", c, cin, 1)
             cin = c
-        conv("feat_encoder.conv2", cfg["feat_dim"], 128, 1)
+        conv("feat_encoder.conv2", cfg["feat_dim"], cin, 1)
     # pyramid encoder (:801-822)
     prev = 3
     for i, c in enumerate(cfg["channels"], 1):
@@ -76,7 +87,8 @@ def amt_shapes(variant):
         d[p + "2.weight"], d[p + "2.bias"] = (c, cout, 4, 4), (cout,)
     # update blocks (SmallUpdateBlock :969-1019 / BasicUpdateBlock :1022-1073)
     hid, fd, cd, cd2, fc = cfg["hidden"], cfg["flow_dim"], cfg["corr_dim"], cfg["corr_dim2"], cfg["fc_dim"]
-    for name, cdim in (("update4", ch[2]), ("update3", ch[1]), ("update2", ch[0])):
+    for name, lvl in UPDATE_BLOCKS[variant]:
+        cdim = ch[lvl]
         conv(name + ".convc1", cd, 2 * COR_PLANES, 1)
         if cd2:
             conv(name + ".convc2", cd2, cd, 3)
@@ -95,10 +107,21 @@ def amt_shapes(variant):
     return d
 
 
+def amt_g_enabled():
+    """config.yaml's ``amt_g`` key (absent = off), read at call time"""
+    from . import ckpt
+
+    return bool(ckpt.load_config().get("amt_g", False))
+
+
 def variant_of(sd):
-    """"S" or "L" by name and shape; AMT-G raises NotImplementedError, anything else RuntimeError."""
-    if any(k.startswith(("update3_high.", "update2_high.", "update3_low.", "update2_low.")) for k in sd):
-        raise NotImplementedError("this state dict is AMT-G's (update*_high / update*_low blocks): only AMT-S and AMT-L are served")
+    """"S" or "L" by name and shape, "G" by name when ``amt_g`` is on; AMT-G raises NotImplementedError otherwise, anything else
+    RuntimeError."""
+    if any(k.startswith(G_BLOCK_PREFIXES) for k in sd):
+        if amt_g_enabled():
+            return "G"
+        raise NotImplementedError("this state dict is AMT-G's (update*_high / update*_low blocks): only AMT-S and AMT-L are served "
+                                  "(AMT-G is opt-in: config.yaml's amt_g key)")
     w = sd.get("encoder.pyramid1.0.0.weight")
     if w is None or "comb_block.0.weight" not in sd or "feat_encoder.conv2.weight" not in sd:
         raise RuntimeError("not an AMT state dict: no 'encoder.pyramid1.0.0.weight' / 'comb_block.0.weight' / 'feat_encoder.conv2.weight'")
@@ -125,13 +148,16 @@ def check_state_dict(sd, variant=None):
 
 
 def variant_of_ckpt(ckpt_name):
-    """The variant a checkpoint name stands for; amt-g.pth raises NotImplementedError naming it, before anything is loaded."""
+    """The variant a checkpoint name stands for; amt-g.pth is "G" when config.yaml's ``amt_g`` key is on and raises NotImplementedError
+    naming it otherwise, before anything is loaded."""
     if ckpt_name not in CKPT_VARIANT:
         raise KeyError(f"unknown AMT checkpoint {ckpt_name!r} (known: {list(CKPT_VARIANT)})")
     v = CKPT_VARIANT[ckpt_name]
     if v is None:
+        if amt_g_enabled():
+            return "G"
         raise NotImplementedError(f"{ckpt_name}: AMT-G has a forward of its own (update*_high blocks) and is not served; use amt-s.pth, "
-                                  "gopro_amt-s.pth or amt-l.pth")
+                                  "gopro_amt-s.pth or amt-l.pth (AMT-G is opt-in: config.yaml's amt_g key)")
     return v
 
 

@@ -1,10 +1,11 @@
-// AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L): the kernels the network needs beyond the shared layer objects, and the network object
+// AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L / AMT_G): the kernels the network needs beyond the shared layer objects, and the network object
 // (vfi_amt_create / _forward / ..., at the end of the file) that runs one frame pair at n timesteps over them.
 //
 //   amt_pool2 / amt_lookup   the bidirectional correlation lookup WITHOUT the all-pairs volume (BidirCorrBlock, :1076-1141)
 //   conv7x7                  7x7 stride-1 zero-padded convolution for thin layers (convf1, AMT-L's comb_block)
 //   amt_warps / amt_out      multi_flow_combine around comb_block (:869-902), clamp and un-pad
 //   amt_pad / amt_mean_* / amt_center   InputPadder's centred replicate pad, mean_ over the padded pair (deterministic), its subtraction
+//   amt_upsample_lrelu       leaky_relu(bilinear x2 / x4 up-sampling) in one pass: AMT-G's update*_high blocks after their commuted convc1
 //   amt_add / amt_warp       residual sums, channel-window and stride-2 copies; amt_arch.warp of a feature window (rife_warp.h's taps)
 //
 // Built with -ffp-contract=off (csrc/build.py): coordinates are coord + flow * scale as two roundings, as torch computes them; the dot
@@ -12,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/vfi_hip.h"
+#include "bilinear_src.h"
 #include "net_object.h"
 #include "rife_warp.h"
 #include "vfi_common.h"
@@ -302,6 +304,39 @@ __global__ void amt_warp_kernel(const float* __restrict__ in, int in_cs, const f
     for (int ch = 0; ch < C; ++ch) o[ch] = a[ch] * t.nw + b[ch] * t.ne + c[ch] * t.sw + d[ch] * t.se;
 }
 
+// out[n, Y, X, 0..C) = leaky_relu(F.interpolate(in, scale_factor=s, mode="bilinear", align_corners=False), slope): one thread per output
+// pixel and group of V channels (V = 4: float4 loads and stores; V = 1 where a stride or a window offset is not 16-byte aligned), the
+// channel groups of a pixel on neighbouring lanes, so the four taps are read and the result is written as contiguous runs.  Taps and blend
+// are torch's (and resize_ratio_kernel's): bil_src with ratio 1 / s, rows blended first.  Each output element is written once.
+template <int V>
+__global__ void amt_upsample_lrelu_kernel(const float* __restrict__ in, int in_cs, float* __restrict__ out, int out_cs, int N, int h, int w,
+                                          int C, int s, float ratio, float slope) {
+    const int CV = C / V, Ho = h * s, Wo = w * s;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)N * Ho * Wo * CV) return;
+    const int cg = (int)(idx % CV);
+    const long p = idx / CV;
+    const int X = (int)(p % Wo), Y = (int)((p / Wo) % Ho), n = (int)(p / ((long)Wo * Ho));
+    const BilS by = bil_src(Y, ratio, h), bx = bil_src(X, ratio, w);
+    const float* b = in + (size_t)n * h * w * in_cs + (size_t)cg * V;
+    const float *p00 = b + ((size_t)by.i0 * w + bx.i0) * in_cs, *p01 = b + ((size_t)by.i0 * w + bx.i1) * in_cs;
+    const float *p10 = b + ((size_t)by.i1 * w + bx.i0) * in_cs, *p11 = b + ((size_t)by.i1 * w + bx.i1) * in_cs;
+    float* o = out + (size_t)p * out_cs + (size_t)cg * V;
+    alignas(16) float a[V], bb[V], c[V], d[V], r[V];
+    if (V == 4) {
+        *(float4*)a = *(const float4*)p00, *(float4*)bb = *(const float4*)p01, *(float4*)c = *(const float4*)p10, *(float4*)d = *(const float4*)p11;
+    } else {
+        a[0] = p00[0], bb[0] = p01[0], c[0] = p10[0], d[0] = p11[0];
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const float v = by.w0 * (bx.w0 * a[k] + bx.w1 * bb[k]) + by.w1 * (bx.w0 * c[k] + bx.w1 * d[k]);      // no contraction: five roundings
+        r[k] = v > 0.f ? v : v * slope;
+    }
+    if (V == 4) *(float4*)o = *(const float4*)r;
+    else o[0] = r[0];
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
@@ -349,9 +384,13 @@ int vfi_amt_corr_lookup(const float* fq_dev, const float* ft_dev, const float* f
 
 int vfi_conv7x7(const float* in_dev, int in_cs, const float* w_dev, const float* bias_dev, const float* prelu_dev, float slope, int act,
                 int Cin, int Cout, float* out_dev, int out_cs, int N, int H, int W, void* stream) {
-    VFI_REQUIRE(in_dev && w_dev && out_dev && N > 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 96 && Cout > 0 && Cout <= 96 && in_cs >= Cin &&
+    // Cout: a workgroup owns 16 output channels whatever Cout is (blockIdx.z walks the groups), so registers and LDS do not depend on it; a
+    // wider layer re-stages the input patch once per group of 16, which is what bounds the layers this direct form is meant for.  96 was
+    // the widest layer served (AMT-L's convf1); AMT-G's convf1 is 4 -> 128: eight groups over one staged float4 per pixel.
+    VFI_REQUIRE(in_dev && w_dev && out_dev && N > 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 96 && Cout > 0 && Cout <= 128 && in_cs >= Cin &&
                     out_cs >= Cout,
-                "vfi_conv7x7: bad arguments (Cin %d and Cout %d at most 96, strides %d / %d at least the channel counts)", Cin, Cout, in_cs, out_cs);
+                "vfi_conv7x7: bad arguments (Cin %d at most 96, Cout %d at most 128, strides %d / %d at least the channel counts)", Cin, Cout,
+                in_cs, out_cs);
     VFI_REQUIRE(act == 0 || act == 1 || (act == 3 && prelu_dev), "vfi_conv7x7: act %d (0 none, 1 leaky relu, 3 PReLU with slopes)", act);
     VFI_REQUIRE((long)N * H * W * in_cs < (1L << 31) * 4 && (long)N * H * W < (1L << 31) && aligned16(w_dev),
                 "vfi_conv7x7: %d x %dx%d pixels are beyond the kernel's index arithmetic, or the weights are not 16-byte aligned", N, H, W);
@@ -365,6 +404,25 @@ int vfi_conv7x7(const float* in_dev, int in_cs, const float* w_dev, const float*
     else
         hipLaunchKernelGGL(conv7x7_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, w_dev, bias_dev, prelu_dev, slope, act,
                            out_dev, out_cs, H, W, Cin, Cout, CoutP, zb);
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int vfi_amt_upsample_lrelu(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int h, int w, int C, int scale, float slope,
+                           void* stream) {
+    VFI_REQUIRE(in_dev && out_dev && N > 0 && h > 0 && w > 0 && C > 0 && in_cs >= C && out_cs >= C && (scale == 2 || scale == 4),
+                "vfi_amt_upsample_lrelu: bad arguments (scale %d must be 2 or 4, strides %d / %d at least C = %d)", scale, in_cs, out_cs, C);
+    const long total = (long)N * h * scale * w * scale * C;
+    VFI_REQUIRE((long)h * scale < (1L << 22) && (long)w * scale < (1L << 22) && total / 256 < (1L << 31) - 1,
+                "vfi_amt_upsample_lrelu: %d x %dx%d x %d channels at scale %d is beyond the kernel's index arithmetic", N, h, w, C, scale);
+    TraceScope ts("amt_upsample", (hipStream_t)stream);
+    const float ratio = 1.0f / (float)scale;
+    if (C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0 && aligned16(in_dev) && aligned16(out_dev))
+        hipLaunchKernelGGL(amt_upsample_lrelu_kernel<4>, dim3(nblk(total / 4, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, out_dev,
+                           out_cs, N, h, w, C, scale, ratio, slope);
+    else
+        hipLaunchKernelGGL(amt_upsample_lrelu_kernel<1>, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, out_dev, out_cs,
+                           N, h, w, C, scale, ratio, slope);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -398,15 +456,23 @@ int vfi_amt_combine_out(const float* warps_dev, int warps_cs, const float* comb_
 
 }  // extern "C"
 
-// ---- the network object: AMT-S / AMT-L on csrc/net_object.h ------------------------------------------------------------------------
+// ---- the network object: AMT-S / AMT-L / AMT-G on csrc/net_object.h ------------------------------------------------------------------------
 
 namespace {
 
+// enc / enc_stride: the feature encoder's stages of two blocks each (AMT-G's LargeEncoder has a fourth, stride-1 stage, layer3_2);
+// n_upd: update4, update3[_low], update2[_low], then AMT-G's update3_high, update2_high; px_floats: the widest activation in floats per
+// padded pixel, which bounds the frame size (vfi_amt_forward)
 struct Cfg {
-    int ch[4], skip, nf, D, comb_k, hid, fd, cd, cd2, fc, e1, enc[3];
+    int ch[4], skip, nf, D, comb_k, hid, fd, cd, cd2, fc, e1, n_enc, enc[4], enc_stride[4], n_upd, px_floats, n_tensors;
+    const char* name;
 };
-const Cfg kCfg[2] = {{{20, 32, 44, 56}, 20, 3, 84, 3, 76, 20, 64, 0, 68, 32, {32, 64, 96}},
-                     {{48, 64, 72, 128}, 48, 5, 128, 7, 128, 48, 256, 160, 124, 64, {64, 72, 128}}};
+// (amt.py's MAX_PADDED_PIXELS_G is derived from the same 88; tests/test_gpu_amt_g.py asserts that the two limits agree.)
+// AMT-G's widest buffer is decoder1's ResBlock at half resolution: r8(3 * 84) + 8 + r8(84) = 352 channels = 88 floats per padded pixel
+// (gru.0's input in update2_high, r8(188 + 4 + 84) = 280 channels, is 70).  AMT-S / AMT-L keep their 64.
+const Cfg kCfg[3] = {{{20, 32, 44, 56}, 20, 3, 84, 3, 76, 20, 64, 0, 68, 32, 3, {32, 64, 96}, {1, 2, 2}, 3, 64, 213, "S"},
+                     {{48, 64, 72, 128}, 48, 5, 128, 7, 128, 48, 256, 160, 124, 64, 3, {64, 72, 128}, {1, 2, 2}, 3, 64, 207, "L"},
+                     {{84, 96, 112, 128}, 84, 5, 128, 7, 192, 64, 256, 192, 188, 64, 4, {64, 112, 160, 160}, {1, 2, 2, 1}, 5, 88, 259, "G"}};
 
 inline int r8(int c) { return (c + 7) & ~7; }
 
@@ -414,8 +480,9 @@ struct Conv7 {      // a vfi_conv7x7 layer: packed weights, bias, PReLU slopes (
     float *w = nullptr, *b = nullptr, *pr = nullptr;
     int cin = 0, cout = 0;
 };
-struct Stem {       // a vfi_conv7x7s2_prelu layer with its output channels padded to 64
+struct Stem {       // a vfi_conv7x7s2_prelu layer: its output channels padded to 64, or AMT-G's 84 as they are
     float *w = nullptr, *b = nullptr, *slope = nullptr;
+    int cout = 64;
 };
 struct EncBlk {
     vfi_conv_t *c1 = nullptr, *c2 = nullptr, *c3 = nullptr, *ds = nullptr;
@@ -434,13 +501,13 @@ struct Upd {
 }  // namespace
 
 struct vfi_amt : NetObject {
-    int variant = 0;      // 0 AMT-S, 1 AMT-L
+    int variant = 0;      // 0 AMT-S, 1 AMT-L, 2 AMT-G
     Stem fe_stem, py_stem;
-    EncBlk blk[6];
+    EncBlk blk[8];
     vfi_conv_t* fe_out = nullptr;
     vfi_conv_t *py0[4] = {}, *py1[4] = {};
     Dec dec[4];           // decoder4, 3, 2, 1
-    Upd upd[3];           // update4, 3, 2
+    Upd upd[5];           // update4, 3[_low], 2[_low]; AMT-G: update3_high, update2_high
     vfi_conv_t *cb0 = nullptr, *cb2 = nullptr;
     Conv7 cb7[2];
     int Hp = 0, Wp = 0;
@@ -481,8 +548,9 @@ struct Run {      // one forward call: the scratch tensors by name and the launc
     // InstanceNorm2d over N = 2 frames: out = relu2(relu1(norm(x)) + add).  out may be x: the apply kernel reads and writes one element per
     // thread at the same position and declares neither pointer __restrict__ (gmfss_bodies.h: instnorm_apply_body)
     int norm(const float* x, int cs, int C, long HW, int relu1, const float* add_, int add_cs, int relu2, float* out, int ocs) {
-        float* stats = buf("stats", 1, 1, 1, 2 * 128 * 2);
-        float* nws = buf("norm_ws", 1, 1, 1, 2 * 64 * 128 * 2 * 2);
+        const int cmax = m->variant == 2 ? 160 : 128;      // the widest normalised layer
+        float* stats = buf("stats", 1, 1, 1, 2 * cmax * 2);
+        float* nws = buf("norm_ws", 1, 1, 1, 2 * 64 * cmax * 2 * 2);
         if (bad) return -1;
         if (vfi_instnorm_stats(x, cs, C, 2, HW, stats, (double*)nws, (int64_t)64 * 2 * C * 2 * sizeof(double), st)) return -1;
         return vfi_instnorm_apply(x, cs, stats, C, 2, HW, relu1, add_, add_cs, relu2, out, ocs, st);
@@ -510,9 +578,27 @@ int run_decoder(Run& r, const Dec& d, int skip, const float* din, int din_cs, in
     return r.conv(d.up, r5, c8, h, w, out, out_cs, 1, 0);
 }
 
+// an update block from convf1 on (:1060-1068), at the h x w of its buffers: convf1 / convf2 of the flow window, `conv` over (cor | flo) into the
+// front of inp (whose flow and net windows the caller has filled), gru, feat_head -> dn, flow_head -> df
+int update_tail(Run& r, const Cfg& g, const Upd& U, const float* flow, int flow_cs, int ch, int h, int w, float* inp, int inp_cs, float* cf, int cf_cs,
+                float* fa, float* h1, float* h2, float* h3, float* dn, float* df) {
+    const int hcs = r8(g.hid), cdo = g.cd2 ? g.cd2 : g.cd;
+    AMT_DO(vfi_conv7x7(flow, flow_cs, U.f1.w, U.f1.b, nullptr, 0.1f, 1, 4, 2 * g.fd, fa, 2 * g.fd, 1, h, w, r.st));
+    AMT_DO(r.conv(U.f2, fa, 2 * g.fd, h, w, cf + cdo, cf_cs, 1, 1));
+    // (writes channels 0 .. fc of inp, directly in front of the flow window: the layer objects store exactly Cout channels, never Cout
+    // rounded up, see the `co < a.Cout` guards of conv_mfma*.hip / conv_wino.hip)
+    AMT_DO(r.conv(U.cv, cf, cf_cs, h, w, inp, inp_cs, 1, 1));
+    AMT_DO(r.conv(U.g0, inp, inp_cs, h, w, h1, hcs, 1, 1));
+    AMT_DO(r.conv(U.g2, h1, hcs, h, w, h2, hcs, 1, 0));
+    AMT_DO(r.conv(U.fh0, h2, hcs, h, w, h1, hcs, 1, 1));
+    AMT_DO(r.conv(U.fh2, h1, hcs, h, w, dn, r8(ch), 1, 0));
+    AMT_DO(r.conv(U.wh0, h2, hcs, h, w, h3, hcs, 1, 1));
+    return r.conv(U.wh2, h3, hcs, h, w, df, 8, 1, 0);
+}
+
 int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int W, const float* ts, int n_t, float* out, hipStream_t st) {
     const Cfg& g = kCfg[m->variant];
-    const bool L = m->variant == 1;
+    const bool basic = m->variant >= 1, G = m->variant == 2;      // basic: the BasicUpdateBlock family, AMT-L and AMT-G, which share a forward; G: the 84-channel stem and the high blocks
     const int Hp = m->Hp, Wp = m->Wp, top = (Hp - H) / 2, left = (Wp - W) / 2;
     const long P = (long)Hp * Wp;
     const int h8 = Hp / 8, w8 = Wp / 8, D = g.D;
@@ -527,7 +613,7 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
     hipLaunchKernelGGL(amt_mean_final_kernel, dim3(1), dim3(1), 0, st, (const double*)part, 2 * P, mean);
     hipLaunchKernelGGL(amt_center_kernel, dim3(nblk(2 * P, 256)), dim3(256), 0, st, img, 2 * P, (const float*)mean);
     VFI_CHECK_HIP(hipGetLastError());
-    // feature encoder (SmallEncoder / BasicEncoder, norm_fn = instance) over both frames
+    // feature encoder (SmallEncoder / BasicEncoder / LargeEncoder, norm_fn = instance) over both frames
     float* fmap = r.buf("fmap", 2, h8, w8, D);
     {
         int h = Hp / 2, w = Wp / 2;
@@ -537,11 +623,11 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
         AMT_DO(r.norm(e1, 64, g.e1, (long)h * w, 1, nullptr, 0, 0, e1, 64));
         const float* x = e1;
         int xcs = 64;
-        for (int k = 0; k < 6; ++k) {
+        for (int k = 0; k < 2 * g.n_enc; ++k) {
             const EncBlk& B = m->blk[k];
             const int ho = h / B.stride, wo = w / B.stride, c = B.c;
             float* y3 = r.buf("fe_y3", 2, ho, wo, c);
-            if (!L) {
+            if (!basic) {
                 const int c4 = c / 4;
                 float *y1 = r.buf("fe_y1", 2, h, w, c4), *y2 = r.buf("fe_y2", 2, ho, wo, c4);
                 if (r.bad) return -1;
@@ -589,11 +675,11 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
         const float* x = img;
         int xcs = 8, h = Hp, w = Wp;
         for (int i = 0; i < 4; ++i) {
-            pcs[i] = (L && i == 0) ? 64 : r8(g.ch[i]);
+            pcs[i] = (basic && !G && i == 0) ? 64 : r8(g.ch[i]);      // AMT-L's stem writes its 64 padded channels, AMT-G's its own 84
             float* a = r.buf("py_a", 2, h / 2, w / 2, pcs[i]);
             pyr[i] = r.buf("py_p", 2, h / 2, w / 2, pcs[i]);
             if (r.bad) return -1;
-            if (L && i == 0) AMT_DO(vfi_conv7x7s2_prelu(img, 8, m->py_stem.w, m->py_stem.b, m->py_stem.slope, 64, a, 64, 2, Hp, Wp, st));
+            if (basic && i == 0) AMT_DO(vfi_conv7x7s2_prelu(img, 8, m->py_stem.w, m->py_stem.b, m->py_stem.slope, m->py_stem.cout, a, pcs[0], 2, Hp, Wp, st));
             else AMT_DO(r.conv(m->py0[i], x, xcs, h, w, a, pcs[i], 2, 3));
             h /= 2, w /= 2;
             AMT_DO(r.conv(m->py1[i], a, pcs[i], h, w, pyr[i], pcs[i], 2, 3));
@@ -641,7 +727,7 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             if (down != 1) AMT_DO(r.resize(ft, fcs, h, w, inp + g.fc + 4, inp_cs, h8, w8, ch, (float)down, 1.0f));
             else AMT_DO(r.copy(ft, fcs, inp + g.fc + 4, inp_cs, h8, w8, ch));
             AMT_DO(r.copy(fd, fd_cs, inp + g.fc, inp_cs, h8, w8, 4));
-            if (L) {
+            if (basic) {
                 float* c1 = r.buf("upd_c1", 1, h8, w8, g.cd);
                 if (r.bad) return -1;
                 AMT_DO(r.conv(U.c1, corr, 392, h8, w8, c1, g.cd, 1, 1));
@@ -649,17 +735,7 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             } else {
                 AMT_DO(r.conv(U.c1, corr, 392, h8, w8, cf, cf_cs, 1, 1));
             }
-            AMT_DO(vfi_conv7x7(fd, fd_cs, U.f1.w, U.f1.b, nullptr, 0.1f, 1, 4, 2 * g.fd, fa, 2 * g.fd, 1, h8, w8, st));
-            AMT_DO(r.conv(U.f2, fa, 2 * g.fd, h8, w8, cf + cdo, cf_cs, 1, 1));
-            // (writes channels 0 .. fc of inp, directly in front of the flow window copied above: the layer objects store exactly Cout
-            // channels, never Cout rounded up, see the `co < a.Cout` guards of conv_mfma*.hip / conv_wino.hip)
-            AMT_DO(r.conv(U.cv, cf, cf_cs, h8, w8, inp, inp_cs, 1, 1));
-            AMT_DO(r.conv(U.g0, inp, inp_cs, h8, w8, h1, hcs, 1, 1));
-            AMT_DO(r.conv(U.g2, h1, hcs, h8, w8, h2, hcs, 1, 0));
-            AMT_DO(r.conv(U.fh0, h2, hcs, h8, w8, h1, hcs, 1, 1));
-            AMT_DO(r.conv(U.fh2, h1, hcs, h8, w8, dn, r8(ch), 1, 0));
-            AMT_DO(r.conv(U.wh0, h2, hcs, h8, w8, h3, hcs, 1, 1));
-            AMT_DO(r.conv(U.wh2, h3, hcs, h8, w8, df, 8, 1, 0));
+            AMT_DO(update_tail(r, g, U, fd, fd_cs, ch, h8, w8, inp, inp_cs, cf, cf_cs, fa, h1, h2, h3, dn, df));
             const float *dnu = dn, *dfu = df;
             int dnu_cs = r8(ch), dfu_cs = 8;
             if (down != 1) {
@@ -678,6 +754,27 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             if (r.bad) return -1;
             AMT_DO(r.add(ft, fcs, w, 1, dnu, dnu_cs, din, din_cs, h, w, ch));
             AMT_DO(r.add(fl, fcs, w, 1, dfu, dfu_cs, din + 3 * ch, din_cs, h, w, 4));
+            if (G && down != 1) {
+                // update3_high / update2_high (:1537-1543, :1558-1564) at this level's own resolution, on the sums just written (ft + dft,
+                // the four flow channels) and on the SAME lookup output.  The reference resizes the 392 lookup channels and then applies
+                // convc1 (1x1); convc1 is linear and per pixel and the bilinear weights sum to 1, so convc1 runs on the 1/8 map (bias, no
+                // activation) and its 256 channels are resized, with the LeakyReLU in the same pass: the resized lookup output never exists
+                const Upd& UH = m->upd[s + 2];
+                TraceScope high("amt_high_blocks", st);      // an outer scope: everything the two high blocks launch (tools/amt_bench.py)
+                float *c1lo = r.buf("updh_c1lo", 1, h8, w8, g.cd), *c1 = r.buf("updh_c1", 1, h, w, g.cd);
+                float *inph = r.buf("upd_in", 1, h, w, inp_cs), *cfh = r.buf("upd_cf", 1, h, w, cf_cs), *fah = r.buf("upd_f1", 1, h, w, 2 * g.fd);
+                float *h1h = r.buf("upd_h1", 1, h, w, hcs), *h2h = r.buf("upd_h2", 1, h, w, hcs), *h3h = r.buf("upd_h3", 1, h, w, hcs);
+                float *dnh = r.buf("upd_dn", 1, h, w, r8(ch)), *dfh = r.buf("upd_df", 1, h, w, 8);
+                if (r.bad) return -1;
+                AMT_DO(r.conv(UH.c1, corr, 392, h8, w8, c1lo, g.cd, 1, 0));
+                AMT_DO(vfi_amt_upsample_lrelu(c1lo, g.cd, c1, g.cd, 1, h8, w8, g.cd, down, 0.1f, st));
+                AMT_DO(r.conv(UH.c2, c1, g.cd, h, w, cfh, cf_cs, 1, 1));
+                AMT_DO(r.copy(din, din_cs, inph + g.fc + 4, inp_cs, h, w, ch));
+                AMT_DO(r.copy(din + 3 * ch, din_cs, inph + g.fc, inp_cs, h, w, 4));
+                AMT_DO(update_tail(r, g, UH, din + 3 * ch, din_cs, ch, h, w, inph, inp_cs, cfh, cf_cs, fah, h1h, h2h, h3h, dnh, dfh));
+                AMT_DO(r.add(din, din_cs, w, 1, dnh, r8(ch), din, din_cs, h, w, ch));
+                AMT_DO(r.add(din + 3 * ch, din_cs, w, 1, dfh, 8, din + 3 * ch, din_cs, h, w, 4));
+            }
             AMT_DO(r.warp(pyr[lvl], pcs[lvl], din + 3 * ch, din_cs, din + ch, din_cs, h, w, ch));
             AMT_DO(r.warp(pyr[lvl] + (size_t)h * w * pcs[lvl], pcs[lvl], din + 3 * ch + 2, din_cs, din + 2 * ch, din_cs, h, w, ch));
             AMT_DO(run_decoder(r, dc, g.skip, din, din_cs, h, w, on, ocs));
@@ -695,7 +792,7 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
         float *wr = r.buf("comb_in", 1, Hp, Wp, wr_cs), *mid = r.buf("comb_mid", 1, Hp, Wp, mid_cs), *cb = r.buf("comb_out", 1, Hp, Wp, 8);
         if (r.bad) return -1;
         AMT_DO(vfi_amt_combine_warps(img, img + (size_t)P * 8, 8, fl, fcs, mean, g.nf, wr, wr_cs, Hp, Wp, st));
-        if (L) {
+        if (basic) {
             AMT_DO(vfi_conv7x7(wr, wr_cs, m->cb7[0].w, m->cb7[0].b, m->cb7[0].pr, 0.f, 3, 3 * g.nf, 6 * g.nf, mid, mid_cs, 1, Hp, Wp, st));
             AMT_DO(vfi_conv7x7(mid, mid_cs, m->cb7[1].w, m->cb7[1].b, nullptr, 0.f, 0, 6 * g.nf, 3, cb, 8, 1, Hp, Wp, st));
         } else {
@@ -714,16 +811,17 @@ int amt_pad(int n) { return n + (((n / 16) + 1) * 16 - n) % 16; }
 extern "C" {
 
 vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, int n_tensors, int variant) {
-    const int want = variant == 0 ? 213 : 207;
-    if (!tensors || !numels || (variant != 0 && variant != 1) || n_tensors != want) {
-        set_error("vfi_amt_create: expected the %d state_dict tensors of AMT-%s in amt_spec.amt_shapes() order (variant 0 = S, 1 = L), got %d (variant %d)",
-                  want, variant == 1 ? "L" : "S", n_tensors, variant);
+    const bool known = variant >= 0 && variant <= 2;
+    const int want = known ? kCfg[variant].n_tensors : 0;
+    if (!tensors || !numels || !known || n_tensors != want) {
+        set_error("vfi_amt_create: expected the %d state_dict tensors of AMT-%s in amt_spec.amt_shapes() order (variant 0 = S, 1 = L, 2 = G), got %d "
+                  "(variant %d)", want, known ? kCfg[variant].name : "?", n_tensors, variant);
         return nullptr;
     }
     vfi_amt* m = new vfi_amt();
     m->variant = variant;
     const Cfg& g = kCfg[variant];
-    const bool L = variant == 1;
+    const bool basic = variant >= 1, G = variant == 2;
     TensorCursor cur(tensors, numels, n_tensors, "vfi_amt_create");
     // Conv2d (kind 0) / ConvTranspose2d (kind 1) with bias, then the PReLU slopes where the layer has them
     auto layer = [&](int kind, int cout, int cin, int k, int stride, bool prelu, const int* map = nullptr, int cin_phys = 0) -> vfi_conv_t* {
@@ -734,23 +832,26 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
         return m->add_layer(vfi_conv_create_ex(kind, w, b, cout, cin, k, stride, 0, map, cin_phys ? cin_phys : r8(cin), p));
     };
     std::vector<float> tmp;
-    // Conv2d(3, cout <= 64, 7, 2, 3) [+ PReLU] for vfi_conv7x7s2_prelu: [7][7][3][64], the missing output channels zero; slope 1 = no activation
+    // Conv2d(3, cout, 7, 2, 3) [+ PReLU] for vfi_conv7x7s2_prelu: [7][7][3][P], P = 64 with the missing output channels zero, or AMT-G's 84
+    // as they are (the two widths the kernel is instantiated for); slope 1 = no activation
     auto stem = [&](Stem& s, int cout, bool prelu) {
         const float* w = cur.take((int64_t)cout * 3 * 49);
         const float* b = cur.take(cout);
         const float* p = prelu ? cur.take(cout) : nullptr;
         if (!cur.ok()) return;
-        tmp.assign((size_t)49 * 3 * 64, 0.f);
+        const int P = cout <= 64 ? 64 : 84;
+        tmp.assign((size_t)49 * 3 * P, 0.f);
         for (int co = 0; co < cout; ++co)
             for (int ci = 0; ci < 3; ++ci)
-                for (int t = 0; t < 49; ++t) tmp[((size_t)t * 3 + ci) * 64 + co] = w[((size_t)co * 3 + ci) * 49 + t];
+                for (int t = 0; t < 49; ++t) tmp[((size_t)t * 3 + ci) * P + co] = w[((size_t)co * 3 + ci) * 49 + t];
         s.w = m->upload(tmp.data(), tmp.size());
-        tmp.assign(64, 0.f);
+        tmp.assign(P, 0.f);
         memcpy(tmp.data(), b, cout * sizeof(float));
-        s.b = m->upload(tmp.data(), 64);
-        tmp.assign(64, 1.f);
+        s.b = m->upload(tmp.data(), P);
+        tmp.assign(P, 1.f);
         if (p) memcpy(tmp.data(), p, cout * sizeof(float));
-        s.slope = m->upload(tmp.data(), 64);
+        s.slope = m->upload(tmp.data(), P);
+        s.cout = P;
     };
     // Conv2d(cin, cout, 7, 1, 3) [+ PReLU] for vfi_conv7x7: [7][7][Cin4][CoutP]
     auto conv7 = [&](Conv7& c, int cout, int cin, bool prelu) {
@@ -771,12 +872,12 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
     // feature encoder
     stem(m->fe_stem, g.e1, false);
     int cin = g.e1;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < g.n_enc; ++i) {
         const int c = g.enc[i];
         for (int b = 0; b < 2; ++b) {
             EncBlk& B = m->blk[2 * i + b];
-            B.cin = b == 0 ? cin : c, B.c = c, B.stride = (b == 0 && i > 0) ? 2 : 1;
-            if (!L) {
+            B.cin = b == 0 ? cin : c, B.c = c, B.stride = b == 0 ? g.enc_stride[i] : 1;
+            if (!basic) {
                 B.c1 = layer(0, c / 4, B.cin, 1, 1, false);
                 B.c2 = layer(0, c / 4, c / 4, 3, B.stride, false);
                 B.c3 = layer(0, c, c / 4, 1, 1, false);
@@ -792,9 +893,9 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
     // pyramid encoder
     int prev = 3;
     for (int i = 0; i < 4; ++i) {
-        if (L && i == 0) stem(m->py_stem, g.ch[0], true);
-        else m->py0[i] = layer(0, g.ch[i], prev, 3, 2, true, nullptr, (L && i == 1) ? 64 : 0);
-        m->py1[i] = layer(0, g.ch[i], g.ch[i], 3, 1, true, nullptr, (L && i == 0) ? 64 : 0);
+        if (basic && i == 0) stem(m->py_stem, g.ch[0], true);
+        else m->py0[i] = layer(0, g.ch[i], prev, 3, 2, true, nullptr, (basic && !G && i == 1) ? 64 : 0);
+        m->py1[i] = layer(0, g.ch[i], g.ch[i], 3, 1, true, nullptr, (basic && !G && i == 0) ? 64 : 0);
         prev = g.ch[i];
     }
     // decoders
@@ -817,9 +918,9 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
         d.up = layer(1, d.cout, c, 4, 2, false);
     }
     // update blocks
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < g.n_upd; ++k) {      // update4, update3[_low], update2[_low], then AMT-G's update3_high, update2_high
         Upd& U = m->upd[k];
-        const int cdim = g.ch[2 - k], cdo = g.cd2 ? g.cd2 : g.cd;
+        const int cdim = g.ch[k < 3 ? 2 - k : 4 - k], cdo = g.cd2 ? g.cd2 : g.cd;
         U.c1 = layer(0, g.cd, 392, 1, 1, false);
         if (g.cd2) U.c2 = layer(0, g.cd2, g.cd, 3, 1, false);
         conv7(U.f1, 2 * g.fd, 4, false);
@@ -832,7 +933,7 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
         U.wh0 = layer(0, g.hid, g.hid, 3, 1, false);
         U.wh2 = layer(0, 4, g.hid, 3, 1, false);
     }
-    if (L) {
+    if (basic) {
         conv7(m->cb7[0], 6 * g.nf, 3 * g.nf, true);
         conv7(m->cb7[1], 3, 6 * g.nf, false);
     } else {
@@ -864,9 +965,10 @@ int vfi_amt_forward(vfi_amt_t* m, const float* frame0_dev, const float* frame1_d
     VFI_REQUIRE(Hp >= 128 && Wp >= 128,
                 "vfi_amt_forward: a %dx%d frame (padded %dx%d): AMT needs padded sides of at least 128 pixels (below, the coarsest correlation level is "
                 "one pixel wide and the reference is all-NaN)", H, W, Hp, Wp);
-    VFI_REQUIRE((long)Hp * Wp * 64 * 4 < 0x7fffffffL,
-                "vfi_amt_forward: a %dx%d frame (padded %dx%d) is over the size limit: Hp * Wp * 256 bytes must stay below 2 GiB for the layers' index "
-                "arithmetic (1088x1920 fits)", H, W, Hp, Wp);
+    const int pxf = kCfg[m->variant].px_floats;      // the variant's widest activation, floats per padded pixel
+    VFI_REQUIRE((long)Hp * Wp * pxf * 4 < 0x7fffffffL,
+                "vfi_amt_forward: a %dx%d frame (padded %dx%d) is over the size limit: Hp * Wp * %d bytes must stay below 2 GiB for the layers' index "
+                "arithmetic (1088x1920 fits)", H, W, Hp, Wp, pxf * 4);
     hipStream_t st = (hipStream_t)stream;
     if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp) && m->ws.release()) return -1;
     m->Hp = Hp, m->Wp = Wp;

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "../../include/vfi_hip.h"
+#include "bilinear_src.h"
 #include "rife_warp.h"
 
 namespace vfi {
@@ -111,25 +112,6 @@ __global__ void fill_items_kernel(float* __restrict__ out, int cs, int C, long p
     out[((size_t)blockIdx.y * px_per_item + p) * cs + (idx - p * C)] = vals.v[blockIdx.y];
 }
 
-// torch area_pixel_compute_source_index(ratio, dst, align_corners=False) + guard_index_and_lambda, with the ratio the
-// caller derived from the user's scale_factor (F.interpolate(scale_factor=s) passes 1/s, not in/out)
-struct BilS {
-    int i0, i1;
-    float w0, w1;
-};
-__device__ static inline BilS bil_src(int d, float ratio, int in_size) {
-    float src = __fsub_rn(__fmul_rn(ratio, __fadd_rn((float)d, 0.5f)), 0.5f);
-    if (src < 0.f) src = 0.f;
-    int i0 = (int)floorf(src);
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    const float l = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
-    BilS b;
-    b.i0 = i0;
-    b.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    b.w1 = l;
-    b.w0 = __fsub_rn(1.0f, l);
-    return b;
-}
 __global__ void resize_ratio_kernel(const float* __restrict__ in, int in_cs, float* __restrict__ out, int out_cs, int N, int Hi,
                                     int Wi, int Ho, int Wo, int C, float ry, float rx, float post_mul) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,11 +209,17 @@ int vfi_conv7x7s2_prelu(const float* in_dev, int in_cs, const float* w_dev, cons
     VFI_REQUIRE(in_dev && w_dev && bias_dev && slope_dev && out_dev && N > 0 && Hin > 0 && Win > 0 && in_cs >= 3 && out_cs >= Cout &&
                     out_cs % 4 == 0 && ((uintptr_t)out_dev & 15) == 0,
                 "vfi_conv7x7s2_prelu: bad arguments");
-    VFI_REQUIRE(Cout == 64, "vfi_conv7x7s2_prelu: Cout=%d not instantiated (IFRNet_L's head has 64)", Cout);
+    VFI_REQUIRE(Cout == 64 || Cout == 84, "vfi_conv7x7s2_prelu: Cout=%d not instantiated (IFRNet_L's head has 64, AMT-G's pyramid stem 84)", Cout);
     const int Ho = (Hin - 1) / 2 + 1, Wo = (Win - 1) / 2 + 1;
     TraceScope ts("conv7x7s2", (hipStream_t)stream);
-    hipLaunchKernelGGL((conv7x7s2_prelu_kernel<64>), dim3((unsigned)(((long)N * Ho * Wo + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
-                       in_dev, in_cs, w_dev, bias_dev, slope_dev, out_dev, out_cs, N, Hin, Win);
+    const dim3 grid((unsigned)(((long)N * Ho * Wo + 127) / 128));
+    // 84 accumulators per thread still fit the registers of a 128-lane workgroup without scratch; the 64-channel instantiation is untouched
+    if (Cout == 64)
+        hipLaunchKernelGGL((conv7x7s2_prelu_kernel<64>), grid, dim3(128), 0, (hipStream_t)stream, in_dev, in_cs, w_dev, bias_dev, slope_dev,
+                           out_dev, out_cs, N, Hin, Win);
+    else
+        hipLaunchKernelGGL((conv7x7s2_prelu_kernel<84>), grid, dim3(128), 0, (hipStream_t)stream, in_dev, in_cs, w_dev, bias_dev, slope_dev,
+                           out_dev, out_cs, N, Hin, Win);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }

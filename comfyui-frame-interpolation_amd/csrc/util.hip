@@ -111,6 +111,7 @@ struct TraceRec {
 };
 static bool g_trace = false;
 static std::vector<TraceRec> g_recs;
+static std::vector<size_t> g_open;      // indices of the scopes begun and not yet ended, innermost last
 static std::vector<hipEvent_t> g_free_events;
 
 static hipEvent_t get_event() {
@@ -131,10 +132,17 @@ void trace_begin(const char* name, hipStream_t s) {
     r.e0 = get_event();
     r.e1 = get_event();
     (void)hipEventRecord(r.e0, s);
+    g_open.push_back(g_recs.size());
     g_recs.push_back(r);
 }
+// TraceScope captures trace_on() when it is constructed, which keeps g_open balanced: vfi_trace_enable must not be toggled while a
+// forward is inside a scope (an inner scope begun after enabling would be closed by an outer destructor's pop).
+// scopes nest: an outer scope (AMT-G's "amt_high_blocks" around the kernels of update*_high) ends on its own record, not on the last inner one
 void trace_end(hipStream_t s) {
-    if (!g_recs.empty()) (void)hipEventRecord(g_recs.back().e1, s);
+    if (g_open.empty()) return;
+    const size_t i = g_open.back();
+    g_open.pop_back();
+    if (i < g_recs.size()) (void)hipEventRecord(g_recs[i].e1, s);
 }
 
 
@@ -335,6 +343,7 @@ int vfi_trace_reset(void) {
         g_free_events.push_back(r.e1);
     }
     g_recs.clear();
+    g_open.clear();
     return 0;
 }
 

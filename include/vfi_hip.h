@@ -325,7 +325,7 @@ int vfi_ifrnet_prep(const float* frame0_dev, const float* frame1_dev, int C, int
  * writes mean_out[n] and subtracts it from the colour channels of both images in place (:248-249). */
 int vfi_ifrnet_center(float* img_dev, const float* chan_means_dev, float* mean_out_dev, int N, int64_t pixels, void* stream);
 /* convrelu(3, 64, 7, 2, 3): Conv2d 7x7 stride 2 pad 3 + PReLU(64), the head of IFRNet_L's encoder (:128-130).
- * w_dev [7][7][3][Cout] (device), out [N,(Hin-1)/2+1,(Win-1)/2+1,out_cs]. */
+ * w_dev [7][7][3][Cout] (device), out [N,(Hin-1)/2+1,(Win-1)/2+1,out_cs].  Cout is 64, or 84 (AMT-G's pyramid stem); out_cs % 4 == 0. */
 int vfi_conv7x7s2_prelu(const float* in_dev, int in_cs, const float* w_dev, const float* bias_dev, const float* slope_dev, int Cout,
                         float* out_dev, int out_cs, int N, int Hin, int Win, void* stream);
 /* torch.sigmoid in place over a C-channel window (:278) */
@@ -682,7 +682,7 @@ int vfi_flavr_forward(vfi_flavr_t* net, const float* const* frames_dev, int N, i
 int vfi_flavr_release_workspace(vfi_flavr_t* net);
 int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* net);
 
-/* ---- AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L): the kernels beside the layer objects ------------------------------------------- */
+/* ---- AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L / AMT_G): the kernels beside the layer objects ------------------------------------------- */
 
 /* The target side of the correlation pyramid without the volume: corr[q][p] = <f0[q], f1[p]> / sqrt(D) is linear in f1, so
  * avg_pool2d(corr[q]) = <f0[q], avg_pool2d(f1)> (BidirCorrBlock.__init__, :1083-1097).  f_dev [h,w,D] -> pooled_dev = levels 1..3
@@ -698,10 +698,17 @@ int vfi_amt_pool_features(const float* f_dev, int h, int w, int D, float* pooled
 int vfi_amt_corr_lookup(const float* fq_dev, const float* ft_dev, const float* ft_pooled_dev, const float* flow_dev, int flow_cs, float scale,
                         int h, int w, int D, float* out_dev, int out_cs, void* stream);
 /* Conv2d(Cin, Cout, 7, stride 1, padding 3) + bias (nullable) + activation (0 none, 1 leaky relu(slope), 3 PReLU(prelu_dev[Cout])) for thin
- * layers, Cin, Cout <= 96: convf1 of the update blocks (:977, :1031) and AMT-L's comb_block (:1322-1326).  in [N,H,W,in_cs], out
+ * layers, Cin <= 96, Cout <= 128: convf1 of the update blocks (:977, :1031; 4 -> 128 in AMT-G) and AMT-L's / AMT-G's comb_block (:1322-1326).  in [N,H,W,in_cs], out
  * [N,H,W,out_cs].  w_dev: [7][7][Cin4][CoutP] zero-padded, Cin4 = Cin rounded up to 4, CoutP = Cout rounded up to 4 (Cout <= 4) or 16. */
 int vfi_conv7x7(const float* in_dev, int in_cs, const float* w_dev, const float* bias_dev, const float* prelu_dev, float slope, int act,
                 int Cin, int Cout, float* out_dev, int out_cs, int N, int H, int W, void* stream);
+/* leaky_relu(F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=False), slope) in one pass, scale 2 or 4: in [N,h,w,in_cs],
+ * a C-channel window; out [N,scale h,scale w,out_cs], C channels written, each once.  AMT-G's update3_high / update2_high re-read the low
+ * blocks' lookup output resized by 2 / 4 (:1537-1543, :1558-1564) and open with a 1x1 convolution: the object runs that convolution on
+ * the low-resolution map and this kernel on its output (the two commute: the bilinear weights sum to 1), so the resized 392-channel tensor
+ * never exists.  float4 accesses when C, both strides and both pointers are multiples of 4 floats, scalar ones otherwise. */
+int vfi_amt_upsample_lrelu(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int h, int w, int C, int scale, float slope,
+                           void* stream);
 /* multi_flow_combine up to comb_block's input (:883-900): out[.., 3 i + c] = sigmoid(mask_i) * warp(img0, flow0_i)[c] + (1 - sigmoid(mask_i))
  * * warp(img1, flow1_i)[c] + mean + res_i[c] for the num_flows flow pairs; warp as amt_arch.warp (:26-34: border, align_corners=True).
  * img{0,1} [Hp,Wp,img_cs] mean-removed, fin [Hp,Wp,fin_cs] = flow0 (2 n) | flow1 (2 n) | mask logits (n) | res (3 n), mean_dev[0]. */
@@ -712,16 +719,18 @@ int vfi_amt_combine_out(const float* warps_dev, int warps_cs, const float* comb_
                         int Wp, int pad_top, int pad_left, int H, int W, void* stream);
 
 typedef struct vfi_amt vfi_amt_t;
-/* The state_dict tensors of AMT-S (variant 0: 213) or AMT-L (variant 1: 207) in amt_spec.amt_shapes(variant) order (fp32 host memory, copied).
- * Replaces AMT_S.__init__ / AMT_L.__init__ + load_state_dict (vfi_models/amt/amt_arch.py:1153-1188, :1297-1332; amt/__init__.py:61-66). */
+/* The state_dict tensors of AMT-S (variant 0: 213), AMT-L (variant 1: 207) or AMT-G (variant 2: 259) in amt_spec.amt_shapes(variant) order
+ * (fp32 host memory, copied).  Replaces AMT_S / AMT_L / AMT_G.__init__ + load_state_dict (vfi_models/amt/amt_arch.py:1153-1188, :1297-1332,
+ * :1441-1471; amt/__init__.py:61-66). */
 vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, int n_tensors, int variant);
 void vfi_amt_destroy(vfi_amt_t* net);
 /* clamp(unpad(model(pad(frame0), pad(frame1), embt = t)), 0, 1) for ONE pair and n_t timesteps ts_host[0 .. n_t) in (0, 1) (amt_arch.py:1205-1285,
  * :1349-1429; amt/__init__.py:88-97): frames [H,W,C>=3] fp32 (not written), out_dev [n_t,H,W,3].  Once per call: the centred replicate pad to
  * multiples of 16, mean_, the feature encoder on both frames, both pyramid encoders, the pooled feature maps.  Per timestep: decoders, lookups,
  * update blocks, multi_flow_combine, clamp, un-pad; a timestep's result does not depend on the others of its call.  No correlation volume is
- * built.  Frames whose padded side is below 128 (the reference is all-NaN there) or whose padded size exceeds 2^23 - 1 pixels are refused
- * before any launch. */
+ * built.  AMT-G (:1494-1581) adds update3_high / update2_high after the low blocks, at 1/4 and 1/2 resolution, on the same lookup output.
+ * Frames whose padded side is below 128 (the reference is all-NaN there) or whose padded size exceeds 2^23 - 1 pixels (AMT-G: 6 100 805,
+ * its widest activation has 88 floats per padded pixel) are refused before any launch. */
 int vfi_amt_forward(vfi_amt_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ts_host, int n_t,
                     float* out_dev, void* stream);
 int vfi_amt_release_workspace(vfi_amt_t* net);

@@ -1,13 +1,16 @@
-"""Device-resident AMT-S / AMT-L at 1080p (one vfi_amt_forward per frame pair with all of the pair's timesteps), seeded weights.
+"""Device-resident AMT-S / AMT-L / AMT-G at 1080p (one vfi_amt_forward per frame pair with all of the pair's timesteps), seeded weights.
 
-    python tools/amt_bench.py [--iters 5] [--variants S,L] [--trace]
+    python tools/amt_bench.py [--iters 5] [--variants S,L | --variant G] [--trace]
 
 Prints one JSON line.  Per variant: ms per NEW frame at multiplier 2 (one timestep per pair) and at multiplier 8 (seven timesteps per
 pair), each the median of `iters` forward calls timed with device events around the call (frames already on the device, workspace
 allocated by two warm-up calls); the per-pair and per-timestep parts those two figures imply (pair = what runs once per call: pad, mean,
 feature encoder, pyramid encoders, pooled maps); the workspace size beside the bytes of the reference's correlation volumes at this size
 (two directions, four levels) and of one level-0 volume; and with --trace the library's per-kernel event trace (vfi_trace_*) of one
-extra 8x call: the share of the new kernels (amt_lookup, amt_pool2, conv7x7, amt_warps, amt_out, ...) and of the layer objects."""
+extra 8x call: the share of the new kernels (amt_lookup, amt_pool2, conv7x7, amt_warps, amt_out, ...) and of the layer objects.
+AMT-G (the tool turns the amt_g key on for its own process; every variant's output is asserted finite): with --trace also the kernel only
+the two high blocks launch, amt_upsample, with the bytes it has to move in the 8x call — its 1/8-resolution input once per launch, its
+1/4- and 1/2-resolution outputs once — over its traced time, as a fraction of the 8.0 TB/s HBM peak (the kernel is bandwidth-bound)."""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--variants", default="S,L")
+    ap.add_argument("--variant", default=None, help="one variant (S, L or G); overrides --variants")
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--trace", action="store_true", help="per-kernel event trace of one extra 8x call (kernel shares)")
@@ -45,55 +49,76 @@ def main():
     f = torch.rand(2, H, W, 3, generator=g).cuda()
     res = {"workload": f"amt {H}x{W} (padded {Hp}x{Wp}), device-resident, ms per new frame", "iters": args.iters,
            "reference_volume_bytes": 2 * 4 * h8 * w8 * sum((h8 >> l) * (w8 >> l) for l in range(4)), "reference_level0_volume_bytes": 4 * (h8 * w8) ** 2}
-    for variant in args.variants.split(","):
-        eng = AmtEngine(seeded_state_dict(variant, 1))
-        r = {}
-        for m in (2, 8):
-            ts = [k / m for k in range(1, m)]
-            out = torch.empty((len(ts), H, W, 3), device="cuda")
-            call = lambda: eng.forward(f[0], f[1], ts, out)      # noqa: E731
-            for _ in range(2):
+    variants = [args.variant] if args.variant else args.variants.split(",")
+    from cfi_amd import ckpt
+
+    real_config = ckpt.load_config
+    if "G" in variants:      # AMT-G is opt-in (config.yaml's amt_g); this tool asks for it by name, and puts the real function back
+        ckpt.load_config = lambda: dict(real_config(), amt_g=True)
+    try:
+        for variant in variants:
+            eng = AmtEngine(seeded_state_dict(variant, 1))
+            r = {}
+            for m in (2, 8):
+                ts = [k / m for k in range(1, m)]
+                out = torch.empty((len(ts), H, W, 3), device="cuda")
+                call = lambda: eng.forward(f[0], f[1], ts, out)      # noqa: E731
+                for _ in range(2):
+                    call()
+                torch.cuda.synchronize()
+                assert torch.isfinite(out).all(), f"AMT-{variant} at {H}x{W}, multiplier {m}: non-finite output"
+                samples = []
+                for _ in range(args.iters):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    call()
+                    b.record()
+                    b.synchronize()
+                    samples.append(a.elapsed_time(b))
+                r[f"x{m}_ms_per_pair"] = round(statistics.median(samples), 3)
+                r[f"x{m}_ms_per_frame"] = round(statistics.median(samples) / len(ts), 3)
+                r[f"x{m}_ms_samples"] = [round(t, 3) for t in samples]
+            per_t = (r["x8_ms_per_pair"] - r["x2_ms_per_pair"]) / 6
+            r["per_timestep_ms"], r["per_pair_ms"] = round(per_t, 3), round(r["x2_ms_per_pair"] - per_t, 3)
+            r["workspace_bytes"] = eng.workspace_bytes()
+            if args.trace:
+                lib = _lib.load()
+                lib.vfi_trace_reset()
+                lib.vfi_trace_enable(1)
                 call()
-            torch.cuda.synchronize()
-            samples = []
-            for _ in range(args.iters):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                call()
-                b.record()
-                b.synchronize()
-                samples.append(a.elapsed_time(b))
-            r[f"x{m}_ms_per_pair"] = round(statistics.median(samples), 3)
-            r[f"x{m}_ms_per_frame"] = round(statistics.median(samples) / len(ts), 3)
-            r[f"x{m}_ms_samples"] = [round(t, 3) for t in samples]
-        per_t = (r["x8_ms_per_pair"] - r["x2_ms_per_pair"]) / 6
-        r["per_timestep_ms"], r["per_pair_ms"] = round(per_t, 3), round(r["x2_ms_per_pair"] - per_t, 3)
-        r["workspace_bytes"] = eng.workspace_bytes()
-        if args.trace:
-            lib = _lib.load()
-            lib.vfi_trace_reset()
-            lib.vfi_trace_enable(1)
-            call()
-            torch.cuda.synchronize()
-            lib.vfi_trace_enable(0)
-            buf = C.create_string_buffer(1 << 20)
-            lib.vfi_trace_report(buf, len(buf))
-            rows = {}
-            for line in buf.value.decode().splitlines():
-                parts = line.split()
-                if len(parts) >= 3:
-                    try:
-                        rows[parts[0]] = (int(parts[1]), float(parts[2]))
-                    except ValueError:
-                        pass
-            total = sum(v[1] for v in rows.values()) or 1.0
-            new = ("amt_", "conv7x7")
-            r["trace_x8_total_ms"] = round(total, 3)
-            r["trace_x8_new_kernels"] = {k: [v[0], round(v[1], 3), round(v[1] / total, 3)] for k, v in rows.items() if k.startswith(new)}
-            r["trace_x8_layer_objects_share"] = round(sum(v[1] for k, v in rows.items() if k.startswith(("conv", "deconv")) and not k.startswith("conv7x7")) / total, 3)
-            r["trace_x8_rows"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rows.items(), key=lambda kv: -kv[1][1])[:12]}
-        res["AMT-" + variant] = r
-        eng.close()
+                torch.cuda.synchronize()
+                lib.vfi_trace_enable(0)
+                buf = C.create_string_buffer(1 << 20)
+                lib.vfi_trace_report(buf, len(buf))
+                rows = {}
+                for line in buf.value.decode().splitlines():
+                    parts = line.split()
+                    if len(parts) >= 3:
+                        try:
+                            rows[parts[0]] = (int(parts[1]), float(parts[2]))
+                        except ValueError:
+                            pass
+                high = rows.pop("amt_high_blocks", None)      # an outer scope around the high blocks' kernels, not a kernel: kept out of the sum
+                total = sum(v[1] for v in rows.values()) or 1.0
+                if high:
+                    r["trace_x8_high_blocks"] = [high[0], round(high[1], 3), round(high[1] / total, 3)]
+                new = ("amt_", "conv7x7")
+                r["trace_x8_total_ms"] = round(total, 3)
+                r["trace_x8_new_kernels"] = {k: [v[0], round(v[1], 3), round(v[1] / total, 3)] for k, v in rows.items() if k.startswith(new)}
+                r["trace_x8_layer_objects_share"] = round(sum(v[1] for k, v in rows.items() if k.startswith(("conv", "deconv")) and not k.startswith("conv7x7")) / total, 3)
+                if variant == "G" and "amt_upsample" in rows:
+                    # vfi_amt_upsample_lrelu per timestep: convc1's 256 channels at 1/8 resolution read twice (x2 and x4), written at 1/4 and 1/2
+                    px8 = h8 * w8
+                    nbytes = 7 * 4 * 256 * (2 * px8 + 4 * px8 + 16 * px8)
+                    ms = rows["amt_upsample"][1]
+                    r["upsample_bytes_x8_call"], r["upsample_ms_x8_call"] = nbytes, round(ms, 3)
+                    r["upsample_bytes_per_s"] = round(nbytes / (ms * 1e-3), 0)
+                    r["upsample_share_of_hbm_peak_8TBps"] = round(nbytes / (ms * 1e-3) / 8.0e12, 3)
+                r["trace_x8_rows"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rows.items(), key=lambda kv: -kv[1][1])[:12]}
+            res["AMT-" + variant] = r
+            eng.close()
+    finally:
+        ckpt.load_config = real_config
     print(json.dumps(res))
 
 
