@@ -17,6 +17,7 @@ _LAZY = {
     "SepconvVFI": ("sepconv", "SepconvVFI"),
     "FLAVR_VFI": ("flavr", "FLAVR_VFI"),
     "AMT_VFI": ("amt", "AMT_VFI"),
+    "ATM_VFI": ("atm", "ATM_VFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -61,6 +62,10 @@ def _node_class_mappings():
         from .amt import AMT_VFI
 
         extra["AMT VFI"] = AMT_VFI
+    if "atm_vfi" in extra_nodes():
+        from .atm import ATM_VFI
+
+        extra["ATM VFI"] = ATM_VFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -75,10 +80,12 @@ def _node_class_mappings():
 
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
 # list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
-# FLAVR's and AMT's keys are the reference's class names lower-cased, "flavr_vfi" / "amt_vfi"; a bare "flavr" or "amt" is not a key.
+# FLAVR's, AMT's and ATM's keys are the reference's class names lower-cased, "flavr_vfi" / "amt_vfi" / "atm_vfi"; a bare "flavr", "amt" or
+# "atm" is not a key.  ATM VFI serves atm-vfi-lite.pt (ATM-lite) with global motion "On" or "Off (fastest)".
 # AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled).
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
-               "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)")}
+               "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)"),
+               "atm_vfi": ("ATM VFI", "ATM VFI (MI355X HIP)")}
 
 
 def extra_nodes():

@@ -1,0 +1,110 @@
+"""ATM VFI node — host-side mirror of the reference's ``ATM_VFI`` (ATM-lite only) over the HIP library.
+
+Node shape follows vfi_models/atm/__init__.py:76-182: the three checkpoint names, the three ``global_motion`` choices and the ``vfi``
+keywords.  ``atm-vfi-lite.pt`` is served; ``atm-vfi-base.pt`` / ``atm-vfi-base-pct.pt`` (ATM-base) and ``"On with Ensemble (slowest)"`` (the
+multi-scale global-motion ensemble) raise NotImplementedError naming themselves, before anything is loaded.  The frame loop is the
+reference's own (:152-177): per kept pair the first frame and the new frames of ``inference()`` (:39-74) — FILM's greedy midpoint schedule,
+every model call the midpoint of two known frames, clamped to [0, 1] and re-used —, a skipped pair contributes nothing at all, the clip's
+last frame is appended: schedule.film_output_plan + nodeloop.run_plan with film.film_schedule.  Each model call is ONE vfi_atm_forward
+(csrc/atm_net.hip): centred replicate pad to multiples of 64, the network, un-pad, clamp.  No pair lanes, no HIP graph.
+"""
+import typing
+
+import torch
+
+from . import _lib
+from .atm_spec import CKPT_NAMES, check_ckpt_name, check_state_dict, load_file, weight_shapes
+from .ckpt import cached_engine, engine_call, load_file_from_github_release
+from .film import film_schedule
+from .netengine import NetEngine, WorkspaceBytes
+from .nodeloop import run_plan
+from .schedule import InterpolationStateList, film_output_plan
+
+MODEL_TYPE = "atm"
+GLOBAL_MOTION = {"On": (True, False), "On with Ensemble (slowest)": (True, True), "Off (fastest)": (False, False)}      # (global motion, ensemble)
+FLOATS_PER_PADDED_PIXEL = 80      # the widest per-image buffer: the refinement net's input, 76 channels padded to 80 (csrc/atm_net.hip)
+MAX_PADDED_PIXELS = ((1 << 31) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)      # = vfi_atm_max_padded_pixels(): 6 710 886
+
+
+def padded_size(H, W):
+    """InputPadder(dims, 64) (atm/__init__.py:13-17): the sides rounded up to multiples of 64"""
+    return H + (((H // 64) + 1) * 64 - H) % 64, W + (((W // 64) + 1) * 64 - W) % 64
+
+
+def check_frame_size(H, W):
+    Hp, Wp = padded_size(H, W)
+    if Hp * Wp > MAX_PADDED_PIXELS:
+        raise ValueError(f"ATM VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({MAX_PADDED_PIXELS} padded pixels)")
+
+
+def global_motion_flag(global_motion):
+    """The widget's choice -> True / False; the ensemble choice and unknown ones raise by name."""
+    if global_motion not in GLOBAL_MOTION:
+        raise KeyError(f"unknown global_motion {global_motion!r} (known: {list(GLOBAL_MOTION)})")
+    on, ensemble = GLOBAL_MOTION[global_motion]
+    if ensemble:
+        raise NotImplementedError(f"global_motion {global_motion!r}: the multi-scale global-motion ensemble is not built yet; use 'On' or 'Off (fastest)'")
+    return on
+
+
+class AtmEngine(WorkspaceBytes, NetEngine):
+    """Device-resident ATM-lite: ``forward(frame0, frame1, global_motion)`` = the model's clamped, un-padded midpoint frame of one pair."""
+
+    PREFIX, LABEL = "vfi_atm", "ATM"
+
+    def shapes(self):
+        return weight_shapes()
+
+    def check_state_dict(self, state_dict):
+        check_state_dict(state_dict)
+
+    def forward(self, frame0, frame1, global_motion=True, out=None):
+        """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
+        H, W, Cc = frame0.shape
+        for f in (frame0, frame1):
+            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        check_frame_size(H, W)
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
+        self._call("forward", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, int(bool(global_motion)), out.data_ptr(), _lib.stream_ptr())
+        return out
+
+
+def atm_pair(eng, f0, f1, task, global_motion):
+    """One pair of the plan: task = (pair, positions) of schedule.film_output_plan.  The greedy midpoint schedule runs sequentially on the
+    current stream; every output is clamped (by the forward) and re-used as an input."""
+    new = task[1]
+    res = {0: f0, len(new) + 1: f1}
+    for l, r, k in film_schedule(len(new)):
+        res[k] = eng.forward(res[l], res[r], global_motion)
+    return [res[k] for k in new]
+
+
+class ATM_VFI:
+    @classmethod
+    def INPUT_TYPES(s):
+        return {
+            "required": {
+                "ckpt_name": (list(CKPT_NAMES),),
+                "frames": ("IMAGE",),
+                "clear_cache_after_n_frames": ("INT", {"default": 10, "min": 1, "max": 1000}),
+                "multiplier": ("INT", {"default": 2, "min": 2, "max": 2}),
+                "global_motion": (["On", "On with Ensemble (slowest)", "Off (fastest)"],),
+            },
+            "optional": {"optional_interpolation_states": ("INTERPOLATION_STATES",)},
+        }
+
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "vfi"
+    CATEGORY = "ComfyUI-Frame-Interpolation/VFI"
+
+    def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10, multiplier: typing.SupportsInt = 2,
+            global_motion="On", optional_interpolation_states: InterpolationStateList = None, **kwargs):
+        check_ckpt_name(ckpt_name)                      # ATM-base: NotImplementedError naming the file, before anything is loaded
+        gm = global_motion_flag(global_motion)          # the ensemble likewise
+        check_frame_size(*frames.shape[1:3])            # before an engine exists
+        plan, tasks = film_output_plan(len(frames), multiplier, optional_interpolation_states)
+        model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
+        entry = cached_engine(MODEL_TYPE, model_path, lambda: AtmEngine(load_file(model_path, ckpt_name)))
+        with engine_call(entry, tuple(frames.shape[1:3])) as engine:
+            return (run_plan(engine, frames, plan, tasks, lambda e, f0, f1, t: atm_pair(e, f0, f1, t, gm), "ATM VFI"),)

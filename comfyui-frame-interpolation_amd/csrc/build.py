@@ -32,7 +32,9 @@ EXTRA_FLAGS = {"conv_wino.hip": ["-fno-slp-vectorize"],
                # fma (a function-scope `#pragma clang fp contract(off)` did not survive inlining: 94 v_fmac_f32 in the first build)
                "m2m_render.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],
                # the lookup's coordinates are coord + flow * scale with two roundings, as torch computes them; dots and convolutions call fmaf
-               "amt_net.hip": ["-ffp-contract=off"]}
+               "amt_net.hip": ["-ffp-contract=off"],
+               # ATM: `score * scale + mask` and the warps' grid coordinates round as torch rounds them; dots and convolutions call fmaf
+               "atm_net.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

@@ -736,6 +736,62 @@ int vfi_amt_forward(vfi_amt_t* net, const float* frame0_dev, const float* frame1
 int vfi_amt_release_workspace(vfi_amt_t* net);
 int64_t vfi_amt_workspace_bytes(const vfi_amt_t* net);
 
+/* ---- ATM-lite (vfi_models/atm/network_lite.py Network, attention.py): the kernels beside the layer objects and the GMFSS ops ------------------ */
+
+/* Multi-head (8) attention over fixed windows of token MAPS, for both windowed blocks of ATM: cross != 0 is AttentionToMotion inside ATMFormer
+ * (attention.py:187-213, :265-334: q of frame f against k, v of frame f ^ 1, same window), cross == 0 is WindowAttention inside RefineBottleneck
+ * (:370-390, :433-495).  q / k / v_dev: channel windows (C channels, head hd at hd * C / 8) of token maps holding the two frames' h x w tokens
+ * back to back (token (f h + y) w + x), already normed (norm1) and projected; (C, window) = (224, 8) or (352, 12); shift = 0 or window / 2.
+ * pad_if_needed's centre padding to a window multiple, torch.roll by -shift, window_partition and their inverses (:8-71, :275-277, :313, :323-331)
+ * are the kernel's addressing: no padded, rolled or partitioned copy exists; a window slot outside the map reads token `pad_token` of q / k / v
+ * (the caller keeps one zero token behind the maps, so that after norm1 and the projections it is what the reference's zero padding becomes;
+ * required when h or w is no multiple of the window).  Additive mask -100 (not -inf) where the region labels of query and key differ: the nine
+ * centre-pad regions and, with a shift, the nine shift regions, BOTH taken at the slot's position in the rolled layout (the reference builds
+ * its pad mask before the roll and applies it after, :28-62, :282-303).  Scores and probabilities never leave the chip; q k^T and p v run on
+ * the fp32 matrix cores.  out_dev [2,h,w,out_cs]: softmax(q k^T / sqrt(C / 8) + mask) v per head, rows of padding dropped.  offsets_dev
+ * (nullable, cross only) [2,h,w,8,2]: per head sum_n p[n] (key x - query x, key y - query y) inside the window, the input of vfi_atm_motion_mlp
+ * (:207-208; the relative_coord buffer is not read: atm_spec.load_file checks that it holds exactly these offsets). */
+int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, int k_cs, const float* v_dev, int v_cs, int64_t pad_token,
+                             float* out_dev, int out_cs, float* offsets_dev, int h, int w, int C, int window, int shift, int cross, void* stream);
+/* AttentionToMotion.mlp over the heads (:143-146, :209-211): out[f * out_frame_stride + p * out_cs + coord] = w2 . gelu(w0 offsets[f][p][:, coord]
+ * + b0) + b2 for both frames, tokens p < tokens_per_frame and coord 0 (x), 1 (y); w0 [4][8], b0 [4], w2 [4], b2 [1] on the device. */
+int vfi_atm_motion_mlp(const float* offsets_dev, const float* w0_dev, const float* b0_dev, const float* w2_dev, const float* b2_dev, float* out_dev,
+                       int out_cs, int64_t out_frame_stride, int64_t tokens_per_frame, void* stream);
+/* gelu(Conv2d(C, C, 3, 1, 1, groups = C)(x) + bias): Mlp.dwconv + Mlp.act (:74-85, :116-119).  w_dev [9][C] (tap-major), bias_dev [C]; C % 4 == 0. */
+int vfi_atm_dwconv3x3_gelu(const float* in_dev, int in_cs, const float* w_dev, const float* bias_dev, float* out_dev, int out_cs, int N, int H, int W,
+                           int C, void* stream);
+/* The taps of Conv2d(C, C, 3, stride, padding = dilation, dilation) (CrossScaleFeatureFusion.layers, network_lite.py:38-50: stride 2 / 4,
+ * dilation 1 / 2) gathered for a 1x1 layer: out[n, y, x, t C + c] = in[n, y stride + (t / 3 - 1) dilation, x stride + (t % 3 - 1) dilation, c],
+ * zero outside; out [N, (H - 1) / stride + 1, (W - 1) / stride + 1, out_cs].  The convolution is vfi_conv_create_ex(0, w1, bias, C, 9 C, 1, 1, ...)
+ * with w1[co][t C + ci] = w[co][ci][t] on the MFMA kernel.  C % 4 == 0. */
+int vfi_atm_gather_taps(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int H, int W, int C, int stride, int dilation, void* stream);
+/* The interleave of ConvTranspose2d(Cin, C, 2, 2, 0) (deconv(), network_lite.py:27-32, :213-232, :256-268) run as a 1x1 layer with 4 C outputs
+ * (output channel (2 ky + kx) C + co; bias and PReLU slopes repeated per tap): out[n, 2 y + ky, 2 x + kx, c] = in[n, y, x, (2 ky + kx) C + c]. */
+int vfi_atm_depth_to_space2(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int H, int W, int C, void* stream);
+/* A synthesis step (network_lite.py:488-490, :515-517): w_k = flow_warp(src_k, flow_k) (flow_warp.py:26-60: bilinear, zeros, align_corners=True),
+ * I_t = sigmoid(m) w_0 + (1 - sigmoid(m)) w_1 with motion_dev [H,W,motion_cs] = (flow0 xy, flow1 xy, m).  out_dev [H,W,out_cs], 15 channels:
+ * (orig0 | w_0 | orig1 | w_1 | I_t), the layout the refinement net reads (:410); orig (nullable, both or none): channels 0..2 / 6..8 are left alone. */
+int vfi_atm_blend_warps(const float* src0_dev, const float* src1_dev, int src_cs, const float* orig0_dev, const float* orig1_dev, int orig_cs,
+                        const float* motion_dev, int motion_cs, float* out_dev, int out_cs, int H, int W, void* stream);
+/* The last step (:421, :524-525, InputPadder.unpad): out [H,W,3] = clamp(I_t + 2 sigmoid(res) - 1, 0, 1) cropped at (pad_top, pad_left) */
+int vfi_atm_refine_out(const float* it_dev, int it_cs, const float* res_dev, int res_cs, float* out_dev, int Hp, int Wp, int pad_top, int pad_left, int H,
+                       int W, void* stream);
+
+typedef struct vfi_atm vfi_atm_t;
+/* The 232 weight tensors of ATM-lite in atm_spec.weight_shapes() order = the state dict of network_lite.Network without its four relative_coord
+ * buffers (fp32 host memory, copied).  Replaces Network() + load_state_dict (vfi_models/atm/__init__.py:115-142). */
+vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors);
+void vfi_atm_destroy(vfi_atm_t* net);
+/* Network.forward_normal (network_lite.py:425-538)["I_t"] for ONE pair: frames [H,W,C>=3] fp32 (not written) are padded to multiples of 64
+ * (centred, replicate: InputPadder(dims, 64), atm/__init__.py:11-34, :62-68), out_dev [H,W,3] is the un-padded result, clamped to [0, 1].
+ * global_motion: 1 = "On", 0 = "Off (fastest)" (:76-80); the multi-scale ensemble is not built.  A frame whose padded size exceeds
+ * vfi_atm_max_padded_pixels() = (2^31 - 1) / 320 = 6 710 886 pixels is refused before any launch: the widest per-image buffer (the refinement
+ * net's input, 76 channels padded to 80) has 320 bytes per padded pixel and the layers index an image with 32 bits (1088 x 1920 fits). */
+int vfi_atm_forward(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream);
+int64_t vfi_atm_max_padded_pixels(void);
+int vfi_atm_release_workspace(vfi_atm_t* net);
+int64_t vfi_atm_workspace_bytes(const vfi_atm_t* net);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,103 @@
+"""Device-resident ATM-lite at 1080p (one vfi_atm_forward per new frame), seeded weights.
+
+    python tools/atm_bench.py [--iters 5] [--height 1080 --width 1920] [--no-parity] [--out profiles/atm_bench.json]
+
+Prints one JSON line (and writes it to --out).  Per global-motion mode ("On", "Off (fastest)"): ms per new frame, the median of `iters`
+forward calls timed with device events around the call (frames already on the device, workspace allocated by two warm-up calls); the
+workspace size; the library's per-kernel event trace (vfi_trace_*) of one extra call: the share of the new kernels (atm_attn_cross,
+atm_attn_self, atm_motion_mlp, atm_dwconv, atm_gather_taps, atm_depth_to_space, atm_blend, atm_out) and of the layer objects; and, unless
+--no-parity, the in-run parity of the timed frame against the float32 restatement (tests/atm_restated.py) on the CPU: max |d| over every
+pixel, asserted <= 1e-3."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--no-parity", action="store_true", help="skip the CPU restatement of the timed frame")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "atm_bench needs the GPU"
+    from pkgload import load_package
+
+    load_package()
+    import atm_restated
+    import cain_restated
+    from cfi_amd import _lib
+    from cfi_amd.atm import AtmEngine, padded_size
+    from cfi_amd.atm_spec import seeded_state_dict
+
+    H, W = args.height, args.width
+    Hp, Wp = padded_size(H, W)
+    frames = cain_restated.seeded_frames(2, H, W, 3, 31)
+    f = frames.cuda()
+    res = {"workload": f"atm-lite {H}x{W} (padded {Hp}x{Wp}), device-resident, ms per new frame", "iters": args.iters}
+    eng = AtmEngine(seeded_state_dict(atm_restated.SEED))
+    lib = _lib.load()
+    torch.set_num_threads(max(1, min(32, os.cpu_count() or 1)))
+    for mode, gm in atm_restated.MODES.items():
+        out = torch.empty((H, W, 3), device="cuda")
+        call = lambda: eng.forward(f[0], f[1], gm, out)      # noqa: E731
+        for _ in range(2):
+            call()
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all(), f"ATM-lite at {H}x{W}, {mode}: non-finite output"
+        samples = []
+        for _ in range(args.iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call()
+            b.record()
+            b.synchronize()
+            samples.append(a.elapsed_time(b))
+        r = {"ms_per_frame": round(statistics.median(samples), 3), "ms_samples": [round(t, 3) for t in samples], "workspace_bytes": eng.workspace_bytes()}
+        lib.vfi_trace_reset()
+        lib.vfi_trace_enable(1)
+        call()
+        torch.cuda.synchronize()
+        lib.vfi_trace_enable(0)
+        buf = C.create_string_buffer(1 << 20)
+        lib.vfi_trace_report(buf, len(buf))
+        rows = {}
+        for line in buf.value.decode().splitlines():
+            parts = line.split()
+            if len(parts) >= 3:
+                try:
+                    rows[parts[0]] = (int(parts[1]), float(parts[2]))
+                except ValueError:
+                    pass
+        total = sum(v[1] for v in rows.values()) or 1.0
+        r["trace_total_ms"] = round(total, 3)
+        r["trace_new_kernels"] = {k: [v[0], round(v[1], 3), round(v[1] / total, 3)] for k, v in rows.items() if k.startswith("atm_")}
+        r["trace_layer_objects_share"] = round(sum(v[1] for k, v in rows.items() if k.startswith(("conv", "deconv"))) / total, 3)
+        r["trace_rows"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rows.items(), key=lambda kv: -kv[1][1])[:12]}
+        if not args.no_parity:
+            x = frames.permute(0, 3, 1, 2).contiguous()
+            with torch.no_grad():
+                want = atm_restated.atm_frame(atm_restated.state_dict_as(torch.float32), x[0:1], x[1:2], gm)[0].permute(1, 2, 0)
+            r["parity_max_abs_vs_float32_restatement"] = float((out.cpu() - want).abs().max())
+            assert r["parity_max_abs_vs_float32_restatement"] <= atm_restated.TOL, r
+        res[mode] = r
+    eng.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
