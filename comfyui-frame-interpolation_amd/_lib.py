@@ -36,7 +36,9 @@ c_int_p = C.POINTER(C.c_int)
 c_i64_p = C.POINTER(C.c_longlong)
 
 # name -> (restype, argtypes); PROTOTYPES mirrors include/vfi_hip.h one to one, TEST_PROTOTYPES include/vfi_hip_test.h
-TEST_NAMES = ("vfi_conv3x3_naive", "vfi_test_conv_algo", "vfi_test_pack_wino3x3", "vfi_test_pack_deconv3x3", "vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_wino_probe_read", "vfi_rife_debug_keep", "vfi_rife_debug_read", "vfi_test_film_schedule", "vfi_test_linspace01", "vfi_film_debug_read_flow", "vfi_m2m_debug_read")
+TEST_NAMES = ("vfi_conv3x3_naive", "vfi_test_conv_algo", "vfi_test_pack_wino3x3", "vfi_test_pack_deconv3x3", "vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_wino_probe_read", "vfi_rife_debug_keep", "vfi_rife_debug_read", "vfi_test_film_schedule", "vfi_test_linspace01", "vfi_film_debug_read_flow", "vfi_m2m_debug_read",
+              "vfi_test_rife_stage_in", "vfi_test_rife_stage_in0_staged", "vfi_test_rife_flow_up", "vfi_test_rife_feat_up", "vfi_test_rife_stage_trans", "vfi_test_rife_stage_trans_x", "vfi_test_rife_trans1_conv0a", "vfi_test_rife_final_blend", "vfi_test_rife_planar4_up", "vfi_test_rife_t_down")
+_T = [C.c_void_p, C.c_int64, c_int_p, c_int_p, c_float_p, C.c_int]
 PROTOTYPES = {
     "vfi_init": (C.c_int, [C.c_int]),
     "vfi_last_error": (C.c_char_p, []),
@@ -157,6 +159,17 @@ PROTOTYPES = {
     "vfi_rife_interpolate": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_float_p, C.c_void_p, C.c_void_p]),
     "vfi_rife_debug_keep": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_rife_debug_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    # the RIFE stage kernels, one launcher per call (include/vfi_hip_test.h); _T = Ppool, pack_stride, slot0, slot1, t, B
+    "vfi_test_rife_stage_in": (C.c_int, _T + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "vfi_test_rife_stage_in0_staged": (C.c_int, _T + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_test_rife_flow_up": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "vfi_test_rife_feat_up": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "vfi_test_rife_stage_trans": (C.c_int, _T + [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "vfi_test_rife_stage_trans_x": (C.c_int, _T + [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "vfi_test_rife_trans1_conv0a": (C.c_int, _T + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "vfi_test_rife_final_blend": (C.c_int, _T + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "vfi_test_rife_planar4_up": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "vfi_test_rife_t_down": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "vfi_rife_work": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vfi_memcpy_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "vfi_stream_create": (C.c_int, [C.POINTER(C.c_void_p)]),

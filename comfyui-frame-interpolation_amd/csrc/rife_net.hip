@@ -719,6 +719,129 @@ int64_t vfi_rife_debug_read(vfi_rife_t* net, int what, int stage, float* host_bu
     }
     return (int64_t)n;
 }
+
+// ---- the stage kernels of rife_ops.hip, one launcher per call, on caller buffers (tests/test_gpu_rife_stage.py) ----
+static int stage_tasks(RifeTasks& tasks, const int* slot0, const int* slot1, const float* t, int B, const char* who) {
+    VFI_REQUIRE(B >= 1 && B <= kMaxTasks, "%s: batch %d outside 1..%d", who, B, kMaxTasks);
+    VFI_REQUIRE(slot0 && slot1 && t, "%s: null task table", who);
+    memset(&tasks, 0, sizeof(tasks));
+    for (int b = 0; b < B; ++b) {
+        VFI_REQUIRE(slot0[b] >= 0 && slot1[b] >= 0, "%s: task %d uses slots %d,%d", who, b, slot0[b], slot1[b]);
+        tasks.slot0[b] = slot0[b];
+        tasks.slot1[b] = slot1[b];
+        tasks.t[b] = t[b];
+    }
+    return 0;
+}
+static int stage_geo(int B, int Hp, int Wp, const char* who) {
+    VFI_REQUIRE(B >= 1 && B <= kMaxTasks, "%s: batch %d outside 1..%d", who, B, kMaxTasks);
+    VFI_REQUIRE(Hp > 0 && Wp > 0 && Hp % 64 == 0 && Wp % 64 == 0, "%s: %dx%d is not a padded frame (multiples of 64)", who, Hp, Wp);
+    return 0;
+}
+static bool stage_pow2(int s, int lo, int hi) { return s >= lo && s <= hi && (s & (s - 1)) == 0; }
+
+int vfi_test_rife_stage_in(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* F,
+                           const float* M, const float* FEAT, float* X, int Hp, int Wp, int s, int CX, int NF, int has_flow, void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_stage_in")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_stage_in")) return rc;
+    VFI_REQUIRE(Ppool && X && (NF == 1 || NF == 2) && pack_stride >= (int64_t)Hp * Wp * 4 * (1 + NF), "vfi_test_rife_stage_in: bad pack (NF %d, stride %lld)", NF,
+                (long long)pack_stride);
+    VFI_REQUIRE(stage_pow2(s, 1, 32), "vfi_test_rife_stage_in: scale %d", s);
+    VFI_REQUIRE(!has_flow || (F && M), "vfi_test_rife_stage_in: a flow needs F and M");
+    return stage_in_launch(Ppool, (size_t)pack_stride, tasks, B, F, M, FEAT, X, Hp, Wp, s, CX, NF, has_flow != 0, (hipStream_t)stream);
+}
+
+int vfi_test_rife_stage_in0_staged(const float* Spool, int64_t stage_stride, const int* slot0, const int* slot1, const float* t, int B, float* X, int Hp,
+                                   int Wp, void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_stage_in0_staged")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_stage_in0_staged")) return rc;
+    VFI_REQUIRE(Spool && X && stage_stride >= (int64_t)(Hp / 8) * (Wp / 8) * 8, "vfi_test_rife_stage_in0_staged: bad staging pool (stride %lld)",
+                (long long)stage_stride);
+    return stage_in0_staged_launch(Spool, (size_t)stage_stride, tasks, B, X, Hp, Wp, (hipStream_t)stream);
+}
+
+int vfi_test_rife_flow_up(const float* T, float* F, float* M, int B, int Hp, int Wp, int s, int tp, int has_prev, void* stream) {
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_flow_up")) return rc;
+    VFI_REQUIRE(T && F && M && stage_pow2(s, 1, 16) && (tp == 2 || tp == 4), "vfi_test_rife_flow_up: scale %d, %d planes", s, tp);
+    return flow_up_launch(T, F, M, B, Hp, Wp, s, tp, has_prev != 0, (hipStream_t)stream);
+}
+
+int vfi_test_rife_feat_up(const float* T, float* FEAT, int B, int Hp, int Wp, int s, void* stream) {
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_feat_up")) return rc;
+    VFI_REQUIRE(T && FEAT && stage_pow2(s, 1, 16), "vfi_test_rife_feat_up: scale %d", s);
+    return feat_up_launch(T, FEAT, B, Hp, Wp, s, (hipStream_t)stream);
+}
+
+int vfi_test_rife_stage_trans(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T, float* F,
+                              float* X, int Hp, int Wp, int s_prev, int s_next, int NF, int CX, int has_prev, void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_stage_trans")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_stage_trans")) return rc;
+    VFI_REQUIRE(Ppool && T && F && X && (NF == 1 || NF == 2) && pack_stride >= (int64_t)Hp * Wp * 4 * (1 + NF),
+                "vfi_test_rife_stage_trans: bad pack (NF %d, stride %lld)", NF, (long long)pack_stride);
+    VFI_REQUIRE(CX == round_up(12 + 8 * NF, 8), "vfi_test_rife_stage_trans: bad CX %d for %d feature planes", CX, NF);
+    return stage_trans_launch(Ppool, (size_t)pack_stride, tasks, B, T, F, X, Hp, Wp, s_prev, s_next, NF, has_prev != 0, (hipStream_t)stream);
+}
+
+int vfi_test_rife_stage_trans_x(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T, float* F,
+                                float* X, int Hp, int Wp, int s_prev, int s_next, int CX, int has_prev, void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_stage_trans_x")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_stage_trans_x")) return rc;
+    VFI_REQUIRE(Ppool && T && F && X && pack_stride >= (int64_t)Hp * Wp * 8, "vfi_test_rife_stage_trans_x: bad pack (stride %lld)", (long long)pack_stride);
+    VFI_REQUIRE(CX == 32, "vfi_test_rife_stage_trans_x: bad CX %d (one feature plane and 8 carried channels: 32)", CX);
+    return stage_trans_x_launch(Ppool, (size_t)pack_stride, tasks, B, T, F, X, Hp, Wp, s_prev, s_next, has_prev != 0, (hipStream_t)stream);
+}
+
+// conv0.0 of the last block as plain OIHW [32][20][3][3] + bias [32] on the HOST: packed here exactly as vfi_rife_create packs conv00[3]
+int vfi_test_rife_trans1_conv0a(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T,
+                                const float* Fin, float* Fout, const float* w_oihw_host, const float* bias_host, float* A0, int Hp, int Wp, float slope,
+                                void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_trans1_conv0a")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_trans1_conv0a")) return rc;
+    VFI_REQUIRE(Ppool && T && Fin && Fout && Fin != Fout && A0 && w_oihw_host && bias_host && pack_stride >= (int64_t)Hp * Wp * 8,
+                "vfi_test_rife_trans1_conv0a: bad operands (stride %lld)", (long long)pack_stride);
+    std::vector<float> wp, bp;
+    pack_conv3x3(w_oihw_host, bias_host, 32, 20, 24, 32, wp, bp);
+    DevBuf w, bias;
+    int rc = -1;
+    if (!upload(w, wp) && !upload(bias, bp)) {
+        rc = trans1_conv0a_launch(Ppool, (size_t)pack_stride, tasks, B, T, Fin, Fout, w.p, bias.p, A0, Hp, Wp, slope, (hipStream_t)stream);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == 0) {
+            set_error("vfi_test_rife_trans1_conv0a: the launch failed");
+            rc = -1;
+        }
+    }
+    w.release();
+    bias.release();
+    return rc;
+}
+
+int vfi_test_rife_final_blend(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T,
+                              const float* F, float* out, float* Fdbg, int H, int W, int Hp, int Wp, int s, int tp, void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_final_blend")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_final_blend")) return rc;
+    VFI_REQUIRE(Ppool && T && F && out && pack_stride >= (int64_t)Hp * Wp * 4, "vfi_test_rife_final_blend: bad operands (stride %lld)", (long long)pack_stride);
+    VFI_REQUIRE(H >= 1 && H <= Hp && W >= 1 && W <= Wp && stage_pow2(s, 1, 16) && (tp == 2 || tp == 4), "vfi_test_rife_final_blend: %dx%d in %dx%d, scale %d, %d planes",
+                H, W, Hp, Wp, s, tp);
+    return final_blend_launch(Ppool, (size_t)pack_stride, tasks, B, T, F, out, Fdbg, H, W, Hp, Wp, s, tp, (hipStream_t)stream);
+}
+
+int vfi_test_rife_planar4_up(const float* X1, float* X, int B, int Hp, int Wp, int u, int CX, int flow_plane, void* stream) {
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_planar4_up")) return rc;
+    VFI_REQUIRE(X1 && X && CX >= 4 && CX % 4 == 0 && flow_plane < CX / 4, "vfi_test_rife_planar4_up: %d channels, flow plane %d", CX, flow_plane);
+    return planar4_up_launch(X1, X, B, Hp, Wp, u, CX, flow_plane, (hipStream_t)stream);
+}
+
+int vfi_test_rife_t_down(const float* T, float* T1, int B, int Hp, int Wp, int u, int tp, void* stream) {
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_t_down")) return rc;
+    VFI_REQUIRE(T && T1 && (tp == 2 || tp == 4), "vfi_test_rife_t_down: %d planes", tp);
+    return t_down_launch(T, T1, B, Hp, Wp, u, tp, (hipStream_t)stream);
+}
 #endif  // VFI_TEST_TAPS
 
 int vfi_rife_work(vfi_rife_t* net, double* conv_flop_per_task, double* hbm_bytes_per_task) {

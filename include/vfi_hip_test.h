@@ -68,6 +68,39 @@ int vfi_test_last_conv_launch(int32_t* out, int cap);
 int64_t vfi_rife_debug_read(vfi_rife_t* net, int what, int stage, float* host_buf, int64_t cap);
 int vfi_rife_debug_keep(vfi_rife_t* net, int on);
 
+/* The RIFE stage kernels (csrc/rife_ops.hip), ONE launcher of csrc/rife_ops.h per call, unchanged, on the caller's device buffers:
+ * tests/test_gpu_rife_stage.py compares each with a float64 restatement of its own operation.  Layouts as in rife_ops.hip (frame pack
+ * planar4 [1 + NF][Hp][Wp][4] at Ppool + slot * pack_stride floats; F [B][Hp][Wp][4]; M [B][Hp][Wp]; X planar4 [B][CX/4][Hs][Ws][4];
+ * T planar4 [B][tp][Hs][Ws][4]).  The task table is three host arrays of B <= 32 entries.  Every call validates its arguments
+ * (B, Hp and Wp multiples of 64, scales, CX against NF, pack_stride against the pack) and returns -2 without a launch if one is bad;
+ * the launches are asynchronous on `stream` except vfi_test_rife_trans1_conv0a, which synchronises it. */
+int vfi_test_rife_stage_in(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* F,
+                           const float* M, const float* FEAT, float* X, int Hp, int Wp, int s, int CX, int NF, int has_flow, void* stream);
+/* Spool: per slot a staging image planar4 [2][Hp/8][Wp/8][4] at Spool + slot * stage_stride floats; X [B][4][Hp/8][Wp/8][4] */
+int vfi_test_rife_stage_in0_staged(const float* Spool, int64_t stage_stride, const int* slot0, const int* slot1, const float* t, int B, float* X, int Hp,
+                                   int Wp, void* stream);
+int vfi_test_rife_flow_up(const float* T, float* F, float* M, int B, int Hp, int Wp, int s, int tp, int has_prev, void* stream);
+/* T with 4 planes -> FEAT [B][2][Hp][Wp][4] */
+int vfi_test_rife_feat_up(const float* T, float* FEAT, int B, int Hp, int Wp, int s, void* stream);
+/* F is updated in place; CX = round_up(12 + 8 NF, 8) */
+int vfi_test_rife_stage_trans(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T, float* F,
+                              float* X, int Hp, int Wp, int s_prev, int s_next, int NF, int CX, int has_prev, void* stream);
+/* arch 4.26: T with 4 planes, CX = 32 */
+int vfi_test_rife_stage_trans_x(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T, float* F,
+                                float* X, int Hp, int Wp, int s_prev, int s_next, int CX, int has_prev, void* stream);
+/* The last transition fused into conv0.0 of the last block.  w_oihw_host [32][20][3][3] and bias_host [32] are plain HOST tensors: the
+ * call packs them with the routine vfi_rife_create uses for that layer.  Fout must differ from Fin; A0 [B][Hp/2][Wp/2][32]. */
+int vfi_test_rife_trans1_conv0a(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T,
+                                const float* Fin, float* Fout, const float* w_oihw_host, const float* bias_host, float* A0, int Hp, int Wp, float slope,
+                                void* stream);
+/* out [B][H][W][3]; Fdbg (nullable) [B][Hp][Wp][4] receives the final flow inside H x W */
+int vfi_test_rife_final_blend(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T,
+                              const float* F, float* out, float* Fdbg, int H, int W, int Hp, int Wp, int s, int tp, void* stream);
+/* X1 [B][CX/4][Hp][Wp][4] -> X [B][CX/4][u Hp][u Wp][4], plane flow_plane (or none: -1) times u */
+int vfi_test_rife_planar4_up(const float* X1, float* X, int B, int Hp, int Wp, int u, int CX, int flow_plane, void* stream);
+/* T [B][tp][u Hp][u Wp][4] -> T1 [B][tp][Hp][Wp][4], plane 0 divided by u */
+int vfi_test_rife_t_down(const float* T, float* T1, int B, int Hp, int Wp, int u, int tp, void* stream);
+
 
 /* The call order of FILM's greedy bisection for `inter_frames` new frames (film/__init__.py:17-40) as the C side computes it:
  * (left, right, new) grid positions, 3 ints per call; returns the number of calls or < 0.  Host only. */

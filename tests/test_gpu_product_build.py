@@ -19,7 +19,8 @@ import torch
 from cfi_amd import _lib, synth
 lib = _lib.load()
 assert not _lib.is_test_build()
-for tap in ("vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_conv_algo", "vfi_rife_debug_read", "vfi_m2m_debug_read"):
+for tap in ("vfi_test_set_option", "vfi_test_variant_override", "vfi_test_last_conv_launch", "vfi_test_conv_algo", "vfi_rife_debug_read", "vfi_m2m_debug_read",
+            "vfi_test_rife_stage_in", "vfi_test_rife_stage_in0_staged", "vfi_test_rife_flow_up", "vfi_test_rife_feat_up", "vfi_test_rife_stage_trans", "vfi_test_rife_stage_trans_x", "vfi_test_rife_trans1_conv0a", "vfi_test_rife_final_blend", "vfi_test_rife_planar4_up", "vfi_test_rife_t_down"):
     assert not hasattr(lib, tap), tap
 loaded = [l.split()[-1] for l in open("/proc/self/maps") if "libvfi_hip" in l]
 assert loaded and all(p.endswith("libvfi_hip.so") for p in loaded), loaded
