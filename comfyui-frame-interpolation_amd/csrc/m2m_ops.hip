@@ -460,6 +460,10 @@ __device__ static inline void splat_far_pass(const float* __restrict__ in, const
         const float fx = (float)x + f.x, fy = (float)y + f.y;
         if (!isfinite(fx) || !isfinite(fy)) continue;
         if (!(fmaxf(fabsf(f.x), fabsf(f.y)) > (float)(SPLAT_RCAP - 1))) continue;
+        // no target inside the image.  Tested in float BEFORE the conversion: a target beyond the int range (a flow of 1e30) has no defined
+        // int value, and the x0 + 1 / y0 + 1 of the bounds checks below would overflow
+        const float x0f = floorf(fx), y0f = floorf(fy);
+        if (!(x0f >= -1.0f && x0f <= (float)(W - 1) && y0f >= -1.0f && y0f <= (float)(H - 1))) continue;
         int x0, y0;
         float w[4];
         splat_weights(fx, fy, x0, y0, w);

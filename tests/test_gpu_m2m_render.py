@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from gpu_util import describe_diff, ptr
+from m2m_restated import tile_ranges
 from cfi_amd import synth
 from oracle import m2m_oracle as M
 
@@ -28,26 +29,6 @@ def _ck(rc, what):
     from cfi_amd import _lib
 
     _lib.check(rc, what)
-
-
-def tile_ranges(tf):
-    """tf [8,H,W,2] (numpy) -> ([8,tiles,4], [8]) as vfi_m2m_photo_tiles defines them."""
-    _, H, W, _ = tf.shape
-    ty, tx = -(-H // 32), -(-W // 32)
-    out = np.empty((8, ty * tx, 4), np.float32)
-    smax = np.zeros(8, np.float32)
-    for s in range(8):
-        for j in range(ty):
-            for i in range(tx):
-                blk = tf[s, 32 * j:32 * j + 32, 32 * i:32 * i + 32].reshape(-1, 2)
-                ok = np.isfinite(blk).all(axis=1)
-                if ok.any():
-                    b = blk[ok]
-                    out[s, j * tx + i] = (b[:, 0].min(), b[:, 0].max(), b[:, 1].min(), b[:, 1].max())
-                    smax[s] = max(smax[s], np.abs(b).max())
-                else:
-                    out[s, j * tx + i] = (3e38, -3e38, 3e38, -3e38)
-    return out, smax
 
 
 def three_step(lib, d0, tf, e, stats, t, H, W):
