@@ -361,7 +361,14 @@ static int attention_launch_t(const AttArgs& a_in, hipStream_t s) {
     }
     const int wgs = cdiv(a.Lq, 128) * a.nb, nblk = cdiv(a.Lk, ATT_KB);
     int ks = 1;
-    if (wgs < cus_of[dev] && nblk >= 16) {
+    if (const long forced = option(kOptAttKsplit); forced > 0) {      // tests: a chosen number of key ranges, whatever the device (default 0)
+        ks = forced > 8 ? 8 : (int)forced;
+        ks = ks > nblk ? nblk : ks;
+        if (ks > 1) {
+            const int per = cdiv(nblk, ks);
+            ks = cdiv(nblk, per);          // no empty range
+        }
+    } else if (wgs < cus_of[dev] && nblk >= 16) {
         ks = (DVT == 4 ? 1 : 2) * cus_of[dev] / wgs;      // (the 2-channel form fits two workgroups per CU)
         ks = ks > nblk / 8 ? nblk / 8 : ks;
         ks = ks > 8 ? 8 : ks;

@@ -78,6 +78,7 @@ enum Option {
     kOptSepconvSplitHeads,  // 1: SepConv++'s four head first-convs as four 64 -> 64 layers, each reading up2(row1) (default 0: one 64 -> 256 layer)
     kOptSepconvPlanar,      // 1: SepConv++'s heads transposed to planar before the output stage (default), 0: the output stage reads them NHWC
     kOptStage0,             // 1: RIFE block 0's input assembled from the per-frame staging images the frame pack kernels write (default), 0: gathered from the packs per pair
+    kOptAttKsplit,          // 1..8: the number of key ranges attention_launch_t asks for (attention.hip; reduced so that no range is empty), default 0: chosen from the device's CU count
     kOptCount
 };
 long option(Option o);
