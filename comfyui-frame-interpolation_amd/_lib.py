@@ -285,6 +285,11 @@ PROTOTYPES = {
 }
 
 TEST_PROTOTYPES = {k: PROTOTYPES.pop(k) for k in TEST_NAMES}
+# ... and include/vfi_hip_test_wino.h (the dead-plane table of the Winograd kernel's transposed-convolution forms): test builds only
+WINO_TEST_PROTOTYPES = {
+    "vfi_test_wino_dead_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int]),
+    "vfi_test_deconv_wino_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p]),
+}
 
 
 # The runtime variables this package honours — all of them select resources or diagnostics, none changes a frame's values
@@ -335,6 +340,7 @@ def load():
     protos = dict(PROTOTYPES)
     if _test_build:
         protos.update(TEST_PROTOTYPES)
+        protos.update(WINO_TEST_PROTOTYPES)
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

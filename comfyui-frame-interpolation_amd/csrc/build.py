@@ -46,6 +46,7 @@ def _digest():
     files = _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.abspath(__file__)]
     files.append(os.path.join(PKG, "..", "include", "vfi_hip.h"))
     files.append(os.path.join(PKG, "..", "include", "vfi_hip_test.h"))
+    files.append(os.path.join(PKG, "..", "include", "vfi_hip_test_wino.h"))
     for f in files:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode())  # names only: the checkout path differs on the GPU box

@@ -5,6 +5,7 @@
 
 #include "../../include/vfi_hip.h"
 #include "../../include/vfi_hip_test.h"
+#include "../../include/vfi_hip_test_wino.h"
 #include "rife_ops.h"
 
 using namespace vfi;
@@ -140,6 +141,31 @@ int64_t vfi_test_pack_deconv3x3(const float* weight_host, const float* bias_host
     return (int64_t)w3.size();
 }
 
+int vfi_test_wino_dead_forms(const float* w3_host, int Cout, int Cin, int Cin_p, int* forms_out, int cap) {
+    VFI_REQUIRE(w3_host && forms_out && Cout > 0 && Cin > 0 && Cin_p % 8 == 0 && Cin_p >= Cin, "vfi_test_wino_dead_forms: bad arguments");
+    const int cp = round_up(Cout, 32);
+    VFI_REQUIRE(cap >= cp / 32, "vfi_test_wino_dead_forms: %d forms do not fit", cp / 32);
+    std::vector<float> wp;
+    std::vector<int> forms;
+    pack_wino3x3(w3_host, Cout, Cin, nullptr, Cin_p, cp, wp);
+    wino_dead_forms(wp.data(), Cin_p, cp, forms);
+    memcpy(forms_out, forms.data(), forms.size() * sizeof(int));
+    return (int)forms.size();
+}
+
+int vfi_test_deconv_wino_plan(const float* weight_host, int Cin, int LO, int* forms_out, int cap, int* gray_out, int* order_out) {
+    VFI_REQUIRE(weight_host && forms_out && gray_out && Cin > 0 && Cin % 8 == 0 && LO > 0 && 4 * LO <= 1024, "vfi_test_deconv_wino_plan: bad arguments");
+    WinoDeconvPack dp;
+    pack_deconv_wino(weight_host, nullptr, nullptr, Cin, LO, nullptr, Cin, dp);
+    const int NY = dp.Cout3_p / 32;
+    VFI_REQUIRE(cap >= NY, "vfi_test_deconv_wino_plan: %d forms do not fit", NY);
+    for (int nb = 0; nb < NY; ++nb) forms_out[nb] = (int)(dp.dead[nb >> 3] >> ((nb & 7) * 4)) & 15;      // as the kernel reads them
+    *gray_out = dp.gray;
+    if (order_out)
+        for (int co = 0; co < 4 * LO; ++co) order_out[co] = dp.gray ? wino_gray_order(co, LO) : co;
+    return NY;
+}
+
 int vfi_conv3x3_naive(const float* in_dev, const float* weight_host, const float* bias_host, const float* beta_host,
                       float* out_dev, int N, int H, int W, int Cin, int Cout, int stride, int act, float slope,
                       void* stream) {
@@ -166,19 +192,16 @@ int vfi_conv3x3_naive(const float* in_dev, const float* weight_host, const float
 int vfi_deconv4x4_ps2(const float* in_dev, const float* weight_host, const float* bias_host, float* out_dev, int N,
                       int H, int W, int Cin, int Cout, void* stream) {
     VFI_REQUIRE(in_dev && weight_host && out_dev, "vfi_deconv4x4_ps2: bad arguments");
-    VFI_REQUIRE(Cin % 16 == 0 && Cout % 4 == 0 && Cout <= 32, "vfi_deconv4x4_ps2: Cin=%d (x16) Cout=%d (x4, <=32)", Cin,
-                Cout);
+    // the Winograd form takes 8-channel chunks, the grouped direct kernel 16-channel ones
+    const bool wino = option(kOptDeconvWino) && conv_wino_mode(-1) != 1 && option(kOptGroupedVariant) < 0;
+    VFI_REQUIRE(Cin % (wino ? 8 : 16) == 0 && Cout % 4 == 0 && Cout <= 32, "vfi_deconv4x4_ps2: Cin=%d (x%d) Cout=%d (x4, <=32)", Cin, wino ? 8 : 16, Cout);
     hipStream_t st = (hipStream_t)stream;
-    std::vector<float> wp, bp;
-    pack_deconv4x4(weight_host, bias_host, Cin, Cout, Cin, 32, wp, bp);
     Tmp dw, db, T;
-    if (dw.put(wp) || db.put(bp) || T.alloc((size_t)N * H * W * 128)) return -1;  // planar4 [N][2][4H][4W][4]
+    if (T.alloc((size_t)N * H * W * 128)) return -1;  // planar4 [N][2][4H][4W][4]
     VFI_CHECK_HIP(hipMemsetAsync(T.p, 0, (size_t)N * H * W * 128 * sizeof(float), st));
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in_dev;
-    a.w = dw.p;
-    a.bias = db.p;
     a.out = T.p;
     a.N = N;
     a.Hin = a.Hout = H;
@@ -190,21 +213,24 @@ int vfi_deconv4x4_ps2(const float* in_dev, const float* weight_host, const float
     a.Cout = Cout;
     a.out_mode = 1;
     Tmp dw3, db3;
-    if (option(kOptDeconvWino) && conv_wino_mode(-1) != 1 && option(kOptGroupedVariant) < 0 && Cin % 8 == 0) {
+    if (wino) {
         // the form the RIFE network uses: one 3x3 layer with 4 * Cout channels on the Winograd kernel, pixel-shuffle epilogue
-        std::vector<float> w3, b3, wq;
-        pack_deconv_as_conv3x3(weight_host, bias_host, Cin, Cout, w3, b3);
-        const int cp = round_up(4 * Cout, 32);
-        pack_wino3x3(w3.data(), 4 * Cout, Cin, nullptr, Cin, cp, wq);
-        b3.resize(cp, 0.f);
-        if (dw3.put(wq) || db3.put(b3)) return -1;
+        WinoDeconvPack dp;
+        pack_deconv_wino(weight_host, bias_host, nullptr, Cin, Cout, nullptr, Cin, dp);
+        if (dw3.put(dp.ww) || db3.put(dp.bias3)) return -1;
         conv3x3_taps(a);
         a.w = dw3.p;
         a.bias = db3.p;
         a.Cout = 4 * Cout;
-        a.Cout_p = cp;
+        a.Cout_p = dp.Cout3_p;
+        dp.apply(a);
         if (conv_wino_launch(a, 8, st, "deconv4x4_wino")) return -1;
     } else {
+        std::vector<float> wp, bp;
+        pack_deconv4x4(weight_host, bias_host, Cin, Cout, Cin, 32, wp, bp);
+        if (dw.put(wp) || db.put(bp)) return -1;
+        a.w = dw.p;
+        a.bias = db.p;
         deconv4x4_taps(a);
         if (conv_launch(a, 1, true, -1, st, nullptr)) return -1;
     }

@@ -55,6 +55,7 @@ struct WinoArgs {
     float inv_NY, inv_per, inv_rx;   // 1 / NY, 1 / (rx * ry), 1 / rx: the work decode divides by multiplication (see wino_div)
     int LO;                          // SHUF epilogue: channels per parity group (Cout / 4) and
     float inv_LO;                    //   its reciprocal (an integer division in the epilogue keeps a hoisted reciprocal alive — spilled — through the K loop)
+    int gray;                        // SHUF epilogue: 1 = the parity groups are packed in the order p00 p01 p11 p10 (ConvArgs::wino_gray)
     int clk_tag;                     // clock probe: the host's index of this launch (read at the kernel's first instructions only)
 };
 
@@ -150,7 +151,8 @@ __device__ __forceinline__ f32x2 wino_pk_mul(f32x2 x, f32x2 y) {
 // FULL: the region lies completely inside the image (wave-uniform, true for all but the last row / column of regions): no
 // row branches and no per-store column test (they were ~260 of the epilogue's 1350 instructions).
 // SHUF != 0: the layer is a ConvTranspose2d(4, 2, 1) written as a 3x3 convolution — output channel co = parity group g x LO + cg
-// (pack_deconv_as_conv3x3) — and the epilogue puts the parities where they belong:
+// (pack_deconv_as_conv3x3; with `gray` the groups sit at the N positions p00 p01 p11 p10, pack_deconv_wino, and g is decoded from the position) —
+// and the epilogue puts the parities where they belong:
 //   1 (ConvArgs::out_mode 1, RIFE lastconv): + PixelShuffle(2) into the planar4 block output T [n][planes][4H][4W][4]: pixel
 //     (4 oy + 2 (g >> 1) + ((cg >> 1) & 1), 4 ox + 2 (g & 1) + (cg & 1)), plane (cg >> 2) >> 2, component (cg >> 2) & 3 — the mapping
 //     of conv_mfma2's out_mode 1 epilogue;
@@ -158,7 +160,7 @@ __device__ __forceinline__ f32x2 wino_pk_mul(f32x2 x, f32x2 y) {
 //     channel cg.  No residual in either form.
 template <int RTX, int MODE, bool FULL = false, int SHUF = 0>
 __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const ConvArgs& a, int n, int oy0, int ox0, int co, int coc, int half, float bs,
-                                              float bt, float pre, int LO = 0, float inv_LO = 0.f) {
+                                              float bt, float pre, int LO = 0, float inv_LO = 0.f, int gray = 0) {
     const int H = a.Hin, W = a.Win;
     const float uslope = a.act == 1 ? a.slope : 1.0f;
     const float ps = a.post_scale != 0.f ? a.post_scale : 1.0f, sh = a.post_scale != 0.f ? a.post_shift : 0.0f;
@@ -181,13 +183,23 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
         int g = (int)((float)co * inv_LO), cg = co - g * LO;      // co / LO by multiplication + one fix-up (0 <= co < 2^10)
         if (cg < 0) --g, cg += LO;
         if (cg >= LO) ++g, cg -= LO;
+        g ^= (g >> 1) & gray;      // gray = 1: the groups sit in the order p00 p01 p11 p10 (wino_gray_order); N position -> parity 2 py + px
         const int c = cg >> 2;
         if (SHUF == 1) lane_o = ((((c >> 2) * 4 * H + 2 * (g >> 1) + ((cg >> 1) & 1)) * Ws4 + 2 * (g & 1) + (cg & 1) + 4 * xlane) * 4 + (c & 3)) * 4;
         else lane_o = (((g >> 1) * 2 * W + (g & 1) + 2 * xlane) * a.out_cs + cg) * 4;
     }
     // Two tiles (accumulator registers r, r + 1 = neighbours in x) per step, in packed fp32: the epilogue's VALU work is not hidden by
     // anything (the wave's MFMAs are over), v_pk_* does two values per instruction in the same order of operations as the scalar form.
-    const f32x2 bsbt = {bs, bt}, sl2 = {MODE == 1 ? pre : uslope, MODE == 1 ? pre : uslope};
+    // SHUF: the slope pair is made here, per epilogue, from a SCALAR.  It is a kernel constant, and with one K loop per dead-plane form between
+    // the kernel's start and this point hipcc hoisted the VGPR pair there and SPILLED it — up to 20 scratch reloads per partial-region epilogue
+    float usl = uslope;
+    if (SHUF != 0 && MODE == 0) {
+        int ub = a.act == 1 ? __float_as_int(a.slope) : 0x3f800000;      // uslope's bits, selected on the scalar unit
+        asm volatile("" : "+s"(ub));
+        usl = __int_as_float(ub);
+    }
+    const float sl = MODE == 1 ? pre : usl;
+    const f32x2 bsbt = {bs, bt}, sl2 = {sl, sl};
 #pragma unroll
     for (int rp = 0; rp < 8; ++rp) {
         const int r = 2 * rp;
@@ -377,10 +389,11 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
 #pragma unroll
         for (int dy = 0; dy < 4; ++dy) read_patch_row(dy);
     };
-    auto read_b = [&](int buf, int j, f32x4(&B)[4]) {
+    auto read_b = [&](int buf, int j, f32x4(&B)[4], int dr = -1) {      // dr: the dead row of the item's form (its fragment is not read)
         const char* sB = (const char*)(smem + buf * G::BUF_FLOATS + 4 * G::A_FLOATS) + lane16;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) B[q] = *(const f32x4*)(sB + (j * 4 + q) * 1024);
+        for (int q = 0; q < 4; ++q)
+            if (q != dr) B[q] = *(const f32x4*)(sB + (j * 4 + q) * 1024);
     };
 
     // ---- per-channel epilogue constants in LDS (bias | beta | PReLU slope, padded channels: 0 | 1 | 0).  A global load in the
@@ -487,30 +500,37 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
         };
         auto pk_add = [](f32x2 x, f32x2 y) { return wino_pk_add(x, y); };
         auto pk_sub = [](f32x2 x, f32x2 y) { return wino_pk_sub(x, y); };
-        auto tf1 = [&](int hi) {       // rows: t = B^T d, for the channel pair (0,1) (hi = 0) or (2,3) (hi = 1)
+        // dr / dc: the dead row / column of the item's form (-1 = none): what only that row / column of V needs is not computed
+        auto tf1 = [&](int hi, int dr = -1, int dc = -1) {       // rows: t = B^T d, for the channel pair (0,1) (hi = 0) or (2,3) (hi = 1)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
+                if (c == dc) continue;
                 const f32x2 d0 = hi ? P[c].hi : P[c].lo, d1 = hi ? P[4 + c].hi : P[4 + c].lo, d2 = hi ? P[8 + c].hi : P[8 + c].lo,
                             d3 = hi ? P[12 + c].hi : P[12 + c].lo;
-                t2[c] = pk_sub(d0, d2);
+                if (dr != 0) t2[c] = pk_sub(d0, d2);
                 t2[4 + c] = pk_add(d1, d2);
                 t2[8 + c] = pk_sub(d2, d1);
-                t2[12 + c] = pk_sub(d1, d3);
+                if (dr != 3) t2[12 + c] = pk_sub(d1, d3);
             }
         };
-        auto tf2 = [&](f32x2(&V)[16]) {       // columns: V = t B
+        auto tf2 = [&](f32x2(&V)[16], int dr = -1, int dc = -1) {       // columns: V = t B
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                V[r * 4 + 0] = pk_sub(t2[r * 4], t2[r * 4 + 2]);
+                if (r == dr) continue;
+                if (dc != 0) V[r * 4 + 0] = pk_sub(t2[r * 4], t2[r * 4 + 2]);
                 V[r * 4 + 1] = pk_add(t2[r * 4 + 1], t2[r * 4 + 2]);
                 V[r * 4 + 2] = pk_sub(t2[r * 4 + 2], t2[r * 4 + 1]);
-                V[r * 4 + 3] = pk_sub(t2[r * 4 + 1], t2[r * 4 + 3]);
+                if (dc != 3) V[r * 4 + 3] = pk_sub(t2[r * 4 + 1], t2[r * 4 + 3]);
             }
         };
+        // the MFMAs of plane row G_ (xi = 4 G_ + e_); DR / DC: the K loop form's dead row / column, whose planes are not multiplied
 #define WINO_MF4(G_, V_, C_, B_)                                                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                                                  \
-    _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_)                                                                    \
-        acc[(G_) * 4 + e_] = __builtin_amdgcn_mfma_f32_32x32x2f32(V_[(G_) * 4 + e_].C_, B_[G_][e_], acc[(G_) * 4 + e_], 0, 0, 0);
+    if ((G_) != DR) {                                                                                                   \
+        _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_)                                                                \
+            if (e_ != DC)                                                                                               \
+                acc[(G_) * 4 + e_] = __builtin_amdgcn_mfma_f32_32x32x2f32(V_[(G_) * 4 + e_].C_, B_[G_][e_], acc[(G_) * 4 + e_], 0, 0, 0); \
+    }
 #define WINO_A(I_) if ((I_) < NA) issue_a(drsrc, (I_), avp[(I_) < NA ? (I_) : 0], d_k, buf)
 #define WINO_B(I_) issue_b(dwrsrc, (I_), dcur.nb, d_k, buf)
         // PROBE: sums of stamps (see g_wino_probe_out).  1: q0 / q1 = before / after sub-step 1's vmcnt wait.  2: q0 / q1 = before sub-step 3's
@@ -523,6 +543,86 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
         V_ = __builtin_amdgcn_s_memtime();                       \
         __builtin_amdgcn_sched_barrier(0);                       \
     }
+        // The K loop of one item in the form (DR_, DC_) of the item's N block (wino_dead_forms): the dead plane row / column of the block's
+        // weights, -1 = none.  One straight-line loop per form — a branch inside the tuned sub-steps makes hipcc split the accumulator
+        // tuples (docs/design/winograd.md 4) — and a macro, not a lambda: behind a by-reference capture the instantiations that have
+        // one form only (all but SHUF) came out scheduled differently from what they were.  A dead plane's accumulators stay the +0
+        // they were cleared to, which is what fma(x, +-0, +0) gives for every finite x: the epilogue adds them as before, same bits.
+#define WINO_KLOOP(DR_, DC_)                                                                                                                     \
+        {                                                                                                                                        \
+            constexpr int DR = (DR_), DC = (DC_);                                                                                                \
+            for (int k = 0; k < C8; ++k, ++gchunk) {                                                                                             \
+                const int buf = (int)(gchunk % G::NBUF), nbuf = buf == G::NBUF - 1 ? 0 : buf + 1;                                                \
+                /* ---- sub-step 0 */                                                                                                            \
+                WINO_STAMP(PROBE == 4, sa);                                                                                                      \
+                WINO_MF4(0, VA, x, Be);                                                                                                          \
+                read_b(buf, 1, Bo, DR);                                                                                                          \
+                load_avoff(avp);                                                                                                                 \
+                WINO_MF4(1, VA, x, Be);                                                                                                          \
+                tf1(1, DR, DC);                                                                                                                  \
+                WINO_MF4(2, VA, x, Be);                                                                                                          \
+                tf2(VB, DR, DC);                                                                                                                 \
+                WINO_MF4(3, VA, x, Be);                                                                                                          \
+                WINO_A(0); WINO_A(1);                                                                                                            \
+                pk_bases(nbuf);                                                                                                                  \
+                /* ---- sub-step 1 */                                                                                                            \
+                __builtin_amdgcn_sched_barrier(0);                                                                                               \
+                WINO_STAMP(PROBE == 1, sa);                                                                                                      \
+                WINO_STAMP(PROBE == 4, sb);                                                                                                      \
+                __builtin_amdgcn_s_waitcnt(wino_waitcnt(W1, 15));                                                                                \
+                WINO_STAMP(PROBE == 1, sb);                                                                                                      \
+                WINO_MF4(0, VA, y, Bo);                                                                                                          \
+                read_b(buf, 2, Be, DR);                                                                                                          \
+                read_patch_row(0);                                                                                                               \
+                WINO_MF4(1, VA, y, Bo);                                                                                                          \
+                read_patch_row(1);                                                                                                               \
+                WINO_A(2);                                                                                                                       \
+                WINO_MF4(2, VA, y, Bo);                                                                                                          \
+                read_patch_row(2);                                                                                                               \
+                WINO_A(3);                                                                                                                       \
+                WINO_MF4(3, VA, y, Bo);                                                                                                          \
+                read_patch_row(3);                                                                                                               \
+                WINO_A(4);                                                                                                                       \
+                /* ---- sub-step 2 */                                                                                                            \
+                WINO_STAMP(PROBE == 4, sc);                                                                                                      \
+                WINO_MF4(0, VB, x, Be);                                                                                                          \
+                read_b(buf, 3, Bo, DR);                                                                                                          \
+                WINO_A(5);                                                                                                                       \
+                WINO_MF4(1, VB, x, Be);                                                                                                          \
+                tf1(0, DR, DC);                                                                                                                  \
+                WINO_MF4(2, VB, x, Be);                                                                                                          \
+                tf2(VA, DR, DC);                                                                                                                 \
+                WINO_MF4(3, VB, x, Be);                                                                                                          \
+                WINO_A(6);                                                                                                                       \
+                /* ---- sub-step 3 */                                                                                                            \
+                __builtin_amdgcn_sched_barrier(0);                                                                                               \
+                if (PROBE == 2) { q1 += (unsigned)sb; }      /* the previous chunk's "after the barrier" (0 before the first: sb starts at 0) */ \
+                WINO_STAMP(PROBE == 2, sa);                                                                                                      \
+                WINO_STAMP(PROBE == 4, sd);                                                                                                      \
+                __builtin_amdgcn_s_waitcnt(wino_waitcnt(W3, 0));                                                                                 \
+                __builtin_amdgcn_s_barrier();                                                                                                    \
+                if (PROBE == 1) { q0 += (unsigned)sa; q1 += (unsigned)sb; ++qn; }                                                                \
+                if (PROBE == 2) { q0 += (unsigned)sa; ++qn; }                                                                                    \
+                if (PROBE == 4) { q0 += (unsigned)sa; q1 += (unsigned)sb; q2 += (unsigned)sc; q3 += (unsigned)sd; ++qn; }                        \
+                WINO_STAMP(PROBE == 2, sb);                                                                                                      \
+                WINO_MF4(0, VB, y, Bo);                                                                                                          \
+                read_b(nbuf, 0, Be, DR);                                                                                                         \
+                WINO_B(0);                                                                                                                       \
+                WINO_MF4(1, VB, y, Bo);                                                                                                          \
+                WINO_B(1);                                                                                                                       \
+                WINO_MF4(2, VB, y, Bo);                                                                                                          \
+                WINO_B(2);                                                                                                                       \
+                WINO_MF4(3, VB, y, Bo);                                                                                                          \
+                WINO_B(3);                                                                                                                       \
+                __builtin_amdgcn_sched_barrier(0);                                                                                               \
+                /* the next chunk's operands are consumed HERE: LLVM's code sinking otherwise moves their computation below the */               \
+                /* cursor-advance branch that follows, out from under the MFMAs */                                                               \
+                _Pragma("unroll")                                                                                                                \
+                for (int i = 0; i < 16; ++i)                                                                                                     \
+                    if ((i >> 2) != DR && (i & 3) != DC) asm volatile("" : "+v"(VA[i]));                                                         \
+                dma_advance();                                                                                                                   \
+            }                                                                                                                                    \
+        }
         unsigned gchunk = 0;                 // chunk counter of this workgroup's stream: LDS buffer = gchunk % 3
         for (int it = 0; item(it, ccur); ++it) {
             WINO_STAMP(PROBE == 3, sa);
@@ -540,75 +640,18 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
             tf1(0);
             tf2(VA);
             WINO_STAMP(PROBE == 3, sb);
-            for (int k = 0; k < C8; ++k, ++gchunk) {
-                const int buf = (int)(gchunk % G::NBUF), nbuf = buf == G::NBUF - 1 ? 0 : buf + 1;
-                // ---- sub-step 0
-                WINO_STAMP(PROBE == 4, sa);
-                WINO_MF4(0, VA, x, Be);
-                read_b(buf, 1, Bo);
-                load_avoff(avp);
-                WINO_MF4(1, VA, x, Be);
-                tf1(1);
-                WINO_MF4(2, VA, x, Be);
-                tf2(VB);
-                WINO_MF4(3, VA, x, Be);
-                WINO_A(0); WINO_A(1);
-                pk_bases(nbuf);
-                // ---- sub-step 1
-                __builtin_amdgcn_sched_barrier(0);
-                WINO_STAMP(PROBE == 1, sa);
-                WINO_STAMP(PROBE == 4, sb);
-                __builtin_amdgcn_s_waitcnt(wino_waitcnt(W1, 15));
-                WINO_STAMP(PROBE == 1, sb);
-                WINO_MF4(0, VA, y, Bo);
-                read_b(buf, 2, Be);
-                read_patch_row(0);
-                WINO_MF4(1, VA, y, Bo);
-                read_patch_row(1);
-                WINO_A(2);
-                WINO_MF4(2, VA, y, Bo);
-                read_patch_row(2);
-                WINO_A(3);
-                WINO_MF4(3, VA, y, Bo);
-                read_patch_row(3);
-                WINO_A(4);
-                // ---- sub-step 2
-                WINO_STAMP(PROBE == 4, sc);
-                WINO_MF4(0, VB, x, Be);
-                read_b(buf, 3, Bo);
-                WINO_A(5);
-                WINO_MF4(1, VB, x, Be);
-                tf1(0);
-                WINO_MF4(2, VB, x, Be);
-                tf2(VA);
-                WINO_MF4(3, VB, x, Be);
-                WINO_A(6);
-                // ---- sub-step 3
-                __builtin_amdgcn_sched_barrier(0);
-                if (PROBE == 2) { q1 += (unsigned)sb; }      // the previous chunk's "after the barrier" (0 before the first: sb starts at 0)
-                WINO_STAMP(PROBE == 2, sa);
-                WINO_STAMP(PROBE == 4, sd);
-                __builtin_amdgcn_s_waitcnt(wino_waitcnt(W3, 0));
-                __builtin_amdgcn_s_barrier();
-                if (PROBE == 1) { q0 += (unsigned)sa; q1 += (unsigned)sb; ++qn; }
-                if (PROBE == 2) { q0 += (unsigned)sa; ++qn; }
-                if (PROBE == 4) { q0 += (unsigned)sa; q1 += (unsigned)sb; q2 += (unsigned)sc; q3 += (unsigned)sd; ++qn; }
-                WINO_STAMP(PROBE == 2, sb);
-                WINO_MF4(0, VB, y, Bo);
-                read_b(nbuf, 0, Be);
-                WINO_B(0);
-                WINO_MF4(1, VB, y, Bo);
-                WINO_B(1);
-                WINO_MF4(2, VB, y, Bo);
-                WINO_B(2);
-                WINO_MF4(3, VB, y, Bo);
-                WINO_B(3);
-                __builtin_amdgcn_sched_barrier(0);
-                // the next chunk's operands are consumed HERE: LLVM's code sinking otherwise moves their computation below the
-                // cursor-advance branch that follows, out from under the MFMAs
-#pragma unroll
-                for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(VA[i]));
-                dma_advance();
+            // the form of this item's N block: 4 bits per block, 8 blocks per word (ConvArgs::wino_dead; all 0 outside the SHUF kernels)
+            const int form = SHUF != 0 ? __builtin_amdgcn_readfirstlane((int)(a.wino_dead[ccur.nb >> 3] >> ((ccur.nb & 7) * 4)) & 7) : 0;
+            if (SHUF == 0) {
+                WINO_KLOOP(-1, -1)
+            } else {
+                switch (form) {
+                    case kWinoDeadRow0: WINO_KLOOP(0, -1) break;
+                    case kWinoDeadRow3: WINO_KLOOP(3, -1) break;
+                    case kWinoDeadCol0: WINO_KLOOP(-1, 0) break;
+                    case kWinoDeadCol3: WINO_KLOOP(-1, 3) break;
+                    default: WINO_KLOOP(-1, -1) break;
+                }
             }
         // ---- epilogue: Y = A^T M A per tile in registers, + bias, * beta, (+ residual), activation, NHWC store
             WINO_STAMP(PROBE == 3, sc);
@@ -618,9 +661,9 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
                 const int co = ccur.nb * 32 + (ole & 31);
                 const int coc = co < a.Cout ? co : a.Cout - 1;
                 if (ccur.Ry0 + RH <= H && ccur.Rx0 + RW <= W)
-                    wino_epilogue<RTX, MODE, true, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO);
+                    wino_epilogue<RTX, MODE, true, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
                 else
-                    wino_epilogue<RTX, MODE, false, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO);
+                    wino_epilogue<RTX, MODE, false, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
             }
             if (PROBE == 3) {
                 WINO_STAMP(true, sd);
@@ -636,6 +679,7 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
                 g_wino_probe_out[wave][l] = v;
             }
         }
+#undef WINO_KLOOP
 #undef WINO_STAMP
 #undef WINO_MF4
 #undef WINO_A
@@ -711,9 +755,12 @@ void pack_wino3x3(const float* w_oihw, int Cout, int Cin, const int* chan_map, i
 // the transposed convolution reads the 2x2 input neighbourhood rows {y + py - 1, y + py} x columns {x + px - 1, x + px} with kernel
 // taps ky = 3 - py - 2a, kx = 3 - px - 2b (pack_deconv4x4) — four of the nine taps of a 3x3 window centred on (y, x).
 // w_iohw [Cin][LO][4][4] -> w3 OIHW [4 * LO][Cin][3][3] with channel g * LO + co, g = 2 py + px; bias repeated per parity.
-// No multiplication is saved against the four 2x2 parity convolutions (5 of 9 taps are zero and Winograd's 16 products per 2x2
-// tile equal the 4 x 4 direct ones) — what is saved is the padding of LO = 24 to a 32-wide MFMA N tile (4 x 24 = 96 = 3 x 32
-// exactly) and the layer runs on the tuned Winograd kernel instead of the grouped direct one.
+// In the spatial domain no multiplication is saved against the four 2x2 parity convolutions (5 of 9 taps are zero and Winograd's 16
+// products per 2x2 tile equal the 4 x 4 direct ones) — what is saved is the padding of LO = 24 to a 32-wide MFMA N tile (4 x 24 =
+// 96 = 3 x 32 exactly) and the layer runs on the tuned Winograd kernel instead of the grouped direct one.  In the Winograd domain
+// the zero taps DO show: parity (py, px) has taps in rows {py, py + 1} and columns {px, px + 1} only, so U = G g G^T has plane row
+// 3 (py = 0) or 0 (py = 1) and plane column 3 (px = 0) or 0 (px = 1) exactly zero — 9 live planes of 16.  wino_dead_forms finds
+// them in the packed image and the SHUF kernels skip the row or column a whole N block shares (docs/design/winograd.md 8).
 void pack_deconv_as_conv3x3(const float* w_iohw, const float* bias, int Cin, int LO, std::vector<float>& w3, std::vector<float>& b3) {
     w3.assign((size_t)4 * LO * Cin * 9, 0.f);
     b3.assign((size_t)4 * LO, 0.f);
@@ -729,6 +776,60 @@ void pack_deconv_as_conv3x3(const float* w_iohw, const float* bias, int Cin, int
             }
         }
     }
+}
+
+// One form per N block of the packed image [Cout_p/32][Cin_p/8][j][xi/4][half][co%32][xi%4]: derived from the DATA, never from the
+// layer type — `!(v == 0.0f)` keeps a plane alive for any non-zero weight and for a NaN, so no padding or pruning can make it wrong.
+void wino_dead_forms(const float* wp, int Cin_p, int Cout_p, std::vector<int>& forms) {
+    const int NY = Cout_p / 32, slices = Cin_p / 8 * 4;      // (c8, j) slices of a block: 4 plane rows x 256 floats each
+    forms.assign(NY, kWinoDeadNone);
+    for (int nb = 0; nb < NY; ++nb) {
+        bool row_live[4] = {false, false, false, false}, col_live[4] = {false, false, false, false};
+        const float* blk = wp + (size_t)nb * slices * 1024;
+        for (int s = 0; s < slices; ++s)
+            for (int r = 0; r < 4; ++r)
+                for (int i = 0; i < 256; ++i)
+                    if (!(blk[((size_t)s * 4 + r) * 256 + i] == 0.0f)) row_live[r] = col_live[i & 3] = true;
+        forms[nb] = !row_live[0]   ? kWinoDeadRow0
+                    : !row_live[3] ? kWinoDeadRow3
+                    : !col_live[0] ? kWinoDeadCol0
+                    : !col_live[3] ? kWinoDeadCol3
+                                   : kWinoDeadNone;
+    }
+}
+
+int wino_dead_planes(const std::vector<int>& forms) {
+    int n = 0;
+    for (int f : forms) n += f != kWinoDeadNone ? 4 : 0;
+    return n;
+}
+
+void pack_deconv_wino(const float* w_iohw, const float* bias, const float* prelu, int Cin, int LO, const int* chan_map, int Cin_p, WinoDeconvPack& out) {
+    std::vector<float> w3, b3;
+    pack_deconv_as_conv3x3(w_iohw, bias, Cin, LO, w3, b3);
+    const int C4 = 4 * LO;
+    out.Cout3_p = round_up(C4, 32);
+    std::vector<int> forms, forms_g;
+    pack_wino3x3(w3.data(), C4, Cin, chan_map, Cin_p, out.Cout3_p, out.ww);
+    wino_dead_forms(out.ww.data(), Cin_p, out.Cout3_p, forms);
+    // the Gray order of the parity groups: a row permutation of w3, kept only where it skips more planes (LO = 24: 12 of 48 against 10)
+    std::vector<float> w3g(w3.size()), wwg;
+    const size_t row = (size_t)Cin * 9;
+    for (int co = 0; co < C4; ++co) memcpy(&w3g[co * row], &w3[wino_gray_order(co, LO) * row], row * sizeof(float));
+    pack_wino3x3(w3g.data(), C4, Cin, chan_map, Cin_p, out.Cout3_p, wwg);
+    wino_dead_forms(wwg.data(), Cin_p, out.Cout3_p, forms_g);
+    out.gray = wino_dead_planes(forms_g) > wino_dead_planes(forms) ? 1 : 0;
+    if (out.gray) out.ww.swap(wwg), forms.swap(forms_g);
+    // bias and PReLU slopes are the same for the four parities: repeated per group, in either order
+    out.bias3.assign(out.Cout3_p, 0.f);
+    out.prelu3.assign(prelu ? out.Cout3_p : 0, 0.f);
+    for (int co = 0; co < C4; ++co) {
+        const int src = out.gray ? wino_gray_order(co, LO) : co;
+        out.bias3[co] = b3[src];
+        if (prelu) out.prelu3[co] = prelu[src % LO];
+    }
+    for (unsigned& d : out.dead) d = 0;
+    for (int nb = 0; nb < (int)forms.size() && nb < 32; ++nb) out.dead[nb >> 3] |= (unsigned)forms[nb] << ((nb & 7) * 4);
 }
 
 // 0 = automatic, 1 = direct kernel only, 2 = Winograd wherever the layer shape allows it.  Set through the test hook
@@ -827,6 +928,9 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
     VFI_REQUIRE(a.act != 3 || a.prelu, "conv_wino %s: act 3 needs per-channel slopes", name);
     WinoArgs p;
     p.a = a;
+    p.gray = a.out_mode != 0 ? a.wino_gray : 0;
+    if (a.out_mode == 0 || !option(kOptWinoDead))      // the table belongs to the SHUF kernels; option 0 = all 16 planes (the order stays)
+        for (unsigned& d : p.a.wino_dead) d = 0;
     if (variant == 0) {     // region shape by covered-area efficiency: 16x8 pixels unless 32x4 wastes clearly less
         const double area = (double)a.Hin * a.Win;
         const double e8 = area / ((double)cdiv(a.Win, 16) * 16 * cdiv(a.Hin, 8) * 8);

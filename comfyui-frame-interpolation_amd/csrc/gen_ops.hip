@@ -182,6 +182,8 @@ struct vfi_conv {
     float* bias3 = nullptr;
     float* prelu3 = nullptr;
     int Cout3_p = 0;
+    unsigned dead3[4] = {0, 0, 0, 0};      // ... its zero transform planes per N block and the order of its parity groups (WinoDeconvPack)
+    int gray3 = 0;
     int Cout = 0, Cout_p = 0, Cin = 0, Cin_p = 0, kh = 0, kw = 0, taps = 0;
     int stride = 1, pad_mode = 0, kind = 0;  // kind 0: Conv2d, 1: ConvTranspose2d(4, 2, 1), 2: nearest x2 up-sampling + Conv2d(2, 'same') (vfi_conv_create_up2x2)
     unsigned char* tapmask = nullptr;         // kind 2: taps of every 64-channel N block's parity
@@ -386,18 +388,13 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
     // vfi_conv_forward_ex sends replicate-padded ones to the direct kernel whatever the image.  Per-channel PReLU layers take it
     // since r5 (conv_wino.hip MODE 1): their slopes are repeated per parity group like the bias.
     if (ok && kind == 1 && 4 * Cout <= 1024 && !pad_mode) {
-        std::vector<float> w3, b3, ww;
-        pack_deconv_as_conv3x3(w_host, bias_host, Cin, Cout, w3, b3);
-        c->Cout3_p = round_up(4 * Cout, 32);
-        pack_wino3x3(w3.data(), 4 * Cout, Cin, chan_map, Cin_phys, c->Cout3_p, ww);
-        b3.resize(c->Cout3_p, 0.f);
-        ok = upload(&c->ww, ww) && upload(&c->bias3, b3);
-        if (ok && prelu_host) {
-            std::vector<float> p3(c->Cout3_p, 0.f);
-            for (int g = 0; g < 4; ++g)
-                for (int co = 0; co < Cout; ++co) p3[(size_t)g * Cout + co] = prelu_host[co];
-            ok = upload(&c->prelu3, p3);
-        }
+        WinoDeconvPack dp;
+        pack_deconv_wino(w_host, bias_host, prelu_host, Cin, Cout, chan_map, Cin_phys, dp);
+        c->Cout3_p = dp.Cout3_p;
+        c->gray3 = dp.gray;
+        memcpy(c->dead3, dp.dead, sizeof(c->dead3));
+        ok = upload(&c->ww, dp.ww) && upload(&c->bias3, dp.bias3);
+        if (ok && prelu_host) ok = upload(&c->prelu3, dp.prelu3);
     }
     if (!ok) {
         set_error("vfi_conv_create_ex: device allocation/upload failed");
@@ -481,6 +478,8 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
         b.prelu = c->prelu3;
         b.Cout = 4 * c->Cout;
         b.Cout_p = c->Cout3_p;
+        b.wino_gray = c->gray3;
+        memcpy(b.wino_dead, c->dead3, sizeof(b.wino_dead));
         const long regions = 2L * cdiv(Hin, 8) * cdiv(Win, 16);
         // ... and from 128 x 128 input pixels up: below that (the 34x60 / 68x120 pyramid levels at 1080p, K = 256 ... 768) the direct kernel's
         // split-K wins by 10-75 % whatever the item count (profiles/r05_deconv_ab.txt: 512->256 @34x60 153 vs 267 us, 256->128 @68x120 114 vs 143 us;

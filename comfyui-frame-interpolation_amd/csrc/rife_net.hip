@@ -71,6 +71,8 @@ struct ConvLayer {
     DevBuf w, ww, bias, beta;   // ww: Winograd F(2x2,3x3) pack (3x3 stride-1 layers: the ResConvs and the 4.17 / 4.26 head; lastconv as a 3x3 layer)
     DevBuf bias3;               // lastconv as a 4 * LO-channel 3x3 layer (pack_deconv_as_conv3x3): its bias, repeated per parity group
     int Cout3_p = 0;
+    unsigned dead3[4] = {0, 0, 0, 0};      // ... its zero transform planes per N block and the order of its parity groups (WinoDeconvPack)
+    int gray3 = 0;
     int Cin = 0, Cin_p = 0, Cout = 0, Cout_p = 0;
     bool folded = false;  // residual folded into the centre tap (ResConv)
 };
@@ -245,12 +247,12 @@ vfi_rife_t* vfi_rife_create(int arch_ver_x10, const float* const* tensors, const
             pack_deconv4x4(w, bi, c, LO, c, LOp, wp, bp);
             ok = !upload(L.w, wp) && !upload(L.bias, bp);
             // the same layer as ONE 3x3 convolution with 4 * LO channels on the Winograd kernel (no padding of 24 to a 32-wide N tile)
-            std::vector<float> w3, b3, wq;
-            pack_deconv_as_conv3x3(w, bi, c, LO, w3, b3);
-            L.Cout3_p = round_up(4 * LO, 32);
-            pack_wino3x3(w3.data(), 4 * LO, c, nullptr, c, L.Cout3_p, wq);
-            b3.resize(L.Cout3_p, 0.f);
-            ok = ok && !upload(L.ww, wq) && !upload(L.bias3, b3);
+            WinoDeconvPack dp;
+            pack_deconv_wino(w, bi, nullptr, c, LO, nullptr, c, dp);
+            L.Cout3_p = dp.Cout3_p;
+            L.gray3 = dp.gray;
+            memcpy(L.dead3, dp.dead, sizeof(L.dead3));
+            ok = ok && !upload(L.ww, dp.ww) && !upload(L.bias3, dp.bias3);
         }
     }
     if (ok) {
@@ -298,6 +300,8 @@ vfi_rife_t* vfi_rife_clone_empty(const vfi_rife_t* src) {
     net->nblocks = src->nblocks, net->NX = src->NX, net->enc_act = src->enc_act;
     auto meta = [](ConvLayer& d, const ConvLayer& s_) {
         d.Cin = s_.Cin, d.Cin_p = s_.Cin_p, d.Cout = s_.Cout, d.Cout_p = s_.Cout_p, d.folded = s_.folded, d.Cout3_p = s_.Cout3_p;
+        d.gray3 = s_.gray3;
+        memcpy(d.dead3, s_.dead3, sizeof(d.dead3));
     };
     for (int b = 0; b < kMaxBlocks; ++b) {
         meta(net->conv00[b], src->conv00[b]);
@@ -628,6 +632,8 @@ int vfi_rife_interpolate(vfi_rife_t* net, int B, const int* slot0, const int* sl
             a.bias = net->last[i].bias3.p;
             a.Cout = 4 * net->last[i].Cout;
             a.Cout_p = net->last[i].Cout3_p;
+            a.wino_gray = net->last[i].gray3;
+            memcpy(a.wino_dead, net->last[i].dead3, sizeof(a.wino_dead));
             if (conv_wino_launch(a, 8, st, kLastName[i])) return -1;
         } else {
             deconv4x4_taps(a);

@@ -79,6 +79,7 @@ enum Option {
     kOptSepconvPlanar,      // 1: SepConv++'s heads transposed to planar before the output stage (default), 0: the output stage reads them NHWC
     kOptStage0,             // 1: RIFE block 0's input assembled from the per-frame staging images the frame pack kernels write (default), 0: gathered from the packs per pair
     kOptAttKsplit,          // 1..8: the number of key ranges attention_launch_t asks for (attention.hip; reduced so that no range is empty), default 0: chosen from the device's CU count
+    kOptWinoDead,           // 1: the Winograd kernel skips the transform planes a transposed-convolution layer's weights leave zero (ConvArgs::wino_dead; default), 0: all 16 planes: same bits
     kOptCount
 };
 long option(Option o);
@@ -152,6 +153,9 @@ struct ConvArgs {
     long split_stride;     //   out + blockIdx.z * split_stride (floats) of the partial-sum workspace
     int cin_live;          // the layer's real input channels where the caller knows them (0 = not given: all Cin_p are multiplied); last, so
                            //   that the kernels' argument offsets of the fields above are what they were
+    unsigned wino_dead[4]; // Winograd kernel, transposed-convolution layers (out_mode 1 / 2): the zero transform planes of each 32-channel N
+                           //   block, 4 bits per block (kWinoDead*, block nb = bits 4 (nb % 8) of word nb / 8), from WinoDeconvPack; 0 = none known
+    int wino_gray;         //   1: the four parity groups of such a layer are packed in the order p00 p01 p11 p10 (wino_gray_order)
 };
 
 struct ConvVariant {
@@ -186,6 +190,32 @@ void conv3x3_taps(ConvArgs& a);
 // variant 0 = pick the region shape, 8 / 16 = 16x8 / 32x4 output pixels per wave.
 void pack_wino3x3(const float* w_oihw, int Cout, int Cin, const int* chan_map, int Cin_p, int Cout_p, std::vector<float>& wp);
 void pack_deconv_as_conv3x3(const float* w_iohw, const float* bias, int Cin, int LO, std::vector<float>& w3, std::vector<float>& b3);
+// The transform planes of each 32-channel N block of a pack_wino3x3 image that hold nothing but zeros, as one form per block: a form is
+// reported only when EVERY packed weight of that plane row / column of the block compares == 0.0f (a NaN or a padded channel beside
+// live ones keeps its plane alive), a row before a column (a row also saves transform work).  forms[Cout_p / 32].
+enum { kWinoDeadNone = 0, kWinoDeadRow0 = 1, kWinoDeadRow3 = 2, kWinoDeadCol0 = 3, kWinoDeadCol3 = 4 };
+void wino_dead_forms(const float* wp, int Cin_p, int Cout_p, std::vector<int>& forms);
+int wino_dead_planes(const std::vector<int>& forms);      // planes the forms skip (4 per block with one)
+// N position co of a 4 * LO-channel transposed-convolution layer -> the row of pack_deconv_as_conv3x3's w3 / b3 that sits there when the
+// parity groups are ordered p00 p01 p11 p10 (consecutive groups share py or px, so a 32-channel block that spans two of them keeps a
+// dead plane row or column); the Winograd epilogue inverts it (g ^= g >> 1).  The map is its own inverse.
+inline int wino_gray_order(int co, int LO) {
+    const int g = co / LO;
+    return (g ^ (g >> 1)) * LO + co % LO;
+}
+// A ConvTranspose2d(Cin, LO, 4, 2, 1) layer ready for the Winograd kernel: pack_deconv_as_conv3x3 + (where it raises the number of
+// skipped planes) the Gray order + pack_wino3x3 + the dead-plane table.  bias3 / prelu3 [Cout3_p] are the per-channel constants
+// repeated per parity group in the SAME order (prelu3 empty without slopes).  apply() hands table and order to a launch.
+struct WinoDeconvPack {
+    std::vector<float> ww, bias3, prelu3;
+    int Cout3_p = 0, gray = 0;
+    unsigned dead[4] = {0, 0, 0, 0};
+    void apply(ConvArgs& a) const {
+        for (int i = 0; i < 4; ++i) a.wino_dead[i] = dead[i];
+        a.wino_gray = gray;
+    }
+};
+void pack_deconv_wino(const float* w_iohw, const float* bias, const float* prelu, int Cin, int LO, const int* chan_map, int Cin_p, WinoDeconvPack& out);
 bool conv_wino_eligible(const ConvArgs& a);
 int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal
 int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* trace_name);

@@ -27,7 +27,7 @@ g = torch.Generator(device="cpu").manual_seed(0)
 raw = torch.rand((B + 1, H, W, 3), generator=g).cuda()
 out = torch.empty((B, H, W, 3), device="cuda")
 slot0, slot1, ts = list(range(B)), list(range(1, B + 1)), [0.5] * B
-names = ("conv0a_b0", "conv0b_b0", "conv0a_b1", "conv0b_b1", "conv0a_b2", "conv0b_b2", "conv0b_b3", "trans1_conv0a", "encode_batch", "stage_in0", "stage_trans4", "stage_trans2", "final_blend")
+names = ("conv0a_b0", "conv0b_b0", "conv0a_b1", "conv0b_b1", "conv0a_b2", "conv0b_b2", "conv0b_b3", "lastconv_b0", "lastconv_b1", "lastconv_b2", "lastconv_b3", "trans1_conv0a", "encode_batch", "stage_in0", "stage_trans4", "stage_trans2", "final_blend")
 
 
 def step():
