@@ -81,7 +81,8 @@ def _node_class_mappings():
 # Nodes registered only on request (their real checkpoints have not been run yet): config.yaml's `extra_nodes`, a comma-separated
 # list such as "cain, sepconv".  (No environment variable: the package's set of variables is kept small, _lib.SUPPORTED_ENV.)
 # FLAVR's, AMT's and ATM's keys are the reference's class names lower-cased, "flavr_vfi" / "amt_vfi" / "atm_vfi"; a bare "flavr", "amt" or
-# "atm" is not a key.  ATM VFI serves atm-vfi-lite.pt (ATM-lite) with global motion "On" or "Off (fastest)".
+# "atm" is not a key.  ATM VFI serves atm-vfi-lite.pt (ATM-lite) with global motion "On" or "Off (fastest)", and atm-vfi-base.pt /
+# atm-vfi-base-pct.pt (ATM-base) only when config.yaml's atm_base key is on as well (atm_spec.atm_base_enabled).
 # AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled).
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
                "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)"),

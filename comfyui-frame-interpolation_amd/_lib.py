@@ -246,9 +246,11 @@ PROTOTYPES = {
                                       C.c_int, C.c_void_p]),
     "vfi_atm_refine_out": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfi_atm_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
+    "vfi_atm_create_variant": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int]),
     "vfi_atm_destroy": (None, [C.c_void_p]),
     "vfi_atm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_atm_max_padded_pixels": (C.c_int64, []),
+    "vfi_atm_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
     "vfi_atm_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_atm_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_m2m_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),

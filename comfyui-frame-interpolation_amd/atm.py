@@ -1,8 +1,9 @@
-"""ATM VFI node — host-side mirror of the reference's ``ATM_VFI`` (ATM-lite only) over the HIP library.
+"""ATM VFI node — host-side mirror of the reference's ``ATM_VFI`` over the HIP library.
 
 Node shape follows vfi_models/atm/__init__.py:76-182: the three checkpoint names, the three ``global_motion`` choices and the ``vfi``
-keywords.  ``atm-vfi-lite.pt`` is served; ``atm-vfi-base.pt`` / ``atm-vfi-base-pct.pt`` (ATM-base) and ``"On with Ensemble (slowest)"`` (the
-multi-scale global-motion ensemble) raise NotImplementedError naming themselves, before anything is loaded.  The frame loop is the
+keywords.  ``atm-vfi-lite.pt`` is served; ``atm-vfi-base.pt`` / ``atm-vfi-base-pct.pt`` (ATM-base) are served when config.yaml's ``atm_base``
+key is on and raise NotImplementedError naming themselves otherwise; ``"On with Ensemble (slowest)"`` (the multi-scale global-motion
+ensemble) raises NotImplementedError by name for both models.  All of this before anything is loaded.  The frame loop is the
 reference's own (:152-177): per kept pair the first frame and the new frames of ``inference()`` (:39-74) — FILM's greedy midpoint schedule,
 every model call the midpoint of two known frames, clamped to [0, 1] and re-used —, a skipped pair contributes nothing at all, the clip's
 last frame is appended: schedule.film_output_plan + nodeloop.run_plan with film.film_schedule.  Each model call is ONE vfi_atm_forward
@@ -13,7 +14,7 @@ import typing
 import torch
 
 from . import _lib
-from .atm_spec import CKPT_NAMES, check_ckpt_name, check_state_dict, load_file, weight_shapes
+from .atm_spec import CKPT_NAMES, VARIANTS, check_ckpt_name, check_state_dict, load_file, weight_shapes
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film import film_schedule
 from .netengine import NetEngine, WorkspaceBytes
@@ -24,6 +25,10 @@ MODEL_TYPE = "atm"
 GLOBAL_MOTION = {"On": (True, False), "On with Ensemble (slowest)": (True, True), "Off (fastest)": (False, False)}      # (global motion, ensemble)
 FLOATS_PER_PADDED_PIXEL = 80      # the widest per-image buffer: the refinement net's input, 76 channels padded to 80 (csrc/atm_net.hip)
 MAX_PADDED_PIXELS = ((1 << 31) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)      # = vfi_atm_max_padded_pixels(): 6 710 886
+# ATM-base: the refinement net's full-resolution concat buffer, 2 * 64 = 128 channels (kCfg[1].px_floats, csrc/atm_net.hip): 1472x2560 fits,
+# 2176x3840 does not; tests/test_gpu_atm_base.py asserts that this limit is vfi_atm_object_max_padded_pixels' of a base object
+BASE_FLOATS_PER_PADDED_PIXEL = 128
+MAX_PADDED_PIXELS_BASE = ((1 << 31) - 1) // (BASE_FLOATS_PER_PADDED_PIXEL * 4)      # 4 194 303
 
 
 def padded_size(H, W):
@@ -31,10 +36,12 @@ def padded_size(H, W):
     return H + (((H // 64) + 1) * 64 - H) % 64, W + (((W // 64) + 1) * 64 - W) % 64
 
 
-def check_frame_size(H, W):
+def check_frame_size(H, W, variant="lite"):
     Hp, Wp = padded_size(H, W)
-    if Hp * Wp > MAX_PADDED_PIXELS:
-        raise ValueError(f"ATM VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({MAX_PADDED_PIXELS} padded pixels)")
+    limit = MAX_PADDED_PIXELS_BASE if variant == "base" else MAX_PADDED_PIXELS
+    if Hp * Wp > limit:
+        raise ValueError(f"ATM VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({limit} padded pixels"
+                         f"{' for ATM-base' if variant == 'base' else ''})")
 
 
 def global_motion_flag(global_motion):
@@ -48,22 +55,34 @@ def global_motion_flag(global_motion):
 
 
 class AtmEngine(WorkspaceBytes, NetEngine):
-    """Device-resident ATM-lite: ``forward(frame0, frame1, global_motion)`` = the model's clamped, un-padded midpoint frame of one pair."""
+    """Device-resident ATM-lite or ATM-base (``variant``; base only with config.yaml's ``atm_base`` on): ``forward(frame0, frame1,
+    global_motion)`` = the model's clamped, un-padded midpoint frame of one pair."""
 
     PREFIX, LABEL = "vfi_atm", "ATM"
 
+    def __init__(self, state_dict, variant="lite", device=None):
+        assert variant in VARIANTS, f"variant: one of {VARIANTS}"
+        self.variant = variant
+        super().__init__(state_dict, device, VARIANTS.index(variant))
+
+    def _fn(self, name):
+        return super()._fn("create_variant" if name == "create" else name)
+
     def shapes(self):
-        return weight_shapes()
+        return weight_shapes(self.variant)
 
     def check_state_dict(self, state_dict):
-        check_state_dict(state_dict)
+        check_state_dict(state_dict, self.variant)
+
+    def max_padded_pixels(self):
+        return int(self._fn("object_max_padded_pixels")(self.handle))
 
     def forward(self, frame0, frame1, global_motion=True, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
         H, W, Cc = frame0.shape
         for f in (frame0, frame1):
             assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
-        check_frame_size(H, W)
+        check_frame_size(H, W, self.variant)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         self._call("forward", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, int(bool(global_motion)), out.data_ptr(), _lib.stream_ptr())
@@ -100,11 +119,11 @@ class ATM_VFI:
 
     def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10, multiplier: typing.SupportsInt = 2,
             global_motion="On", optional_interpolation_states: InterpolationStateList = None, **kwargs):
-        check_ckpt_name(ckpt_name)                      # ATM-base: NotImplementedError naming the file, before anything is loaded
-        gm = global_motion_flag(global_motion)          # the ensemble likewise
-        check_frame_size(*frames.shape[1:3])            # before an engine exists
+        variant = check_ckpt_name(ckpt_name)            # ATM-base without the atm_base key: NotImplementedError naming the file, before anything is loaded
+        gm = global_motion_flag(global_motion)          # the ensemble likewise, for both models
+        check_frame_size(*frames.shape[1:3], variant)   # before an engine exists
         plan, tasks = film_output_plan(len(frames), multiplier, optional_interpolation_states)
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
-        entry = cached_engine(MODEL_TYPE, model_path, lambda: AtmEngine(load_file(model_path, ckpt_name)))
+        entry = cached_engine(MODEL_TYPE, model_path, lambda: AtmEngine(load_file(model_path, ckpt_name), variant))
         with engine_call(entry, tuple(frames.shape[1:3])) as engine:
             return (run_plan(engine, frames, plan, tasks, lambda e, f0, f1, t: atm_pair(e, f0, f1, t, gm), "ATM VFI"),)

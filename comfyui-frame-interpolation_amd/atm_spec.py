@@ -5,8 +5,12 @@ Key names / shapes follow ``network_lite.Network`` (vfi_models/atm/network_lite.
 (attention.py:216-237, :393-416); order = torch state_dict order (a module's own parameters, then its buffers, then its children): 236
 entries, 11 975 523 parameters, plus the four ``relative_coord`` buffers of the ATM blocks.  Those buffers are not weights: they hold key
 position minus query position inside the window (x, then y; attention.py:150-165), which the attention kernel computes itself, so a file
-whose buffers say otherwise is refused (``load_file``).  ATM-base (atm-vfi-base.pt, atm-vfi-base-pct.pt: ``network_base.Network``) is not
-built yet and is refused by name."""
+whose buffers say otherwise is refused (``load_file``).
+
+ATM-base (atm-vfi-base.pt and its perceptual-loss fine-tune atm-vfi-base-pct.pt: ``network_base.Network``, network_base.py:88-260) has the same
+module tree and forward, hence the same 236 names in the same order; only the widths differ (``CONFIG``): 51 564 259 parameters.  It is
+served only when config.yaml's ``atm_base`` key is on (``atm_base_enabled()``); absent or off, both files and 24-channel state dicts are
+refused as before."""
 from collections import OrderedDict
 
 CKPT_NAMES = ("atm-vfi-base.pt", "atm-vfi-lite.pt", "atm-vfi-base-pct.pt")      # the reference's widget order
@@ -17,9 +21,20 @@ LOCAL_DIM, LOCAL_WIN = 224, 8        # 96 + 64 + 2 * 32 on the H/8 map
 GLOBAL_DIM, GLOBAL_WIN = 352, 12     # 128 + 96 + 2 * 64 on the H/16 map
 MOTION_OUT = 5                       # flow 0 (x, y), flow 1 (x, y), mask logit
 N_TENSORS, N_PARAMETERS = 236, 11975523
+VARIANTS = ("lite", "base")          # the index is vfi_atm_create_variant's ``variant``
+CKPT_VARIANT = {"atm-vfi-base.pt": "base", "atm-vfi-lite.pt": "lite", "atm-vfi-base-pct.pt": "base"}
+# hidden: hidden_dims; last_extra: last_feat_extract's width over hidden[-1]; mlp_ratio: of all six windowed blocks (base passes none: the
+# class default); local_head / global_head: the motion heads' hidden widths (lite 0.5 x 448 and 352, base int(0.75 x 768) and the constant
+# 768); refine: the refinement net's hidden_dim
+CONFIG = {"lite": dict(hidden=HIDDEN, last_extra=32, mlp_ratio=2, local_head=224, global_head=352, refine=32, n_parameters=N_PARAMETERS),
+          "base": dict(hidden=(24, 48, 96, 192), last_extra=96, mlp_ratio=4, local_head=576, global_head=768, refine=64, n_parameters=51564259)}
 
 
-def atm_shapes():
+def atm_shapes(variant="lite"):
+    cfg = CONFIG[variant]
+    HIDDEN = cfg["hidden"]
+    LOCAL_DIM = HIDDEN[3] + HIDDEN[2] + 2 * HIDDEN[1]
+    GLOBAL_DIM = 2 * HIDDEN[3] + cfg["last_extra"] + 2 * HIDDEN[2]
     d = OrderedDict()
 
     def conv(name, cout, cin, k=3):
@@ -40,10 +55,10 @@ def atm_shapes():
     def norm(name, c):
         d[name + ".weight"], d[name + ".bias"] = (c,), (c,)
 
-    def mlp(name, c):
-        linear(name + ".fc1", 2 * c, c)
-        d[name + ".dwconv.dwconv.weight"], d[name + ".dwconv.dwconv.bias"] = (2 * c, 1, 3, 3), (2 * c,)
-        linear(name + ".fc2", c, 2 * c)
+    def mlp(name, c, ratio=cfg["mlp_ratio"]):
+        linear(name + ".fc1", ratio * c, c)
+        d[name + ".dwconv.dwconv.weight"], d[name + ".dwconv.dwconv.bias"] = (ratio * c, 1, 3, 3), (ratio * c,)
+        linear(name + ".fc2", c, ratio * c)
 
     def fusion(name, dims):      # CrossScaleFeatureFusion(in_dims = dims) (:34-56)
         conv(name + ".layers.0", dims[1], dims[1])
@@ -64,10 +79,10 @@ def atm_shapes():
         norm(name + ".norm2", c)
         mlp(name + ".mlp", c)
 
-    def motion_mlp(name, c):
-        convprelu(name + ".0", 2 * c + HEADS, c)
-        convprelu(name + ".1", c, c)
-        conv(name + ".2", MOTION_OUT, c, 1)
+    def motion_mlp(name, c, hidden):
+        convprelu(name + ".0", 2 * c + HEADS, hidden)
+        convprelu(name + ".1", hidden, hidden)
+        conv(name + ".2", MOTION_OUT, hidden, 1)
 
     prev = 3
     for i, c in enumerate(HIDDEN):
@@ -84,14 +99,14 @@ def atm_shapes():
         mlp(p + ".mlp", LOCAL_DIM)
     for k in range(2):
         atmformer(f"local_motion_atmformer.{k}", LOCAL_DIM, LOCAL_WIN)
-    motion_mlp("local_motion_mlp", LOCAL_DIM)
-    last = HIDDEN[-1] + 32
+    motion_mlp("local_motion_mlp", LOCAL_DIM, cfg["local_head"])
+    last = HIDDEN[-1] + cfg["last_extra"]
     convprelu("last_feat_extract.0", HIDDEN[-1], last)
     convprelu("last_feat_extract.1", last, last)
     fusion("global_feature_fusion", (HIDDEN[-2], HIDDEN[-1], last))
     for k in range(2):
         atmformer(f"global_motion_atmformer.{k}", GLOBAL_DIM, GLOBAL_WIN)
-    motion_mlp("global_motion_mlp", GLOBAL_DIM)
+    motion_mlp("global_motion_mlp", GLOBAL_DIM, cfg["global_head"])
     cin = 2 * LOCAL_DIM + MOTION_OUT
     for i, f in enumerate((LOCAL_DIM, LOCAL_DIM // 2, LOCAL_DIM // 4)):
         p, c = f"upsample_pyramid.{i}", f + MOTION_OUT
@@ -103,7 +118,7 @@ def atm_shapes():
         convprelu(f"{p}.{j + 1}", c, c)
         conv(f"{p}.{j + 2}", c, c)
         cin = c
-    hid = 32
+    hid = cfg["refine"]
     convprelu("proj", LOCAL_DIM // 4 + MOTION_OUT + 15, hid)
     convprelu("down1.0", hid, hid)
     convprelu("down2.0", LOCAL_DIM // 2 + hid, 2 * hid)
@@ -121,9 +136,9 @@ def atm_shapes():
     return d
 
 
-def weight_shapes():
-    """The tensors the C object takes (vfi_atm_create), in order: every entry but the ``relative_coord`` buffers."""
-    return OrderedDict((k, v) for k, v in atm_shapes().items() if not k.endswith(".relative_coord"))
+def weight_shapes(variant="lite"):
+    """The tensors the C object takes (vfi_atm_create / vfi_atm_create_variant), in order: every entry but the ``relative_coord`` buffers."""
+    return OrderedDict((k, v) for k, v in atm_shapes(variant).items() if not k.endswith(".relative_coord"))
 
 
 def relative_coord(win):
@@ -135,22 +150,41 @@ def relative_coord(win):
     return torch.stack([x[None, :] - x[:, None], y[None, :] - y[:, None]])[None, None]
 
 
+def atm_base_enabled():
+    """config.yaml's ``atm_base`` key (absent = off), read at call time"""
+    from . import ckpt
+
+    return bool(ckpt.load_config().get("atm_base", False))
+
+
 def check_ckpt_name(ckpt_name):
+    """-> the variant the name stands for.  The two base files are "base" when config.yaml's ``atm_base`` key is on and raise
+    NotImplementedError naming themselves otherwise, before anything is loaded."""
     if ckpt_name not in CKPT_NAMES:
         raise KeyError(f"unknown ATM checkpoint {ckpt_name!r} (known: {list(CKPT_NAMES)})")
-    if ckpt_name != LITE:
+    if ckpt_name != LITE and not atm_base_enabled():
         raise NotImplementedError(f"{ckpt_name}: ATM-base is not built yet; only {LITE} (ATM-lite) is served")
+    return CKPT_VARIANT[ckpt_name]
 
 
-def check_state_dict(sd):
-    """Strict, as ``load_state_dict(sd)``: every key, no extra key, every shape; and the ``relative_coord`` buffers equal the analytic table."""
+def check_state_dict(sd, variant=None):
+    """Strict, as ``load_state_dict(sd)``: every key, no extra key, every shape; and the ``relative_coord`` buffers equal the analytic table.
+    variant None: told by the first convolution's width (16 = lite; 24 = base, with ``atm_base`` on); a dict of the other model than the
+    variant asked for is a size mismatch, as it is for ``load_state_dict``.  Returns the variant."""
     import torch
 
     first = sd.get("feat_extracts.0.0.0.weight")
-    if first is not None and int(first.shape[0]) != HIDDEN[0]:
-        raise NotImplementedError(f"an ATM state dict with {int(first.shape[0])} first feature channels: ATM-base is not built yet; only ATM-lite "
-                                  f"({HIDDEN[0]}) is served")
-    want = atm_shapes()
+    width = None if first is None else int(first.shape[0])
+    if not atm_base_enabled():
+        if width is not None and width != HIDDEN[0]:
+            raise NotImplementedError(f"an ATM state dict with {width} first feature channels: ATM-base is not built yet; only ATM-lite "
+                                      f"({HIDDEN[0]}) is served")
+        if variant == "base":
+            raise NotImplementedError(f"ATM-base is not built yet; only {LITE} (ATM-lite) is served")
+        variant = "lite"
+    elif variant is None:
+        variant = "base" if width == CONFIG["base"]["hidden"][0] else "lite"
+    want = atm_shapes(variant)
     missing = [k for k in want if k not in sd]
     unexpected = [k for k in sd if k not in want]
     if missing or unexpected:
@@ -164,6 +198,7 @@ def check_state_dict(sd):
             if not torch.equal(sd[k].detach().to("cpu", torch.float32), relative_coord(win)):
                 raise RuntimeError(f"{k} is not key position minus query position inside the {win}x{win} window: the attention kernel computes "
                                    "these offsets itself and cannot serve a checkpoint trained with another table")
+    return variant
 
 
 def load_file(path, ckpt_name=None):
@@ -173,20 +208,22 @@ def load_file(path, ckpt_name=None):
 
     import torch
 
-    check_ckpt_name(ckpt_name or os.path.basename(path))
+    variant = check_ckpt_name(ckpt_name or os.path.basename(path))
     blob = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(blob, dict) or "model_state_dict" not in blob:
         raise RuntimeError(f"{path}: an ATM checkpoint is a dict with a 'model_state_dict' entry")
     sd = OrderedDict((k, v) for k, v in blob["model_state_dict"].items() if "attn_mask" not in k and "HW" not in k)
-    check_state_dict(sd)
+    check_state_dict(sd, variant)
     return sd
 
 
 # gains of seeded_state_dict over torch's default draws
 GAIN_CONV, GAIN_QKV, GAIN_LINEAR, GAIN_GLOBAL_HEAD = 2.0, 4.0, 2.0, 1.0
+# (conv, q / kv / qkv, other linears, global_motion_mlp.2) per variant
+GAINS = {"lite": (GAIN_CONV, GAIN_QKV, GAIN_LINEAR, GAIN_GLOBAL_HEAD), "base": (2.0, 4.0, 3.0, 1.0)}
 
 
-def seeded_state_dict(seed):
+def seeded_state_dict(seed, variant="lite"):
     """A stand-in for atm-vfi-lite.pt, for the tests and goldens.  With the network's own initialisation (trunc_normal 0.02 linears, unit
     LayerNorms) the model is dead: final flows of 0.05 px, and the motion read-out of the ATM blocks moves the frame by 2e-8.  So the draws
     are torch's default ``reset_parameters`` ones, U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for weights and biases, in state-dict order from one
@@ -197,11 +234,20 @@ def seeded_state_dict(seed):
     U(0.5, 1.5) and biases U(-0.2, 0.2) (the bias is what a pad token holds after norm1), PReLU slopes 0.25.  Biases keep gain 1.
     tests/test_atm_restated_cpu.py asserts what the gains are for, at every golden shape and in both global-motion modes: read-out effect >=
     1e-3, largest flow >= 0.5 px, <= 10 % of the output clamped, float32 within 1e-4 of float64 (at x 2.4 the "On" mode clamps half the
-    frame)."""
+    frame).
+
+    variant "base": a stand-in for atm-vfi-base.pt, drawn the same way over base's shapes with GAINS["base"] = (conv 2, q / kv / qkv 4, other
+    linears 3, global_motion_mlp.2 1).  Lite's gains do not carry over: base's linears have 1.7 to 2 times the fan-in (384 / 672 / 1536 /
+    2688 against 224 / 352 / 448 / 704), and at lite's linear gain of 2 the read-out effect with global motion off is 9.9e-4 at 128x192 and
+    8.6e-4 at 192x320, below the 1e-3 the condition asks (q / kv / qkv at 6 instead also passes, with less margin).  With the gains above
+    the reference's network_base.Network gives (tests/golden/atm_base_net.npz; On / Off over the three golden shapes): read-out effect
+    2.5e-2 .. 5.7e-2 / 2.8e-3 .. 5.2e-3, largest flow 1.80 .. 2.10 / 1.60 .. 2.03 px, clamped <= 1.7 % / <= 1.5 %, and the float32
+    restatement is within 3.1e-5 of the float64 one.  tests/test_atm_base_cpu.py asserts the four conditions."""
     import torch
 
     g = torch.Generator().manual_seed(seed)
-    shapes = atm_shapes()
+    shapes = atm_shapes(variant)
+    gain_conv, gain_qkv, gain_linear, gain_global_head = GAINS[variant]
     sd = OrderedDict()
 
     def uni(shp, lo, hi):
@@ -221,6 +267,6 @@ def seeded_state_dict(seed):
             fan = wshape[1] * (wshape[2] * wshape[3] if len(wshape) == 4 else 1)
             gain = 1.0
             if leaf == "weight":
-                gain = GAIN_GLOBAL_HEAD if k == "global_motion_mlp.2.weight" else GAIN_CONV if len(wshape) == 4 else (GAIN_QKV if stem.rsplit(".", 1)[1] in ("q", "kv", "qkv") else GAIN_LINEAR)
+                gain = gain_global_head if k == "global_motion_mlp.2.weight" else gain_conv if len(wshape) == 4 else (gain_qkv if stem.rsplit(".", 1)[1] in ("q", "kv", "qkv") else gain_linear)
             sd[k] = uni(shp, -1.0, 1.0) * (gain / fan ** 0.5)
     return sd

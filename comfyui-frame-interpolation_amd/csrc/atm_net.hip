@@ -1,6 +1,6 @@
-// ATM-lite (vfi_models/atm/network_lite.py Network, attention.py ATMFormer / RefineBottleneck): the kernels the network needs beyond the
-// shared layer objects and GMFSS ops, and the network object (vfi_atm_create / _forward / ..., at the end of the file) that runs one frame
-// pair over them.
+// ATM-lite and ATM-base (vfi_models/atm/network_lite.py / network_base.py Network, attention.py ATMFormer / RefineBottleneck): the kernels the
+// network needs beyond the shared layer objects and GMFSS ops, and the network object (vfi_atm_create / _create_variant / _forward / ..., at
+// the end of the file) that runs one frame pair over them.  The two models share one forward and one module tree; their widths are kCfg's.
 //
 //   atm_attn            multi-head window attention on token MAPS, 8 heads: centre pad, roll, window cut and their inverses are addressing;
 //                       scores and probabilities live in registers; q k^T and p v on the fp32 matrix cores (v_mfma_f32_16x16x4_f32); the
@@ -301,8 +301,9 @@ int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, i
                              float* out_dev, int out_cs, float* offsets_dev, int h, int w, int C, int window, int shift, int cross, void* stream) {
     VFI_REQUIRE(q_dev && k_dev && v_dev && out_dev && h > 0 && w > 0 && q_cs >= C && k_cs >= C && v_cs >= C && out_cs >= C,
                 "vfi_atm_window_attention: bad arguments");
-    VFI_REQUIRE((C == 224 && window == 8) || (C == 352 && window == 12),
-                "vfi_atm_window_attention: C = %d with window %d: the kernel is built for 224 / 8 and 352 / 12 (8 heads of 28 / 44)", C, window);
+    VFI_REQUIRE(((C == 224 || C == 384) && window == 8) || ((C == 352 || C == 672) && window == 12),
+                "vfi_atm_window_attention: C = %d with window %d: the kernel is built for 224 / 8 and 352 / 12 (ATM-lite: 8 heads of 28 / 44) and for "
+                "384 / 8 and 672 / 12 (ATM-base: 8 heads of 48 / 84)", C, window);
     VFI_REQUIRE(shift == 0 || shift == window / 2, "vfi_atm_window_attention: shift %d must be 0 or half the window (%d)", shift, window / 2);
     VFI_REQUIRE(!offsets_dev || cross, "vfi_atm_window_attention: the motion read-out belongs to the cross kind");
     const int hp = round_up(h, window), wp = round_up(w, window);
@@ -310,12 +311,14 @@ int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, i
     VFI_REQUIRE((long)2 * h * w * 3 * C < (1L << 31) && pad_token < (1L << 31) / (3 * C), "vfi_atm_window_attention: a %dx%d map is beyond the kernel's index arithmetic", h, w);
     TraceScope ts(cross ? "atm_attn_cross" : "atm_attn_self", (hipStream_t)stream);
     const dim3 grid((hp / window) * (wp / window), 2 * kHeads);
-    if (window == 8)
-        hipLaunchKernelGGL((atm_attn_kernel<8, 28>), grid, dim3(256), 0, (hipStream_t)stream, q_dev, q_cs, k_dev, k_cs, v_dev, v_cs, (long)pad_token,
-                           out_dev, out_cs, offsets_dev, h, w, hp, wp, shift, cross, (float)(1.0 / sqrt(28.0)));
-    else
-        hipLaunchKernelGGL((atm_attn_kernel<12, 44>), grid, dim3(256), 0, (hipStream_t)stream, q_dev, q_cs, k_dev, k_cs, v_dev, v_cs, (long)pad_token,
-                           out_dev, out_cs, offsets_dev, h, w, hp, wp, shift, cross, (float)(1.0 / sqrt(44.0)));
+#define ATM_ATTN(WIN, D)                                                                                                                              \
+    hipLaunchKernelGGL((atm_attn_kernel<WIN, D>), grid, dim3(256), 0, (hipStream_t)stream, q_dev, q_cs, k_dev, k_cs, v_dev, v_cs, (long)pad_token, \
+                       out_dev, out_cs, offsets_dev, h, w, hp, wp, shift, cross, (float)(1.0 / sqrt((double)D)))
+    if (C == 224) ATM_ATTN(8, 28);
+    else if (C == 352) ATM_ATTN(12, 44);
+    else if (C == 384) ATM_ATTN(8, 48);
+    else ATM_ATTN(12, 84);
+#undef ATM_ATTN
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -393,15 +396,24 @@ int vfi_atm_refine_out(const float* it_dev, int it_cs, const float* res_dev, int
 
 }  // extern "C"
 
-// ---- the network object: ATM-lite on csrc/net_object.h --------------------------------------------------------------------------------------
+// ---- the network object: ATM-lite / ATM-base on csrc/net_object.h --------------------------------------------------------------------------------------
 
 namespace {
 
-constexpr int kHid[4] = {16, 32, 64, 96};
-constexpr int kLocalC = 224, kGlobalC = 352, kLast = 128, kMotion = 5, kTensors = 232;
-// the widest per-image buffer: the refinement net's input, 61 + 15 channels padded to 80 floats per padded pixel (the layers index one image
-// with 32 bits of bytes)
-constexpr int kPxFloats = 80;
+constexpr int kMotion = 5, kTensors = 232;
+
+// What tells ATM-lite (network_lite.py:88-273) and ATM-base (network_base.py:88-260) apart; the module tree, the 232 tensors and the forward are
+// shared.  local_c = hid[3] + hid[2] + 2 hid[1] tokens on the 1/8 map, last = last_feat_extract's width, global_c = last + hid[3] + 2 hid[2] on
+// the 1/16 map.  px_floats: the widest per-image buffer in floats per padded pixel (the layers index one image with 32 bits of bytes).  lite:
+// the refinement net's input, local_c / 4 + 5 + 15 = 76 channels padded to 80 (its 2 ref_hid = 64-channel concat buffer is narrower).  base:
+// the refinement net's full-resolution concat buffer (up3 | proj), 2 ref_hid = 128 channels; its input is 116 padded to 120, the last
+// up-sampling level's taps r8(4 * 101) / 4 = 102, the 4 C MLP buffers 1536 / 64.
+struct Cfg {
+    int hid[4], local_c, global_c, last, mlp_ratio, local_head, global_head, ref_hid, px_floats;
+    const char* name;
+};
+const Cfg kCfg[2] = {{{16, 32, 64, 96}, 224, 352, 128, 2, 224, 352, 32, 80, "ATM-lite"},
+                     {{24, 48, 96, 192}, 384, 672, 288, 4, 576, 768, 64, 128, "ATM-base"}};
 
 struct Fusion {       // CrossScaleFeatureFusion: three tap-gathered convolutions as 1x1 layers, proj, norm
     vfi_conv_t *l[3] = {}, *proj = nullptr;
@@ -432,7 +444,7 @@ struct vfi_atm : NetObject {
     Up up[3];
     vfi_conv_t *proj = nullptr, *down1 = nullptr, *down2[2] = {}, *down3[3] = {}, *up1d = nullptr, *up1c = nullptr, *up2d = nullptr, *up2c = nullptr,
                *up3d = nullptr, *rh[2] = {};
-    int Hp = 0, Wp = 0;
+    int Hp = 0, Wp = 0, variant = 0;
 };
 
 namespace {
@@ -494,7 +506,8 @@ int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w
     const long ntok = (long)2 * h * w;
     float *xn = r.buf("blk_xn", 1, rows, w, C), *qkv = r.buf("blk_qkv", 1, rows, w, 3 * C), *ao = r.buf("blk_ao", 2, h, w, C);
     float *of = r.buf("blk_offs", 2, h, w, 2 * kHeads), *y = r.buf("blk_y", 2, h, w, C), *t2 = r.buf("blk_t2", 2, h, w, C);
-    float *h1 = r.buf("blk_h1", 2, h, w, 2 * C), *h2 = r.buf("blk_h2", 2, h, w, 2 * C);
+    const int M = kCfg[r.m->variant].mlp_ratio * C;      // Mlp's hidden width
+    float *h1 = r.buf("blk_h1", 2, h, w, M), *h2 = r.buf("blk_h2", 2, h, w, M);
     if (r.bad) return -1;
     ATM_DO(vfi_layernorm(tok, C, C, (int64_t)rows * w, B.n1w, B.n1b, xn, C, r.st));
     if (cross) {
@@ -507,27 +520,30 @@ int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w
     if (cross) ATM_DO(vfi_atm_motion_mlp(of, B.m0w, B.m0b, B.m2w, B.m2b, mot, mot_cs, 2, (int64_t)h * w, r.st));
     ATM_DO(r.conv(B.proj, ao, C, 2 * h, w, y, C, 1, 0, xn, C));      // norm1(x) + proj(attention): the residual is the NORMED token
     ATM_DO(vfi_layernorm(y, C, C, ntok, B.n2w, B.n2b, t2, C, r.st));
-    ATM_DO(r.conv(B.fc1, t2, C, 2 * h, w, h1, 2 * C, 1, 0));
-    ATM_DO(vfi_atm_dwconv3x3_gelu(h1, 2 * C, B.dww, B.dwb, h2, 2 * C, 2, h, w, 2 * C, r.st));
-    return r.conv(B.fc2, h2, 2 * C, 2 * h, w, out, C, 1, 0, y, C);
+    ATM_DO(r.conv(B.fc1, t2, C, 2 * h, w, h1, M, 1, 0));
+    ATM_DO(vfi_atm_dwconv3x3_gelu(h1, M, B.dww, B.dwb, h2, M, 2, h, w, M, r.st));
+    return r.conv(B.fc2, h2, M, 2 * h, w, out, C, 1, 0, y, C);
 }
 
-// two ATM blocks and the motion head: tok -> tok (in place through a second buffer), out5 [h,w,8] = (flow0 xy, flow1 xy, mask logit)
-int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, int h, int w, int C, int win, float* out5) {
+// two ATM blocks and the motion head (hidden width Ch): tok -> tok (in place through a second buffer), out5 [h,w,8] = (flow0 xy, flow1 xy, mask logit)
+int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, int h, int w, int C, int Ch, int win, float* out5) {
     const int mcs = 2 * kHeads / 2 + 2 * C;      // 8 motion channels | frame 0 tokens | frame 1 tokens
-    float *mh = r.buf("mh_in", 1, h, w, mcs), *a = r.buf("mh_a", 1, h, w, C), *b = r.buf("mh_b", 1, h, w, C);
+    float *mh = r.buf("mh_in", 1, h, w, mcs), *a = r.buf("mh_a", 1, h, w, Ch), *b = r.buf("mh_b", 1, h, w, Ch);
     if (r.bad) return -1;
     ATM_DO(run_block(r, B[0], tok, tok2, h, w, C, win, 0, true, mh, mcs));
     ATM_DO(run_block(r, B[1], tok2, tok, h, w, C, win, win / 2, true, mh + 4, mcs));
     const long px = (long)h * w;
     ATM_DO(r.copy(tok, C, mh + 8, mcs, px, C));
     ATM_DO(r.copy(tok + (size_t)px * C, C, mh + 8 + C, mcs, px, C));
-    ATM_DO(r.conv(H.c[0], mh, mcs, h, w, a, C, 1, 3));
-    ATM_DO(r.conv(H.c[1], a, C, h, w, b, C, 1, 3));
-    return r.conv(H.c[2], b, C, h, w, out5, 8, 1, 0);
+    ATM_DO(r.conv(H.c[0], mh, mcs, h, w, a, Ch, 1, 3));
+    ATM_DO(r.conv(H.c[1], a, Ch, h, w, b, Ch, 1, 3));
+    return r.conv(H.c[2], b, Ch, h, w, out5, 8, 1, 0);
 }
 
 int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int W, int global_motion, float* out, hipStream_t st) {
+    const Cfg& g = kCfg[m->variant];
+    const int CL = g.local_c, CG = g.global_c;      // the local / global token widths
+    const int rcs = r8(CL / 4 + kMotion + 15);      // the refinement net's input: 76 -> 80 / 116 -> 120 floats per pixel
     const int Hp = m->Hp, Wp = m->Wp, top = (Hp - H) / 2, left = (Wp - W) / 2;
     const int hs[5] = {Hp, Hp / 2, Hp / 4, Hp / 8, Hp / 16}, wsz[5] = {Wp, Wp / 2, Wp / 4, Wp / 8, Wp / 16};
     const int h8 = hs[3], w8 = wsz[3], h16 = hs[4], w16 = wsz[4];
@@ -540,38 +556,38 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
     hipLaunchKernelGGL(atm_pad_kernel, dim3(nblk((long)Hp * Wp, 256), 2), dim3(256), 0, st, f0, f1, Cf, H, W, pyr[0], Hp, Wp, top, left);
     VFI_CHECK_HIP(hipGetLastError());
     for (int i = 1; i < 4; ++i) ATM_DO(vfi_resize_bilinear_ac(pyr[i - 1], 8, pyr[i], 8, 2, hs[i - 1], wsz[i - 1], hs[i], wsz[i], 3, 1.0f, st));
-    // feature extraction on both frames; the 1/8 map lands in the last 96 channels of the local fusion's concat buffer
-    float* cat_l = r.buf("cat_l", 2, h8, w8, kLocalC);
+    // feature extraction on both frames; the 1/8 map lands in the last hid[3] channels of the local fusion's concat buffer
+    float* cat_l = r.buf("cat_l", 2, h8, w8, CL);
     float* feat[3];
     {
         const float* x = pyr[0];
         int xcs = 8;
         const char *an[4] = {"fe_a0", "fe_a1", "fe_a2", "fe_a3"}, *fn[3] = {"fe_f0", "fe_f1", "fe_f2"};
         for (int i = 0; i < 4; ++i) {
-            const int hi = i ? hs[i - 1] : Hp, wi = i ? wsz[i - 1] : Wp, c = kHid[i];
+            const int hi = i ? hs[i - 1] : Hp, wi = i ? wsz[i - 1] : Wp, c = g.hid[i];
             float* a = r.buf(an[i], 2, hs[i], wsz[i], c);
-            float* f = i < 3 ? r.buf(fn[i], 2, hs[i], wsz[i], c) : cat_l + (kLocalC - kHid[3]);
+            float* f = i < 3 ? r.buf(fn[i], 2, hs[i], wsz[i], c) : cat_l + (CL - g.hid[3]);
             if (r.bad) return -1;
             ATM_DO(r.conv(m->fe[i][0], x, xcs, hi, wi, a, c, 2, 3));
-            ATM_DO(r.conv(m->fe[i][1], a, c, hs[i], wsz[i], f, i < 3 ? c : kLocalC, 2, 3));
+            ATM_DO(r.conv(m->fe[i][1], a, c, hs[i], wsz[i], f, i < 3 ? c : CL, 2, 3));
             if (i < 3) feat[i] = f;
-            x = f, xcs = i < 3 ? c : kLocalC;
+            x = f, xcs = i < 3 ? c : CL;
         }
     }
-    const float* f3 = cat_l + (kLocalC - kHid[3]);
-    float *tok = r.buf("tok_a", 1, 2 * h8 + 1, w8, kLocalC), *tok2 = r.buf("tok_b", 1, 2 * h8 + 1, w8, kLocalC);
+    const float* f3 = cat_l + (CL - g.hid[3]);
+    float *tok = r.buf("tok_a", 1, 2 * h8 + 1, w8, CL), *tok2 = r.buf("tok_b", 1, 2 * h8 + 1, w8, CL);
     if (r.bad) return -1;
-    ATM_DO(run_fusion(r, m->lf, feat[1], kHid[1], kHid[1], feat[2], kHid[2], kHid[2], cat_l, kLocalC, h8, w8, tok));
+    ATM_DO(run_fusion(r, m->lf, feat[1], g.hid[1], g.hid[1], feat[2], g.hid[2], g.hid[2], cat_l, CL, h8, w8, tok));
     const float *src0 = pyr[0], *src1 = pyr[0] + (size_t)Hp * Wp * 8;      // what the last synthesis step warps
     if (global_motion) {
-        float *g0 = r.buf("gl_a", 2, h16, w16, kLast), *cat_g = r.buf("cat_g", 2, h16, w16, kGlobalC);
-        float *gtok = r.buf("gtok_a", 1, 2 * h16 + 1, w16, kGlobalC), *gtok2 = r.buf("gtok_b", 1, 2 * h16 + 1, w16, kGlobalC);
+        float *g0 = r.buf("gl_a", 2, h16, w16, g.last), *cat_g = r.buf("cat_g", 2, h16, w16, CG);
+        float *gtok = r.buf("gtok_a", 1, 2 * h16 + 1, w16, CG), *gtok2 = r.buf("gtok_b", 1, 2 * h16 + 1, w16, CG);
         float* g5 = r.buf("gl_out5", 1, h16, w16, 8);
         if (r.bad) return -1;
-        ATM_DO(r.conv(m->last[0], f3, kLocalC, h8, w8, g0, kLast, 2, 3));
-        ATM_DO(r.conv(m->last[1], g0, kLast, h16, w16, cat_g + (kGlobalC - kLast), kGlobalC, 2, 3));
-        ATM_DO(run_fusion(r, m->gf, feat[2], kHid[2], kHid[2], f3, kLocalC, kHid[3], cat_g, kGlobalC, h16, w16, gtok));
-        ATM_DO(run_motion(r, m->glo, m->gh, gtok, gtok2, h16, w16, kGlobalC, 12, g5));
+        ATM_DO(r.conv(m->last[0], f3, CL, h8, w8, g0, g.last, 2, 3));
+        ATM_DO(r.conv(m->last[1], g0, g.last, h16, w16, cat_g + (CG - g.last), CG, 2, 3));
+        ATM_DO(run_fusion(r, m->gf, feat[2], g.hid[2], g.hid[2], f3, CL, g.hid[3], cat_g, CG, h16, w16, gtok));
+        ATM_DO(run_motion(r, m->glo, m->gh, gtok, gtok2, h16, w16, CG, g.global_head, 12, g5));
         // the global flows, x2 per level up to full resolution; the tokens and every pyramid level are warped by them
         float* fl[4];
         const char* fl_names[4] = {"gl_fl0", "gl_fl1", "gl_fl2", "gl_fl3"};
@@ -582,8 +598,8 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
         if (r.bad) return -1;
         ATM_DO(vfi_resize_bilinear_ac(g5, 8, fl[3], 4, 1, h16, w16, h8, w8, 4, 2.0f, st));
         const size_t p8 = (size_t)h8 * w8;
-        ATM_DO(vfi_flow_sample(tok, kLocalC, fl[3], 4, tok2, kLocalC, 1, h8, w8, kLocalC, st));
-        ATM_DO(vfi_flow_sample(tok + p8 * kLocalC, kLocalC, fl[3] + 2, 4, tok2 + p8 * kLocalC, kLocalC, 1, h8, w8, kLocalC, st));
+        ATM_DO(vfi_flow_sample(tok, CL, fl[3], 4, tok2, CL, 1, h8, w8, CL, st));
+        ATM_DO(vfi_flow_sample(tok + p8 * CL, CL, fl[3] + 2, 4, tok2 + p8 * CL, CL, 1, h8, w8, CL, st));
         float* t = tok;
         tok = tok2, tok2 = t;
         for (int i = 3; i >= 0; --i) {
@@ -597,22 +613,22 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
     // local motion, feature enhancement
     float* o5 = r.buf("lo_out5", 1, h8, w8, 8);
     if (r.bad) return -1;
-    ATM_DO(run_motion(r, m->loc, m->lh, tok, tok2, h8, w8, kLocalC, 8, o5));
-    ATM_DO(run_block(r, m->enh[0], tok, tok2, h8, w8, kLocalC, 8, 0, false, nullptr, 0));
-    ATM_DO(run_block(r, m->enh[1], tok2, tok, h8, w8, kLocalC, 8, 4, false, nullptr, 0));
+    ATM_DO(run_motion(r, m->loc, m->lh, tok, tok2, h8, w8, CL, g.local_head, 8, o5));
+    ATM_DO(run_block(r, m->enh[0], tok, tok2, h8, w8, CL, 8, 0, false, nullptr, 0));
+    ATM_DO(run_block(r, m->enh[1], tok2, tok, h8, w8, CL, 8, 4, false, nullptr, 0));
     // (warped frame 0 tokens | warped frame 1 tokens | the 5 motion channels), then the three up-sampling levels
-    const int c0cs = r8(2 * kLocalC + kMotion);
+    const int c0cs = r8(2 * CL + kMotion);
     float* fcat = r.buf("up_in", 1, h8, w8, c0cs);
     if (r.bad) return -1;
     {
         const size_t p8 = (size_t)h8 * w8;
-        ATM_DO(vfi_flow_sample(tok, kLocalC, o5, 8, fcat, c0cs, 1, h8, w8, kLocalC, st));
-        ATM_DO(vfi_flow_sample(tok + p8 * kLocalC, kLocalC, o5 + 2, 8, fcat + kLocalC, c0cs, 1, h8, w8, kLocalC, st));
-        ATM_DO(r.copy(o5, 8, fcat + 2 * kLocalC, c0cs, (long)p8, kMotion));
+        ATM_DO(vfi_flow_sample(tok, CL, o5, 8, fcat, c0cs, 1, h8, w8, CL, st));
+        ATM_DO(vfi_flow_sample(tok + p8 * CL, CL, o5 + 2, 8, fcat + CL, c0cs, 1, h8, w8, CL, st));
+        ATM_DO(r.copy(o5, 8, fcat + 2 * CL, c0cs, (long)p8, kMotion));
     }
-    float* R = r.buf("ref_in", 1, Hp, Wp, kPxFloats);      // (feat 61 | im0 | warped 0 | im1 | warped 1 | I_t)
+    float* R = r.buf("ref_in", 1, Hp, Wp, rcs);      // (feat local_c / 4 + 5 | im0 | warped 0 | im1 | warped 1 | I_t)
     float* lvl[3] = {nullptr, nullptr, R};
-    int lcs[3] = {0, 0, kPxFloats};
+    int lcs[3] = {0, 0, rcs};
     {
         const float* x = fcat;
         int xcs = c0cs;
@@ -635,33 +651,35 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
             x = lvl[i], xcs = lcs[i];
         }
     }
-    const int fc = kLocalC / 4 + kMotion;      // 61
-    ATM_DO(vfi_atm_blend_warps(src0, src1, 8, pyr[0], pyr[0] + (size_t)Hp * Wp * 8, 8, R + fc - kMotion, kPxFloats, R + fc, kPxFloats, Hp, Wp, st));
-    // residual refinement (network_lite.py:409-423); concat buffers: c6 = (u0 | r0), c2 = (r1 | skip 1/2), c3 = (r2 | skip 1/4), c4 = (u2 | r2), c5 = (u1 | r1)
+    const int fc = CL / 4 + kMotion;      // 61 / 101
+    ATM_DO(vfi_atm_blend_warps(src0, src1, 8, pyr[0], pyr[0] + (size_t)Hp * Wp * 8, 8, R + fc - kMotion, rcs, R + fc, rcs, Hp, Wp, st));
+    // residual refinement (network_lite.py:409-423), hidden width hd; concat buffers: c6 = (u0 | r0), c2 = (r1 | skip 1/2), c3 = (r2 | skip 1/4),
+    // c4 = (u2 | r2), c5 = (u1 | r1)
     const int h2 = hs[1], w2 = wsz[1], h4 = hs[2], w4 = wsz[2];
-    float *c6 = r.buf("rf_c6", 1, Hp, Wp, 64), *c2 = r.buf("rf_c2", 1, h2, w2, 144), *c3 = r.buf("rf_c3", 1, h4, w4, 288), *c4 = r.buf("rf_c4", 1, h4, w4, 128);
-    float *c5 = r.buf("rf_c5", 1, h2, w2, 64), *d2 = r.buf("rf_d2", 1, h4, w4, 64), *d3a = r.buf("rf_d3a", 1, h8, w8, 128), *d3b = r.buf("rf_d3b", 1, h8, w8, 128);
-    float *u2 = r.buf("rf_u2", 1, h4, w4, 64), *u1 = r.buf("rf_u1", 1, h2, w2, 64), *rh = r.buf("rf_h", 1, Hp, Wp, 32), *res = r.buf("rf_res", 1, Hp, Wp, 8);
+    const int hd = g.ref_hid, s2 = hd + CL / 2, s3 = 2 * hd + CL;      // the channel strides of c2 and c3
+    float *c6 = r.buf("rf_c6", 1, Hp, Wp, 2 * hd), *c2 = r.buf("rf_c2", 1, h2, w2, s2), *c3 = r.buf("rf_c3", 1, h4, w4, s3), *c4 = r.buf("rf_c4", 1, h4, w4, 4 * hd);
+    float *c5 = r.buf("rf_c5", 1, h2, w2, 2 * hd), *d2 = r.buf("rf_d2", 1, h4, w4, 2 * hd), *d3a = r.buf("rf_d3a", 1, h8, w8, 4 * hd), *d3b = r.buf("rf_d3b", 1, h8, w8, 4 * hd);
+    float *u2 = r.buf("rf_u2", 1, h4, w4, 2 * hd), *u1 = r.buf("rf_u1", 1, h2, w2, 2 * hd), *rh = r.buf("rf_h", 1, Hp, Wp, hd), *res = r.buf("rf_res", 1, Hp, Wp, 8);
     if (r.bad) return -1;
-    ATM_DO(r.conv(m->proj, R, kPxFloats, Hp, Wp, c6 + 32, 64, 1, 3));
-    ATM_DO(r.conv(m->down1, c6 + 32, 64, Hp, Wp, c2, 144, 1, 3));
-    ATM_DO(r.copy(lvl[1], lcs[1], c2 + 32, 144, (long)h2 * w2, kLocalC / 2));
-    ATM_DO(r.conv(m->down2[0], c2, 144, h2, w2, d2, 64, 1, 3));
-    ATM_DO(r.conv(m->down2[1], d2, 64, h4, w4, c3, 288, 1, 3));
-    ATM_DO(r.copy(lvl[0], lcs[0], c3 + 64, 288, (long)h4 * w4, kLocalC));
-    ATM_DO(r.copy(c3, 288, c4 + 64, 128, (long)h4 * w4, 64));
-    ATM_DO(r.copy(c2, 144, c5 + 32, 64, (long)h2 * w2, 32));
-    ATM_DO(r.conv(m->down3[0], c3, 288, h4, w4, d3a, 128, 1, 3));
-    ATM_DO(r.conv(m->down3[1], d3a, 128, h8, w8, d3b, 128, 1, 3));
-    ATM_DO(r.conv(m->down3[2], d3b, 128, h8, w8, d3a, 128, 1, 3));
-    ATM_DO(r.deconv(m->up1d, 64, d3a, 128, h8, w8, u2, 64));
-    ATM_DO(r.conv(m->up1c, u2, 64, h4, w4, c4, 128, 1, 3));
-    ATM_DO(r.deconv(m->up2d, 64, c4, 128, h4, w4, u1, 64));
-    ATM_DO(r.conv(m->up2c, u1, 64, h2, w2, c5, 64, 1, 3));
-    ATM_DO(r.deconv(m->up3d, 32, c5, 64, h2, w2, c6, 64));
-    ATM_DO(r.conv(m->rh[0], c6, 64, Hp, Wp, rh, 32, 1, 3));
-    ATM_DO(r.conv(m->rh[1], rh, 32, Hp, Wp, res, 8, 1, 3));
-    return vfi_atm_refine_out(R + fc + 12, kPxFloats, res, 8, out, Hp, Wp, top, left, H, W, st);
+    ATM_DO(r.conv(m->proj, R, rcs, Hp, Wp, c6 + hd, 2 * hd, 1, 3));
+    ATM_DO(r.conv(m->down1, c6 + hd, 2 * hd, Hp, Wp, c2, s2, 1, 3));
+    ATM_DO(r.copy(lvl[1], lcs[1], c2 + hd, s2, (long)h2 * w2, CL / 2));
+    ATM_DO(r.conv(m->down2[0], c2, s2, h2, w2, d2, 2 * hd, 1, 3));
+    ATM_DO(r.conv(m->down2[1], d2, 2 * hd, h4, w4, c3, s3, 1, 3));
+    ATM_DO(r.copy(lvl[0], lcs[0], c3 + 2 * hd, s3, (long)h4 * w4, CL));
+    ATM_DO(r.copy(c3, s3, c4 + 2 * hd, 4 * hd, (long)h4 * w4, 2 * hd));
+    ATM_DO(r.copy(c2, s2, c5 + hd, 2 * hd, (long)h2 * w2, hd));
+    ATM_DO(r.conv(m->down3[0], c3, s3, h4, w4, d3a, 4 * hd, 1, 3));
+    ATM_DO(r.conv(m->down3[1], d3a, 4 * hd, h8, w8, d3b, 4 * hd, 1, 3));
+    ATM_DO(r.conv(m->down3[2], d3b, 4 * hd, h8, w8, d3a, 4 * hd, 1, 3));
+    ATM_DO(r.deconv(m->up1d, 2 * hd, d3a, 4 * hd, h8, w8, u2, 2 * hd));
+    ATM_DO(r.conv(m->up1c, u2, 2 * hd, h4, w4, c4, 4 * hd, 1, 3));
+    ATM_DO(r.deconv(m->up2d, 2 * hd, c4, 4 * hd, h4, w4, u1, 2 * hd));
+    ATM_DO(r.conv(m->up2c, u1, 2 * hd, h2, w2, c5, 2 * hd, 1, 3));
+    ATM_DO(r.deconv(m->up3d, hd, c5, 2 * hd, h2, w2, c6, 2 * hd));
+    ATM_DO(r.conv(m->rh[0], c6, 2 * hd, Hp, Wp, rh, hd, 1, 3));
+    ATM_DO(r.conv(m->rh[1], rh, hd, Hp, Wp, res, 8, 1, 3));
+    return vfi_atm_refine_out(R + fc + 12, rcs, res, 8, out, Hp, Wp, top, left, H, W, st);
 }
 
 int atm_pad64(int n) { return n + (((n / 64) + 1) * 64 - n) % 64; }
@@ -670,15 +688,25 @@ int atm_pad64(int n) { return n + (((n / 64) + 1) * 64 - n) % 64; }
 
 extern "C" {
 
-int64_t vfi_atm_max_padded_pixels(void) { return (int64_t)(0x7fffffffL / (kPxFloats * 4)); }
+int64_t vfi_atm_max_padded_pixels(void) { return (int64_t)(0x7fffffffL / (kCfg[0].px_floats * 4)); }
 
-vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors) {
-    if (!tensors || !numels || n_tensors != kTensors) {
-        set_error("vfi_atm_create: expected the %d weight tensors of ATM-lite in atm_spec.weight_shapes() order, got %d", kTensors, n_tensors);
+int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* m) { return m ? (int64_t)(0x7fffffffL / (kCfg[m->variant].px_floats * 4)) : 0; }
+
+vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors) { return vfi_atm_create_variant(tensors, numels, n_tensors, 0); }
+
+vfi_atm_t* vfi_atm_create_variant(const float* const* tensors, const int64_t* numels, int n_tensors, int variant) {
+    const bool known = variant == 0 || variant == 1;
+    if (!tensors || !numels || !known || n_tensors != kTensors) {
+        set_error("vfi_atm_create: expected the %d weight tensors of %s in atm_spec.weight_shapes() order (variant 0 = ATM-lite, 1 = ATM-base), got %d "
+                  "(variant %d)", kTensors, known ? kCfg[variant].name : "ATM-?", n_tensors, variant);
         return nullptr;
     }
+    const Cfg& g = kCfg[variant];
+    const int CL = g.local_c, CG = g.global_c;
     vfi_atm* m = new vfi_atm();
-    TensorCursor cur(tensors, numels, n_tensors, "vfi_atm_create");
+    m->variant = variant;
+    // both variants have 232 tensors: the per-tensor element counts are what tells a file of the other model
+    TensorCursor cur(tensors, numels, n_tensors, variant ? "vfi_atm_create (ATM-base)" : "vfi_atm_create (ATM-lite)");
     std::vector<float> tmp, tb, tp;
     // Conv2d(cin, cout, k, stride, padding k / 2) with bias [+ PReLU]
     auto conv = [&](int cout, int cin, int k, int stride, bool prelu, bool bias = true) -> vfi_conv_t* {
@@ -724,16 +752,17 @@ vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, in
     };
     auto mlp = [&](Block& B, int C) {
         B.n2w = vec(C), B.n2b = vec(C);
-        B.fc1 = conv(2 * C, C, 1, 1, false);
-        const float* w = cur.take((int64_t)2 * C * 9);
+        const int M = g.mlp_ratio * C;
+        B.fc1 = conv(M, C, 1, 1, false);
+        const float* w = cur.take((int64_t)M * 9);
         if (w) {
-            tmp.assign((size_t)9 * 2 * C, 0.f);
-            for (int c = 0; c < 2 * C; ++c)
-                for (int t = 0; t < 9; ++t) tmp[(size_t)t * 2 * C + c] = w[(size_t)c * 9 + t];
+            tmp.assign((size_t)9 * M, 0.f);
+            for (int c = 0; c < M; ++c)
+                for (int t = 0; t < 9; ++t) tmp[(size_t)t * M + c] = w[(size_t)c * 9 + t];
             B.dww = m->upload(tmp.data(), tmp.size());
         }
-        B.dwb = vec(2 * C);
-        B.fc2 = conv(C, 2 * C, 1, 1, false);
+        B.dwb = vec(M);
+        B.fc2 = conv(C, M, 1, 1, false);
     };
     auto atmformer = [&](Block& B, int C) {
         B.n1w = vec(C), B.n1b = vec(C);
@@ -743,48 +772,48 @@ vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, in
         B.m0w = vec(kHeads / 2 * kHeads), B.m0b = vec(kHeads / 2), B.m2w = vec(kHeads / 2), B.m2b = vec(1);
         mlp(B, C);
     };
-    auto head = [&](Head& Hd, int C) {
-        Hd.c[0] = conv(C, 2 * C + kHeads, 3, 1, true);
-        Hd.c[1] = conv(C, C, 3, 1, true);
-        Hd.c[2] = conv(kMotion, C, 1, 1, false);
+    auto head = [&](Head& Hd, int C, int Ch) {
+        Hd.c[0] = conv(Ch, 2 * C + kHeads, 3, 1, true);
+        Hd.c[1] = conv(Ch, Ch, 3, 1, true);
+        Hd.c[2] = conv(kMotion, Ch, 1, 1, false);
     };
     int prev = 3;
     for (int i = 0; i < 4; ++i) {
-        m->fe[i][0] = conv(kHid[i], prev, 3, i ? 2 : 1, true);
-        m->fe[i][1] = conv(kHid[i], kHid[i], 3, 1, true);
-        prev = kHid[i];
+        m->fe[i][0] = conv(g.hid[i], prev, 3, i ? 2 : 1, true);
+        m->fe[i][1] = conv(g.hid[i], g.hid[i], 3, 1, true);
+        prev = g.hid[i];
     }
-    fusion(m->lf, kHid[1], kHid[2], kLocalC);
+    fusion(m->lf, g.hid[1], g.hid[2], CL);
     for (int k = 0; k < 2; ++k) {
         Block& B = m->enh[k];
-        B.n1w = vec(kLocalC), B.n1b = vec(kLocalC);
-        B.qkv = conv(3 * kLocalC, kLocalC, 1, 1, false, false);
-        B.proj = conv(kLocalC, kLocalC, 1, 1, false);
-        mlp(B, kLocalC);
+        B.n1w = vec(CL), B.n1b = vec(CL);
+        B.qkv = conv(3 * CL, CL, 1, 1, false, false);
+        B.proj = conv(CL, CL, 1, 1, false);
+        mlp(B, CL);
     }
-    for (int k = 0; k < 2; ++k) atmformer(m->loc[k], kLocalC);
-    head(m->lh, kLocalC);
-    m->last[0] = conv(kLast, kHid[3], 3, 2, true);
-    m->last[1] = conv(kLast, kLast, 3, 1, true);
-    fusion(m->gf, kHid[2], kHid[3], kGlobalC);
-    for (int k = 0; k < 2; ++k) atmformer(m->glo[k], kGlobalC);
-    head(m->gh, kGlobalC);
-    int cin = 2 * kLocalC + kMotion;
+    for (int k = 0; k < 2; ++k) atmformer(m->loc[k], CL);
+    head(m->lh, CL, g.local_head);
+    m->last[0] = conv(g.last, g.hid[3], 3, 2, true);
+    m->last[1] = conv(g.last, g.last, 3, 1, true);
+    fusion(m->gf, g.hid[2], g.hid[3], CG);
+    for (int k = 0; k < 2; ++k) atmformer(m->glo[k], CG);
+    head(m->gh, CG, g.global_head);
+    int cin = 2 * CL + kMotion;
     for (int i = 0; i < 3; ++i) {
         Up& U = m->up[i];
-        U.cin = cin, U.c = (kLocalC >> i) + kMotion;
+        U.cin = cin, U.c = (CL >> i) + kMotion;
         if (i) U.pre = vec(cin);
         U.de = deconv(cin, U.c);
         U.c1 = conv(U.c, U.c, 3, 1, true);
         U.c2 = conv(U.c, U.c, 3, 1, false);
         cin = U.c;
     }
-    const int hid = 32;
-    m->proj = conv(hid, kLocalC / 4 + kMotion + 15, 3, 1, true);
+    const int hid = g.ref_hid;
+    m->proj = conv(hid, CL / 4 + kMotion + 15, 3, 1, true);
     m->down1 = conv(hid, hid, 3, 2, true);
-    m->down2[0] = conv(2 * hid, kLocalC / 2 + hid, 3, 2, true);
+    m->down2[0] = conv(2 * hid, CL / 2 + hid, 3, 2, true);
     m->down2[1] = conv(2 * hid, 2 * hid, 3, 1, true);
-    m->down3[0] = conv(4 * hid, kLocalC + 2 * hid, 3, 2, true);
+    m->down3[0] = conv(4 * hid, CL + 2 * hid, 3, 2, true);
     m->down3[1] = conv(4 * hid, 4 * hid, 3, 1, true);
     m->down3[2] = conv(4 * hid, 4 * hid, 3, 1, true);
     m->up1d = deconv(4 * hid, 2 * hid);
@@ -814,9 +843,9 @@ int vfi_atm_forward(vfi_atm_t* m, const float* frame0_dev, const float* frame1_d
     VFI_REQUIRE(m && frame0_dev && frame1_dev && out_dev && C >= 3 && H > 0 && W > 0 && (global_motion == 0 || global_motion == 1),
                 "vfi_atm_forward: bad arguments (global_motion %d: 0 off, 1 on; the multi-scale ensemble is not built)", global_motion);
     const int Hp = atm_pad64(H), Wp = atm_pad64(W);
-    VFI_REQUIRE((int64_t)Hp * Wp <= vfi_atm_max_padded_pixels(),
-                "vfi_atm_forward: a %dx%d frame (padded %dx%d) is over the size limit: Hp * Wp * %d bytes must stay below 2 GiB for the layers' index "
-                "arithmetic (1088x1920 fits)", H, W, Hp, Wp, kPxFloats * 4);
+    VFI_REQUIRE((int64_t)Hp * Wp <= vfi_atm_object_max_padded_pixels(m),
+                "vfi_atm_forward: a %dx%d frame (padded %dx%d) is over the size limit of %s: Hp * Wp * %d bytes must stay below 2 GiB for the layers' "
+                "index arithmetic (1088x1920 fits)", H, W, Hp, Wp, kCfg[m->variant].name, kCfg[m->variant].px_floats * 4);
     if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp) && m->ws.release()) return -1;
     m->Hp = Hp, m->Wp = Wp;
     return atm_forward(m, frame0_dev, frame1_dev, C, H, W, global_motion, out_dev, (hipStream_t)stream);

@@ -736,12 +736,13 @@ int vfi_amt_forward(vfi_amt_t* net, const float* frame0_dev, const float* frame1
 int vfi_amt_release_workspace(vfi_amt_t* net);
 int64_t vfi_amt_workspace_bytes(const vfi_amt_t* net);
 
-/* ---- ATM-lite (vfi_models/atm/network_lite.py Network, attention.py): the kernels beside the layer objects and the GMFSS ops ------------------ */
+/* ---- ATM-lite / ATM-base (vfi_models/atm/network_lite.py, network_base.py Network, attention.py): the kernels beside the layer objects and the GMFSS ops */
 
 /* Multi-head (8) attention over fixed windows of token MAPS, for both windowed blocks of ATM: cross != 0 is AttentionToMotion inside ATMFormer
  * (attention.py:187-213, :265-334: q of frame f against k, v of frame f ^ 1, same window), cross == 0 is WindowAttention inside RefineBottleneck
  * (:370-390, :433-495).  q / k / v_dev: channel windows (C channels, head hd at hd * C / 8) of token maps holding the two frames' h x w tokens
- * back to back (token (f h + y) w + x), already normed (norm1) and projected; (C, window) = (224, 8) or (352, 12); shift = 0 or window / 2.
+ * back to back (token (f h + y) w + x), already normed (norm1) and projected; (C, window) = (224, 8) or (352, 12) (ATM-lite), (384, 8) or (672, 12)
+ * (ATM-base), every other pair is refused; shift = 0 or window / 2.
  * pad_if_needed's centre padding to a window multiple, torch.roll by -shift, window_partition and their inverses (:8-71, :275-277, :313, :323-331)
  * are the kernel's addressing: no padded, rolled or partitioned copy exists; a window slot outside the map reads token `pad_token` of q / k / v
  * (the caller keeps one zero token behind the maps, so that after norm1 and the projections it is what the reference's zero padding becomes;
@@ -781,14 +782,23 @@ typedef struct vfi_atm vfi_atm_t;
 /* The 232 weight tensors of ATM-lite in atm_spec.weight_shapes() order = the state dict of network_lite.Network without its four relative_coord
  * buffers (fp32 host memory, copied).  Replaces Network() + load_state_dict (vfi_models/atm/__init__.py:115-142). */
 vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors);
+/* The same for either model: variant 0 = ATM-lite (what vfi_atm_create makes), 1 = ATM-base (network_base.Network: hidden_dims 24 / 48 / 96 / 192,
+ * 384 / 672-wide tokens, mlp_ratio 4, motion heads 576 / 768 wide, refinement width 64).  Both state dicts have the same 232 names in the same
+ * order, so a file of the other model is told by its per-tensor element counts: NULL, with an error that names the variant. */
+vfi_atm_t* vfi_atm_create_variant(const float* const* tensors, const int64_t* numels, int n_tensors, int variant);
 void vfi_atm_destroy(vfi_atm_t* net);
 /* Network.forward_normal (network_lite.py:425-538)["I_t"] for ONE pair: frames [H,W,C>=3] fp32 (not written) are padded to multiples of 64
  * (centred, replicate: InputPadder(dims, 64), atm/__init__.py:11-34, :62-68), out_dev [H,W,3] is the un-padded result, clamped to [0, 1].
  * global_motion: 1 = "On", 0 = "Off (fastest)" (:76-80); the multi-scale ensemble is not built.  A frame whose padded size exceeds
  * vfi_atm_max_padded_pixels() = (2^31 - 1) / 320 = 6 710 886 pixels is refused before any launch: the widest per-image buffer (the refinement
- * net's input, 76 channels padded to 80) has 320 bytes per padded pixel and the layers index an image with 32 bits (1088 x 1920 fits). */
+ * net's input, 76 channels padded to 80) has 320 bytes per padded pixel and the layers index an image with 32 bits (1088 x 1920 fits).  That
+ * is ATM-lite's limit; the limit that vfi_atm_forward applies is the object's own, vfi_atm_object_max_padded_pixels(net): for ATM-base
+ * (2^31 - 1) / 512 = 4 194 303 pixels, its widest per-image buffer being the refinement net's full-resolution concat buffer of 2 * 64 = 128
+ * channels (its input is 116 channels padded to 120, the last transposed convolution's taps r8(4 * 101) / 4 = 102 floats per full-resolution
+ * pixel, the 4 C MLP buffers 1536 / 64): 1472 x 2560 fits, 2176 x 3840 does not. */
 int vfi_atm_forward(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream);
 int64_t vfi_atm_max_padded_pixels(void);
+int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* net);
 int vfi_atm_release_workspace(vfi_atm_t* net);
 int64_t vfi_atm_workspace_bytes(const vfi_atm_t* net);
 

@@ -1,13 +1,13 @@
-"""Device-resident ATM-lite at 1080p (one vfi_atm_forward per new frame), seeded weights.
+"""Device-resident ATM-lite or ATM-base at 1080p (one vfi_atm_forward per new frame), seeded weights.
 
-    python tools/atm_bench.py [--iters 5] [--height 1080 --width 1920] [--no-parity] [--out profiles/atm_bench.json]
+    python tools/atm_bench.py [--variant lite|base] [--iters 5] [--height 1080 --width 1920] [--no-parity] [--out profiles/atm_bench.json]
 
-Prints one JSON line (and writes it to --out).  Per global-motion mode ("On", "Off (fastest)"): ms per new frame, the median of `iters`
+Prints one JSON line (and writes it to --out: lite's result is the file's top level, base's its "base" entry; the other one is kept).  Per global-motion mode ("On", "Off (fastest)"): ms per new frame, the median of `iters`
 forward calls timed with device events around the call (frames already on the device, workspace allocated by two warm-up calls); the
 workspace size; the library's per-kernel event trace (vfi_trace_*) of one extra call: the share of the new kernels (atm_attn_cross,
 atm_attn_self, atm_motion_mlp, atm_dwconv, atm_gather_taps, atm_depth_to_space, atm_blend, atm_out) and of the layer objects; and, unless
---no-parity, the in-run parity of the timed frame against the float32 restatement (tests/atm_restated.py) on the CPU: max |d| over every
-pixel, asserted <= 1e-3."""
+--no-parity, the in-run parity of the timed frame against the float32 restatement (tests/atm_restated.py, tests/atm_base_restated.py) on the
+CPU: max |d| over every pixel, asserted <= 1e-3."""
 import argparse
 import ctypes as C
 import json
@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", choices=("lite", "base"), default="lite")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
@@ -34,9 +35,10 @@ def main():
     from pkgload import load_package
 
     load_package()
+    import atm_base_restated
     import atm_restated
     import cain_restated
-    from cfi_amd import _lib
+    from cfi_amd import _lib, ckpt
     from cfi_amd.atm import AtmEngine, padded_size
     from cfi_amd.atm_spec import seeded_state_dict
 
@@ -44,8 +46,11 @@ def main():
     Hp, Wp = padded_size(H, W)
     frames = cain_restated.seeded_frames(2, H, W, 3, 31)
     f = frames.cuda()
-    res = {"workload": f"atm-lite {H}x{W} (padded {Hp}x{Wp}), device-resident, ms per new frame", "iters": args.iters}
-    eng = AtmEngine(seeded_state_dict(atm_restated.SEED))
+    res = {"workload": f"atm-{args.variant} {H}x{W} (padded {Hp}x{Wp}), device-resident, ms per new frame", "iters": args.iters}
+    restated = atm_restated
+    if args.variant == "base":      # opt-in: the tool turns the key on for itself
+        restated, ckpt.load_config = atm_base_restated, atm_base_restated.config_with(True)
+    eng = AtmEngine(seeded_state_dict(atm_restated.SEED, args.variant), args.variant)
     lib = _lib.load()
     torch.set_num_threads(max(1, min(32, os.cpu_count() or 1)))
     for mode, gm in atm_restated.MODES.items():
@@ -54,7 +59,7 @@ def main():
         for _ in range(2):
             call()
         torch.cuda.synchronize()
-        assert torch.isfinite(out).all(), f"ATM-lite at {H}x{W}, {mode}: non-finite output"
+        assert torch.isfinite(out).all(), f"ATM-{args.variant} at {H}x{W}, {mode}: non-finite output"
         samples = []
         for _ in range(args.iters):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,19 +89,24 @@ def main():
         r["trace_new_kernels"] = {k: [v[0], round(v[1], 3), round(v[1] / total, 3)] for k, v in rows.items() if k.startswith("atm_")}
         r["trace_layer_objects_share"] = round(sum(v[1] for k, v in rows.items() if k.startswith(("conv", "deconv"))) / total, 3)
         r["trace_rows"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rows.items(), key=lambda kv: -kv[1][1])[:12]}
+        print(f"{mode}: {r['ms_per_frame']} ms per frame, workspace {r['workspace_bytes']} bytes", file=sys.stderr, flush=True)
         if not args.no_parity:
             x = frames.permute(0, 3, 1, 2).contiguous()
             with torch.no_grad():
-                want = atm_restated.atm_frame(atm_restated.state_dict_as(torch.float32), x[0:1], x[1:2], gm)[0].permute(1, 2, 0)
+                want = restated.atm_frame(restated.state_dict_as(torch.float32), x[0:1], x[1:2], gm)[0].permute(1, 2, 0)
             r["parity_max_abs_vs_float32_restatement"] = float((out.cpu() - want).abs().max())
             assert r["parity_max_abs_vs_float32_restatement"] <= atm_restated.TOL, r
         res[mode] = r
     eng.close()
-    line = json.dumps(res)
-    print(line)
+    print(json.dumps(res))
     if args.out:
+        doc = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                doc = json.load(fh)
+        doc = dict(res, **({"base": doc["base"]} if "base" in doc else {})) if args.variant == "lite" else dict(doc, base=res)
         with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+            fh.write(json.dumps(doc) + "\n")
 
 
 if __name__ == "__main__":
