@@ -544,8 +544,9 @@ int vfi_conv_forward(const vfi_conv_t* c, const float* in_dev, int in_cs, float*
 }
 
 int vfi_avgpool2(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int H, int W, int C, void* stream) {
-    VFI_REQUIRE(in_dev && out_dev && C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0 && H >= 2 && W >= 2,
+    VFI_REQUIRE(in_dev && out_dev && N > 0 && C > 0 && C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0 && in_cs >= C && out_cs >= C && H >= 2 && W >= 2,
                 "vfi_avgpool2: bad arguments (C, strides multiples of 4)");
+    VFI_REQUIRE((((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0, "vfi_avgpool2: channel windows must be 16-byte aligned");
     const long n = (long)N * (H / 2) * (W / 2) * (C / 4);
     TraceScope ts("avgpool2", (hipStream_t)stream);
     hipLaunchKernelGGL(avgpool2_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, out_dev, out_cs, N, H, W, C / 4);
@@ -555,7 +556,10 @@ int vfi_avgpool2(const float* in_dev, int in_cs, float* out_dev, int out_cs, int
 
 int vfi_upsample_nearest(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int Hin, int Win, int Hout,
                          int Wout, int C, void* stream) {
-    VFI_REQUIRE(in_dev && out_dev && C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0, "vfi_upsample_nearest: bad arguments");
+    VFI_REQUIRE(in_dev && out_dev && N > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && C > 0 && C % 4 == 0 && in_cs % 4 == 0 &&
+                    out_cs % 4 == 0 && in_cs >= C && out_cs >= C,
+                "vfi_upsample_nearest: bad arguments");
+    VFI_REQUIRE((((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0, "vfi_upsample_nearest: channel windows must be 16-byte aligned");
     const long n = (long)N * Hout * Wout * (C / 4);
     TraceScope ts("upsample_nearest", (hipStream_t)stream);
     hipLaunchKernelGGL(upsample_nearest_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, out_dev, out_cs, N,
@@ -566,7 +570,8 @@ int vfi_upsample_nearest(const float* in_dev, int in_cs, float* out_dev, int out
 
 int vfi_resize_bilinear(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int Hin, int Win, int Hout,
                         int Wout, int C, float mul, void* stream) {
-    VFI_REQUIRE(in_dev && out_dev && C > 0, "vfi_resize_bilinear: bad arguments");
+    VFI_REQUIRE(in_dev && out_dev && C > 0 && in_cs >= C && out_cs >= C && N > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0,
+                "vfi_resize_bilinear: bad arguments");
     const long n = (long)N * Hout * Wout;
     TraceScope ts("resize_bilinear", (hipStream_t)stream);
     hipLaunchKernelGGL(resize_bilinear_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, out_dev, out_cs, N,
@@ -579,6 +584,7 @@ int vfi_warp_film(const float* in_dev, int in_cs, const float* flow_dev, int flo
                   int out_cs, int N, int H, int W, int C, void* stream) {
     VFI_REQUIRE(in_dev && flow_dev && out_dev && C % 4 == 0 && in_cs % 4 == 0 && out_cs % 4 == 0 && H > 1 && W > 1,
                 "vfi_warp_film: bad arguments (C and strides multiples of 4)");
+    VFI_REQUIRE((((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0, "vfi_warp_film: channel windows must be 16-byte aligned");
     // torch.linspace(-ls, ls, n) in fp32: start/end rounded from double, step = (end-start)/(n-1)
     const float sx1 = (float)(1.0 - 1.0 / (double)W), sx0 = -sx1, stepx = (sx1 - sx0) / (float)(W - 1);
     const float sy1 = (float)(1.0 - 1.0 / (double)H), sy0 = -sy1, stepy = (sy1 - sy0) / (float)(H - 1);

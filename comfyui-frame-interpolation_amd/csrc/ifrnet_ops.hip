@@ -257,7 +257,7 @@ int vfi_resize_bilinear_ratio(const float* in_dev, int in_cs, float* out_dev, in
 
 int vfi_ifrnet_output(const float* img0_dev, const float* img1_dev, const float* fin_dev, const float* mean_dev, float* out_dev, int N,
                       int Hp, int Wp, int Hf, int Wf, int H, int W, void* stream) {
-    VFI_REQUIRE(img0_dev && img1_dev && fin_dev && mean_dev && out_dev && N > 0 && Hp >= H && Wp >= W && Hf >= H && Wf >= W && Hf > 1 &&
+    VFI_REQUIRE(img0_dev && img1_dev && fin_dev && mean_dev && out_dev && N > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W && Hf >= H && Wf >= W && Hf > 1 &&
                     Wf > 1,
                 "vfi_ifrnet_output: bad arguments (the flow field must cover the %dx%d frame: %dx%d)", H, W, Hf, Wf);
     TraceScope ts("ifrnet_output", (hipStream_t)stream);

@@ -107,16 +107,20 @@ int vfi_conv_forward(const vfi_conv_t* conv, const float* in_dev, int in_cs, flo
  * Only for an exact x2 (the caller falls back to vfi_upsample_nearest + vfi_conv_forward otherwise). */
 vfi_conv_t* vfi_conv_create_up2x2(const float* weight_oihw_host, const float* bias_host, int Cout, int Cin, const int* chan_map, int Cin_phys);
 
-/* F.avg_pool2d(x, 2, 2) (odd sizes floor), film_arch.py:655-674, :112-113.  C % 4 == 0. */
+/* F.avg_pool2d(x, 2, 2) (odd sizes floor), film_arch.py:655-674, :112-113.  C % 4 == 0, both strides % 4 == 0 and >= C, both windows
+ * 16-byte aligned (float4 accesses), N > 0, H, W >= 2: anything else is refused before the launch. */
 int vfi_avgpool2(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int H, int W, int C, void* stream);
-/* F.interpolate(x, size=(Hout,Wout), mode='nearest'), film_arch.py:286.  C % 4 == 0. */
+/* F.interpolate(x, size=(Hout,Wout), mode='nearest'), film_arch.py:286.  C % 4 == 0, both strides % 4 == 0 and >= C, both windows
+ * 16-byte aligned, N and every size > 0. */
 int vfi_upsample_nearest(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int Hin, int Win,
                          int Hout, int Wout, int C, void* stream);
-/* F.interpolate(mul * x, size=(Hout,Wout), mode='bilinear') (align_corners=False), film_arch.py:597,610,752. */
+/* F.interpolate(mul * x, size=(Hout,Wout), mode='bilinear') (align_corners=False), film_arch.py:597,610,752.  Any C > 0; strides >= C,
+ * N and every size > 0. */
 int vfi_resize_bilinear(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int Hin, int Win,
                         int Hout, int Wout, int C, float mul, void* stream);
 /* film_arch.warp(image, flow_mul * flow): backward bilinear warp sampling at (x + fx, y + fy), border padding,
- * align_corners=False, reference fp32 expression order; flow = [dx, dy] per pixel.  film_arch.py:677-724. */
+ * align_corners=False, reference fp32 expression order; flow = [dx, dy] per pixel.  film_arch.py:677-724.  C % 4 == 0, in_cs and out_cs
+ * % 4 == 0, the image and output windows 16-byte aligned, H, W > 1. */
 int vfi_warp_film(const float* in_dev, int in_cs, const float* flow_dev, int flow_cs, float flow_mul,
                   float* out_dev, int out_cs, int N, int H, int W, int C, void* stream);
 /* out = alpha * a + beta * b over a C-channel window (b may be NULL): flow accumulation v = v_res + v,
@@ -339,7 +343,7 @@ int vfi_resize_bilinear_ratio(const float* in_dev, int in_cs, float* out_dev, in
                               int C, float ratio_h, float ratio_w, float post_mul, void* stream);
 /* imgt = clamp(mask * warp(img0, flow0) + (1 - mask) * warp(img1, flow1) + mean_ + res, 0, 1)[:H, :W] (:290-294).
  * fin [N,Hf,Wf,8] = (flow0 xy, flow1 xy, mask, res rgb) at the size of the reference's last resize (the warp grid has
- * that size, the images Hp x Wp); img{0,1} [N,Hp,Wp,4] mean-removed; out [N,H,W,3]. */
+ * that size, the images Hp x Wp); img{0,1} [N,Hp,Wp,4] mean-removed; out [N,H,W,3].  0 < H <= min(Hp, Hf), 0 < W <= min(Wp, Wf). */
 int vfi_ifrnet_output(const float* img0_dev, const float* img1_dev, const float* fin_dev, const float* mean_dev, float* out_dev, int N,
                       int Hp, int Wp, int Hf, int Wf, int H, int W, void* stream);
 
