@@ -238,6 +238,8 @@ PROTOTYPES = {
     "vfi_amt_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_atm_window_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_atm_window_attention_labels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfi_atm_motion_mlp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "vfi_atm_dwconv3x3_gelu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfi_atm_gather_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -245,10 +247,14 @@ PROTOTYPES = {
     "vfi_atm_blend_warps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p]),
     "vfi_atm_refine_out": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_atm_alignment_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfi_atm_alignment_scratch_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "vfi_atm_select_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_atm_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
     "vfi_atm_create_variant": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int]),
     "vfi_atm_destroy": (None, [C.c_void_p]),
     "vfi_atm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfi_atm_forward_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_atm_max_padded_pixels": (C.c_int64, []),
     "vfi_atm_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
     "vfi_atm_release_workspace": (C.c_int, [C.c_void_p]),
@@ -291,6 +297,10 @@ TEST_PROTOTYPES = {k: PROTOTYPES.pop(k) for k in TEST_NAMES}
 WINO_TEST_PROTOTYPES = {
     "vfi_test_wino_dead_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int]),
     "vfi_test_deconv_wino_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p]),
+}
+# ... and include/vfi_hip_test_atm.h (the record of the ATM ensemble's last forward): test builds only
+ATM_TEST_PROTOTYPES = {
+    "vfi_atm_ensemble_record": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
 }
 
 
@@ -343,6 +353,7 @@ def load():
     if _test_build:
         protos.update(TEST_PROTOTYPES)
         protos.update(WINO_TEST_PROTOTYPES)
+        protos.update(ATM_TEST_PROTOTYPES)
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

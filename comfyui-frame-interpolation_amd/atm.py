@@ -3,18 +3,20 @@
 Node shape follows vfi_models/atm/__init__.py:76-182: the three checkpoint names, the three ``global_motion`` choices and the ``vfi``
 keywords.  ``atm-vfi-lite.pt`` is served; ``atm-vfi-base.pt`` / ``atm-vfi-base-pct.pt`` (ATM-base) are served when config.yaml's ``atm_base``
 key is on and raise NotImplementedError naming themselves otherwise; ``"On with Ensemble (slowest)"`` (the multi-scale global-motion
-ensemble) raises NotImplementedError by name for both models.  All of this before anything is loaded.  The frame loop is the
+ensemble, network_lite.py:540-704) is served for both models when config.yaml's ``atm_ensemble`` key is on and raises NotImplementedError by
+name otherwise.  All of this before anything is loaded.  The frame loop is the
 reference's own (:152-177): per kept pair the first frame and the new frames of ``inference()`` (:39-74) — FILM's greedy midpoint schedule,
 every model call the midpoint of two known frames, clamped to [0, 1] and re-used —, a skipped pair contributes nothing at all, the clip's
 last frame is appended: schedule.film_output_plan + nodeloop.run_plan with film.film_schedule.  Each model call is ONE vfi_atm_forward
-(csrc/atm_net.hip): centred replicate pad to multiples of 64, the network, un-pad, clamp.  No pair lanes, no HIP graph.
+(csrc/atm_net.hip), or ONE vfi_atm_forward_ensemble in the ensemble mode (the global branch at scales 1, 1/2 and 1/4, scored and chosen on
+the device): centred replicate pad to multiples of 64, the network, un-pad, clamp.  No pair lanes, no HIP graph.
 """
 import typing
 
 import torch
 
 from . import _lib
-from .atm_spec import CKPT_NAMES, VARIANTS, check_ckpt_name, check_state_dict, load_file, weight_shapes
+from .atm_spec import CKPT_NAMES, VARIANTS, atm_ensemble_enabled, check_ckpt_name, check_state_dict, load_file, weight_shapes
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film import film_schedule
 from .netengine import NetEngine, WorkspaceBytes
@@ -23,6 +25,7 @@ from .schedule import InterpolationStateList, film_output_plan
 
 MODEL_TYPE = "atm"
 GLOBAL_MOTION = {"On": (True, False), "On with Ensemble (slowest)": (True, True), "Off (fastest)": (False, False)}      # (global motion, ensemble)
+ENSEMBLE = 2      # global_motion_flag's value for the ensemble choice (True / False: on / off), what AtmEngine.forward routes to vfi_atm_forward_ensemble
 FLOATS_PER_PADDED_PIXEL = 80      # the widest per-image buffer: the refinement net's input, 76 channels padded to 80 (csrc/atm_net.hip)
 MAX_PADDED_PIXELS = ((1 << 31) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)      # = vfi_atm_max_padded_pixels(): 6 710 886
 # ATM-base: the refinement net's full-resolution concat buffer, 2 * 64 = 128 channels (kCfg[1].px_floats, csrc/atm_net.hip): 1472x2560 fits,
@@ -45,10 +48,13 @@ def check_frame_size(H, W, variant="lite"):
 
 
 def global_motion_flag(global_motion):
-    """The widget's choice -> True / False; the ensemble choice and unknown ones raise by name."""
+    """The widget's choice -> True / False, or ENSEMBLE for the ensemble choice when config.yaml's ``atm_ensemble`` key is on; without the key
+    the ensemble choice raises by name, as unknown ones do."""
     if global_motion not in GLOBAL_MOTION:
         raise KeyError(f"unknown global_motion {global_motion!r} (known: {list(GLOBAL_MOTION)})")
     on, ensemble = GLOBAL_MOTION[global_motion]
+    if ensemble and atm_ensemble_enabled():
+        return ENSEMBLE
     if ensemble:
         raise NotImplementedError(f"global_motion {global_motion!r}: the multi-scale global-motion ensemble is not built yet; use 'On' or 'Off (fastest)'")
     return on
@@ -56,7 +62,8 @@ def global_motion_flag(global_motion):
 
 class AtmEngine(WorkspaceBytes, NetEngine):
     """Device-resident ATM-lite or ATM-base (``variant``; base only with config.yaml's ``atm_base`` on): ``forward(frame0, frame1,
-    global_motion)`` = the model's clamped, un-padded midpoint frame of one pair."""
+    global_motion)`` = the model's clamped, un-padded midpoint frame of one pair; global_motion: False / True, or ENSEMBLE for the multi-scale
+    ensemble."""
 
     PREFIX, LABEL = "vfi_atm", "ATM"
 
@@ -85,8 +92,19 @@ class AtmEngine(WorkspaceBytes, NetEngine):
         check_frame_size(H, W, self.variant)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-        self._call("forward", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, int(bool(global_motion)), out.data_ptr(), _lib.stream_ptr())
+        if global_motion == ENSEMBLE:
+            self._call("forward_ensemble", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, out.data_ptr(), _lib.stream_ptr())
+        else:
+            self._call("forward", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, int(bool(global_motion)), out.data_ptr(), _lib.stream_ptr())
         return out
+
+    def ensemble_record(self):
+        """(three losses, chosen level) of the last ensemble forward (a test tap: libvfi_hip_test.so only); synchronises its stream"""
+        import ctypes
+
+        losses, level = (ctypes.c_float * 3)(), ctypes.c_int()
+        _lib.check(_lib.test_tap("vfi_atm_ensemble_record")(self.handle, losses, ctypes.byref(level)), "vfi_atm_ensemble_record")
+        return [float(x) for x in losses], level.value
 
 
 def atm_pair(eng, f0, f1, task, global_motion):
@@ -120,7 +138,7 @@ class ATM_VFI:
     def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10, multiplier: typing.SupportsInt = 2,
             global_motion="On", optional_interpolation_states: InterpolationStateList = None, **kwargs):
         variant = check_ckpt_name(ckpt_name)            # ATM-base without the atm_base key: NotImplementedError naming the file, before anything is loaded
-        gm = global_motion_flag(global_motion)          # the ensemble likewise, for both models
+        gm = global_motion_flag(global_motion)          # the ensemble without the atm_ensemble key likewise, for both models
         check_frame_size(*frames.shape[1:3], variant)   # before an engine exists
         plan, tasks = film_output_plan(len(frames), multiplier, optional_interpolation_states)
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)

@@ -10,7 +10,10 @@ whose buffers say otherwise is refused (``load_file``).
 ATM-base (atm-vfi-base.pt and its perceptual-loss fine-tune atm-vfi-base-pct.pt: ``network_base.Network``, network_base.py:88-260) has the same
 module tree and forward, hence the same 236 names in the same order; only the widths differ (``CONFIG``): 51 564 259 parameters.  It is
 served only when config.yaml's ``atm_base`` key is on (``atm_base_enabled()``); absent or off, both files and 24-channel state dicts are
-refused as before."""
+refused as before.
+
+The multi-scale global-motion ensemble ("On with Ensemble (slowest)", for both models) is served only when config.yaml's ``atm_ensemble`` key
+is on (``atm_ensemble_enabled()``); absent or off, the choice is refused by name as before."""
 from collections import OrderedDict
 
 CKPT_NAMES = ("atm-vfi-base.pt", "atm-vfi-lite.pt", "atm-vfi-base-pct.pt")      # the reference's widget order
@@ -155,6 +158,13 @@ def atm_base_enabled():
     from . import ckpt
 
     return bool(ckpt.load_config().get("atm_base", False))
+
+
+def atm_ensemble_enabled():
+    """config.yaml's ``atm_ensemble`` key (absent = off), read at call time"""
+    from . import ckpt
+
+    return bool(ckpt.load_config().get("atm_ensemble", False))
 
 
 def check_ckpt_name(ckpt_name):

@@ -12,11 +12,15 @@
 //   atm_depth_to_space  ConvTranspose2d(k 2, s 2) = a 1x1 layer with 4 Cout outputs + this interleave
 //   atm_blend / atm_out the two synthesis steps
 //   atm_pad / atm_copy  InputPadder(64)'s centred replicate pad; channel-window copies with an optional per-channel PReLU
+//   atm_alignment_*     the ensemble's score ("On with Ensemble (slowest)", network_lite.py:540-554): flow up-sampling, both warps and the L1
+//                       mean in one pass over the full-resolution pair, summed in a fixed order in two launches (no atomics)
+//   atm_select_flow     the ensemble's choice and the winner's resize to the 1/16 map, on the device
 //
 // Built with -ffp-contract=off (csrc/build.py): `score * scale + mask` and the warp coordinates round as torch rounds them.
 #include <cstring>
 
 #include "../../include/vfi_hip.h"
+#include "../../include/vfi_hip_test_atm.h"
 #include "gmfss_bodies.h"
 #include "net_object.h"
 #include "vfi_common.h"
@@ -40,10 +44,12 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the columns D, D + 1 = the key's x, y inside the window); a wave computes S^T = K Q^T for its 16 queries, so that a lane holds the scores
 // of ONE query (column lane & 15) against keys 4 (lane >> 4) + i of every key tile: the softmax is a reduction over the lane's registers and
 // two xor-shuffles, and the same registers are the A operand of P V with the key order of the B operand permuted alike.
+// lh x lw: the map the PAD labels are taken from, centred in the same hp x wp layout (h x w everywhere but in the ensemble's shifted global
+// block, vfi_atm_window_attention_labels); the tokens are addressed by h x w alone.
 template <int WIN, int D>
 __global__ __launch_bounds__(256) void atm_attn_kernel(const float* __restrict__ q, int q_cs, const float* __restrict__ k, int k_cs,
                                                        const float* __restrict__ v, int v_cs, long pad_tok, float* __restrict__ out, int out_cs,
-                                                       float* __restrict__ offs, int h, int w, int hp, int wp, int shift, int cross, float scale) {
+                                                       float* __restrict__ offs, int h, int w, int hp, int wp, int lh, int lw, int shift, int cross, float scale) {
     constexpr int N = WIN * WIN, NT = N / 16, KS = D / 4, CT = (D + 2 + 15) / 16, DV = CT * 16, KST = D + 1;
     __shared__ float k_s[N * KST];
     __shared__ float v_s[N * DV];
@@ -51,12 +57,12 @@ __global__ __launch_bounds__(256) void atm_attn_kernel(const float* __restrict__
     const int tid = threadIdx.x;
     const int nwx = wp / WIN, wy = blockIdx.x / nwx, wx = blockIdx.x % nwx;
     const int f = blockIdx.y / kHeads, head = blockIdx.y % kHeads;
-    const int top = (hp - h) / 2, left = (wp - w) / 2;
-    const bool padded = hp != h || wp != w;
+    const int top = (hp - h) / 2, left = (wp - w) / 2, ltop = (hp - lh) / 2, lleft = (wp - lw) / 2;
+    const bool padded = hp != lh || wp != lw;
     if (tid < N) {
         const int r = wy * WIN + tid / WIN, c = wx * WIN + tid % WIN;
         int lab = 0;
-        if (padded) lab = 3 * ((r >= top) + (r >= h + top)) + (c >= left) + (c >= w + left);
+        if (padded) lab = 3 * ((r >= ltop) + (r >= lh + ltop)) + (c >= lleft) + (c >= lw + lleft);
         if (shift) lab = lab * 9 + 3 * ((r >= hp - WIN) + (r >= hp - shift)) + (c >= wp - WIN) + (c >= wp - shift);
         const int y = (r + shift) % hp - top, x = (c + shift) % wp - left;
         tok_s[tid] = (y >= 0 && y < h && x >= 0 && x < w) ? y * w + x : -1;
@@ -290,6 +296,94 @@ __global__ void atm_copy_kernel(const float* __restrict__ in, int in_cs, const f
     out[(size_t)p * out_cs + c] = (slopes && v < 0.f) ? v * slopes[c] : v;
 }
 
+// F.interpolate(align_corners=True) of a coarse [hi,wi] map at destination pixel (y, x) of an [ho,wo] one: the taps and weights of
+// resize_ac_body (csrc/gmfss_bodies.h): PyTorch's area-pixel scale (in - 1) / (out - 1), 0 for a one-pixel destination, so a one-pixel source
+// gives a constant
+struct AcTap {
+    int i00, i01, i10, i11;      // pixel indices into the coarse map
+    float hy, ly, hx, lx;
+};
+__device__ inline AcTap ac_tap(int y, int x, int hi, int wi, int ho, int wo) {
+    const float ry = ho > 1 ? (float)(hi - 1) / (float)(ho - 1) : 0.f, rx = wo > 1 ? (float)(wi - 1) / (float)(wo - 1) : 0.f;
+    const float sy = ry * (float)y, sx = rx * (float)x;
+    const int y0 = min((int)sy, hi - 1), x0 = min((int)sx, wi - 1);      // (the min never binds for y < ho, x < wo: it keeps the taps inside whatever the caller passes)
+    const int y1 = y0 + (y0 < hi - 1 ? 1 : 0), x1 = x0 + (x0 < wi - 1 ? 1 : 0);
+    AcTap t;
+    t.i00 = y0 * wi + x0, t.i01 = y0 * wi + x1, t.i10 = y1 * wi + x0, t.i11 = y1 * wi + x1;
+    t.ly = sy - (float)y0, t.lx = sx - (float)x0, t.hy = 1.0f - t.ly, t.hx = 1.0f - t.lx;
+    return t;
+}
+__device__ inline float ac_read(const float* map, int cs, const AcTap& t, int c, float mul) {
+    return (t.hy * (t.hx * map[(size_t)t.i00 * cs + c] + t.lx * map[(size_t)t.i01 * cs + c]) +
+            t.ly * (t.hx * map[(size_t)t.i10 * cs + c] + t.lx * map[(size_t)t.i11 * cs + c])) * mul;
+}
+
+constexpr int kLossBlock = 256;      // pixels (= threads) per workgroup of the scoring kernel; its grid follows from the frame size alone
+
+// global_alignmentness (network_lite.py:540-554), stage 1: per full-resolution pixel the four flow channels of the coarse motion map are
+// interpolated (upsample_flow: align_corners=True, values x f), both frames are warped there (warp3: the warps' own arithmetic) and |a - b| is
+// summed over the three channels; nothing full-resolution is written.  The workgroup's 256 terms are summed in a fixed tree: xor-shuffles
+// over the wave (32, 16, .., 1), then the four wave sums in wave order through LDS.  partial[blockIdx.x] = that sum.
+__global__ __launch_bounds__(kLossBlock) void atm_alignment_partial_kernel(const float* __restrict__ pair, int cs, int Hp, int Wp,
+                                                                            const float* __restrict__ motion, int mcs, int h, int w, float f,
+                                                                            float* __restrict__ partial) {
+    __shared__ float wave_s[kLossBlock / 64];
+    const long idx = (long)blockIdx.x * kLossBlock + threadIdx.x;
+    float v = 0.f;
+    if (idx < (long)Hp * Wp) {
+        const int X = (int)(idx % Wp), Y = (int)(idx / Wp);
+        const AcTap t = ac_tap(Y, X, h, w, Hp, Wp);
+        float a[3], b[3];
+        warp3(pair, cs, Wp, Hp, X, Y, ac_read(motion, mcs, t, 0, f), ac_read(motion, mcs, t, 1, f), a);
+        warp3(pair + (size_t)Hp * Wp * cs, cs, Wp, Hp, X, Y, ac_read(motion, mcs, t, 2, f), ac_read(motion, mcs, t, 3, f), b);
+        v = (fabsf(a[0] - b[0]) + fabsf(a[1] - b[1])) + fabsf(a[2] - b[2]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) wave_s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wave_s[0] + wave_s[1]) + wave_s[2]) + wave_s[3];
+}
+
+// stage 2, ONE workgroup: thread t adds partial[t], partial[t + 256], .. in index order in double, the 256 sums are added in a fixed LDS tree;
+// loss = sum / (3 Hp Wp).  No atomics, and no dependence on the number of CUs: the same input gives the same bits.
+__global__ __launch_bounds__(256) void atm_alignment_final_kernel(const float* __restrict__ partial, int n, double count, float* __restrict__ loss) {
+    __shared__ double sum_s[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
+    sum_s[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sum_s[threadIdx.x] += sum_s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(sum_s[0] / count);
+}
+
+// multiscale_global_motion_ensemble's choice (network_lite.py:583-595) on the device: level = the first of 0, 1, 2 whose loss equals the
+// smallest (Python's min, then the == chain), and channels 0..3 of out [h16,w16] = that level's flows resized x 1 / 2 / 4 (upsample_flow:
+// align_corners=True, values x factor; level 0 is copied).  Every thread reads the three losses; thread 0 writes the record.
+__global__ void atm_select_flow_kernel(const float* __restrict__ losses, const float* __restrict__ m0, const float* __restrict__ m1,
+                                       const float* __restrict__ m2, int mcs, int h16, int w16, float* __restrict__ out, int out_cs,
+                                       float* __restrict__ record) {
+    const float l0 = losses[0], l1 = losses[1], l2 = losses[2];
+    const float mn = fminf(fminf(l0, l1), l2);
+    const int level = l0 == mn ? 0 : l1 == mn ? 1 : 2;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx == 0 && record) record[0] = l0, record[1] = l1, record[2] = l2, record[3] = (float)level;
+    if (idx >= (long)h16 * w16) return;
+    float* o = out + (size_t)idx * out_cs;
+    if (level == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = m0[(size_t)idx * mcs + c];
+        return;
+    }
+    const float* m = level == 1 ? m1 : m2;
+    const AcTap t = ac_tap((int)(idx / w16), (int)(idx % w16), h16 >> level, w16 >> level, h16, w16);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = ac_read(m, mcs, t, c, (float)(1 << level));
+}
+
 }  // namespace
 }  // namespace vfi
 
@@ -299,6 +393,13 @@ extern "C" {
 
 int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, int k_cs, const float* v_dev, int v_cs, int64_t pad_token,
                              float* out_dev, int out_cs, float* offsets_dev, int h, int w, int C, int window, int shift, int cross, void* stream) {
+    return vfi_atm_window_attention_labels(q_dev, q_cs, k_dev, k_cs, v_dev, v_cs, pad_token, out_dev, out_cs, offsets_dev, h, w, h, w, C, window, shift,
+                                           cross, stream);
+}
+
+int vfi_atm_window_attention_labels(const float* q_dev, int q_cs, const float* k_dev, int k_cs, const float* v_dev, int v_cs, int64_t pad_token,
+                                    float* out_dev, int out_cs, float* offsets_dev, int h, int w, int label_h, int label_w, int C, int window,
+                                    int shift, int cross, void* stream) {
     VFI_REQUIRE(q_dev && k_dev && v_dev && out_dev && h > 0 && w > 0 && q_cs >= C && k_cs >= C && v_cs >= C && out_cs >= C,
                 "vfi_atm_window_attention: bad arguments");
     VFI_REQUIRE(((C == 224 || C == 384) && window == 8) || ((C == 352 || C == 672) && window == 12),
@@ -307,13 +408,15 @@ int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, i
     VFI_REQUIRE(shift == 0 || shift == window / 2, "vfi_atm_window_attention: shift %d must be 0 or half the window (%d)", shift, window / 2);
     VFI_REQUIRE(!offsets_dev || cross, "vfi_atm_window_attention: the motion read-out belongs to the cross kind");
     const int hp = round_up(h, window), wp = round_up(w, window);
+    VFI_REQUIRE(label_h > 0 && label_w > 0 && round_up(label_h, window) == hp && round_up(label_w, window) == wp,
+                "vfi_atm_window_attention: the %dx%d label map does not pad to the %dx%d layout of the %dx%d map", label_h, label_w, hp, wp, h, w);
     VFI_REQUIRE((hp == h && wp == w) || pad_token >= 0, "vfi_atm_window_attention: a %dx%d map is padded to %dx%d and needs a pad token", h, w, hp, wp);
     VFI_REQUIRE((long)2 * h * w * 3 * C < (1L << 31) && pad_token < (1L << 31) / (3 * C), "vfi_atm_window_attention: a %dx%d map is beyond the kernel's index arithmetic", h, w);
     TraceScope ts(cross ? "atm_attn_cross" : "atm_attn_self", (hipStream_t)stream);
     const dim3 grid((hp / window) * (wp / window), 2 * kHeads);
 #define ATM_ATTN(WIN, D)                                                                                                                              \
     hipLaunchKernelGGL((atm_attn_kernel<WIN, D>), grid, dim3(256), 0, (hipStream_t)stream, q_dev, q_cs, k_dev, k_cs, v_dev, v_cs, (long)pad_token, \
-                       out_dev, out_cs, offsets_dev, h, w, hp, wp, shift, cross, (float)(1.0 / sqrt((double)D)))
+                       out_dev, out_cs, offsets_dev, h, w, hp, wp, label_h, label_w, shift, cross, (float)(1.0 / sqrt((double)D)))
     if (C == 224) ATM_ATTN(8, 28);
     else if (C == 352) ATM_ATTN(12, 44);
     else if (C == 384) ATM_ATTN(8, 48);
@@ -394,6 +497,39 @@ int vfi_atm_refine_out(const float* it_dev, int it_cs, const float* res_dev, int
     return 0;
 }
 
+int64_t vfi_atm_alignment_scratch_floats(int Hp, int Wp) { return Hp > 0 && Wp > 0 ? ((int64_t)Hp * Wp + kLossBlock - 1) / kLossBlock : 0; }
+
+int vfi_atm_alignment_loss(const float* pair_dev, int pair_cs, int Hp, int Wp, const float* motion_dev, int motion_cs, int h, int w, float* scratch_dev,
+                           float* loss_dev, void* stream) {
+    VFI_REQUIRE(pair_dev && motion_dev && scratch_dev && loss_dev && pair_cs >= 3 && motion_cs >= 4 && h > 0 && w > 0 && Hp > 1 && Wp > 1,
+                "vfi_atm_alignment_loss: bad arguments");
+    VFI_REQUIRE(Hp % h == 0 && Wp % w == 0 && Hp / h == Wp / w, "vfi_atm_alignment_loss: a %dx%d frame is no whole multiple of the %dx%d motion map (one "
+                "factor for both sides)", Hp, Wp, h, w);
+    VFI_REQUIRE((long)2 * Hp * Wp * pair_cs < (1L << 31) && (long)h * w * motion_cs < (1L << 31),
+                "vfi_atm_alignment_loss: a %dx%d frame is beyond the kernel's index arithmetic", Hp, Wp);
+    TraceScope ts("atm_alignment_loss", (hipStream_t)stream);
+    const int blocks = (int)vfi_atm_alignment_scratch_floats(Hp, Wp);
+    hipLaunchKernelGGL(atm_alignment_partial_kernel, dim3(blocks), dim3(kLossBlock), 0, (hipStream_t)stream, pair_dev, pair_cs, Hp, Wp, motion_dev, motion_cs,
+                       h, w, (float)(Hp / h), scratch_dev);
+    VFI_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(atm_alignment_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)scratch_dev, blocks, 3.0 * Hp * Wp, loss_dev);
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int vfi_atm_select_flow(const float* losses_dev, const float* motion0_dev, const float* motion1_dev, const float* motion2_dev, int motion_cs, int h16,
+                        int w16, float* out_dev, int out_cs, float* record_dev, void* stream) {
+    VFI_REQUIRE(losses_dev && motion0_dev && motion1_dev && motion2_dev && out_dev && motion_cs >= 4 && out_cs >= 4 && h16 >= 4 && w16 >= 4,
+                "vfi_atm_select_flow: bad arguments (a %dx%d map: both sides at least 4, level k is [h16 >> k, w16 >> k])", h16, w16);
+    VFI_REQUIRE((long)h16 * w16 * out_cs < (1L << 31) && (long)h16 * w16 * motion_cs < (1L << 31),
+                "vfi_atm_select_flow: a %dx%d map is beyond the kernel's index arithmetic", h16, w16);
+    TraceScope ts("atm_select_flow", (hipStream_t)stream);
+    hipLaunchKernelGGL(atm_select_flow_kernel, dim3(nblk((long)h16 * w16, 256)), dim3(256), 0, (hipStream_t)stream, losses_dev, motion0_dev, motion1_dev,
+                       motion2_dev, motion_cs, h16, w16, out_dev, out_cs, record_dev);
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"
 
 // ---- the network object: ATM-lite / ATM-base on csrc/net_object.h --------------------------------------------------------------------------------------
@@ -445,6 +581,11 @@ struct vfi_atm : NetObject {
     vfi_conv_t *proj = nullptr, *down1 = nullptr, *down2[2] = {}, *down3[3] = {}, *up1d = nullptr, *up1c = nullptr, *up2d = nullptr, *up2c = nullptr,
                *up3d = nullptr, *rh[2] = {};
     int Hp = 0, Wp = 0, variant = 0;
+    // the ensemble's device record: [0..2] the three losses and [3] the chosen level as vfi_atm_select_flow wrote them, [4..6] the losses as the
+    // scoring kernels wrote them; ens_ran: an ensemble forward has been enqueued on ens_stream
+    float* ens_rec = nullptr;
+    hipStream_t ens_stream = nullptr;
+    bool ens_ran = false;
 };
 
 namespace {
@@ -500,8 +641,9 @@ int run_fusion(Run& r, const Fusion& F, const float* fine, int fine_cs, int c0, 
 }
 
 // One windowed block on tok [2 h + 1 rows, w, C] (the last row is zero: the pad token) -> out (same layout, 2 h rows written).  cross: the motion
-// read-out goes to mot[f * 2 + p * mot_cs + {0, 1}].
-int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w, int C, int win, int shift, bool cross, float* mot, int mot_cs) {
+// read-out goes to mot[f * 2 + p * mot_cs + {0, 1}].  lab_h x lab_w: the map the pad labels come from (0: h x w, the block's own).
+int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w, int C, int win, int shift, bool cross, float* mot, int mot_cs,
+              int lab_h = 0, int lab_w = 0) {
     const int rows = 2 * h + 1;
     const long ntok = (long)2 * h * w;
     float *xn = r.buf("blk_xn", 1, rows, w, C), *qkv = r.buf("blk_qkv", 1, rows, w, 3 * C), *ao = r.buf("blk_ao", 2, h, w, C);
@@ -516,7 +658,8 @@ int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w
     } else {
         ATM_DO(r.conv(B.qkv, xn, C, rows, w, qkv, 3 * C, 1, 0));
     }
-    ATM_DO(vfi_atm_window_attention(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, ntok, ao, C, cross ? of : nullptr, h, w, C, win, shift, cross, r.st));
+    ATM_DO(vfi_atm_window_attention_labels(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, ntok, ao, C, cross ? of : nullptr, h, w, lab_h ? lab_h : h,
+                                           lab_w ? lab_w : w, C, win, shift, cross, r.st));
     if (cross) ATM_DO(vfi_atm_motion_mlp(of, B.m0w, B.m0b, B.m2w, B.m2b, mot, mot_cs, 2, (int64_t)h * w, r.st));
     ATM_DO(r.conv(B.proj, ao, C, 2 * h, w, y, C, 1, 0, xn, C));      // norm1(x) + proj(attention): the residual is the NORMED token
     ATM_DO(vfi_layernorm(y, C, C, ntok, B.n2w, B.n2b, t2, C, r.st));
@@ -525,13 +668,15 @@ int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w
     return r.conv(B.fc2, h2, M, 2 * h, w, out, C, 1, 0, y, C);
 }
 
-// two ATM blocks and the motion head (hidden width Ch): tok -> tok (in place through a second buffer), out5 [h,w,8] = (flow0 xy, flow1 xy, mask logit)
-int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, int h, int w, int C, int Ch, int win, float* out5) {
+// two ATM blocks and the motion head (hidden width Ch): tok -> tok (in place through a second buffer), out5 [h,w,8] = (flow0 xy, flow1 xy, mask logit).
+// lab_h x lab_w: the pad-label map of the SHIFTED block (0: its own)
+int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, int h, int w, int C, int Ch, int win, float* out5, int lab_h = 0,
+               int lab_w = 0) {
     const int mcs = 2 * kHeads / 2 + 2 * C;      // 8 motion channels | frame 0 tokens | frame 1 tokens
     float *mh = r.buf("mh_in", 1, h, w, mcs), *a = r.buf("mh_a", 1, h, w, Ch), *b = r.buf("mh_b", 1, h, w, Ch);
     if (r.bad) return -1;
     ATM_DO(run_block(r, B[0], tok, tok2, h, w, C, win, 0, true, mh, mcs));
-    ATM_DO(run_block(r, B[1], tok2, tok, h, w, C, win, win / 2, true, mh + 4, mcs));
+    ATM_DO(run_block(r, B[1], tok2, tok, h, w, C, win, win / 2, true, mh + 4, mcs, lab_h, lab_w));
     const long px = (long)h * w;
     ATM_DO(r.copy(tok, C, mh + 8, mcs, px, C));
     ATM_DO(r.copy(tok + (size_t)px * C, C, mh + 8 + C, mcs, px, C));
@@ -540,12 +685,46 @@ int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, i
     return r.conv(H.c[2], b, Ch, h, w, out5, 8, 1, 0);
 }
 
-int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int W, int global_motion, float* out, hipStream_t st) {
+// The four feature-extractor stages on an image pair x [2,h0,w0,8] (h0 x w0 = the size of level `first` of hs / wsz): stage i -> f[i], channel
+// stride fcs[i].  Scratch names carry the level, so that the ensemble's smaller passes keep buffers of their own.
+int run_features(Run& r, const float* x, const int* hs, const int* wsz, int first, float* const* f, const int* fcs) {
+    const Cfg& g = kCfg[r.m->variant];
+    static const char* an[3][4] = {{"fe_a0", "fe_a1", "fe_a2", "fe_a3"}, {"e1_fe_a0", "e1_fe_a1", "e1_fe_a2", "e1_fe_a3"}, {"e2_fe_a0", "e2_fe_a1", "e2_fe_a2", "e2_fe_a3"}};
+    int xcs = 8;
+    for (int i = 0; i < 4; ++i) {
+        const int hi = hs[first + (i ? i - 1 : 0)], wi = wsz[first + (i ? i - 1 : 0)], ho = hs[first + i], wo = wsz[first + i], c = g.hid[i];
+        float* a = r.buf(an[first][i], 2, ho, wo, c);
+        if (r.bad) return -1;
+        ATM_DO(r.conv(r.m->fe[i][0], x, xcs, hi, wi, a, c, 2, 3));
+        ATM_DO(r.conv(r.m->fe[i][1], a, c, ho, wo, f[i], fcs[i], 2, 3));
+        x = f[i], xcs = fcs[i];
+    }
+    return 0;
+}
+
+// estimate_global_motion (network_lite.py:383-407) at one image level: last_feat_extract on the stage-3 features f3 [2,2h,2w] (channel stride
+// f3cs), the global fusion with the stage-2 features fine [2,4h,4w,hid[2]], the two ATM blocks (window 12) and the motion head -> out5 [h,w,8] =
+// (flow0 xy, flow1 xy, mask logit) on this level's h x w map.  Scratch is keyed by size: every level has its own.  lab_h x lab_w: run_motion's.
+int run_global(Run& r, const float* fine, const float* f3, int f3cs, int h, int w, float* out5, int lab_h = 0, int lab_w = 0) {
+    vfi_atm* m = r.m;
+    const Cfg& g = kCfg[m->variant];
+    const int CG = g.global_c;
+    float *g0 = r.buf("gl_a", 2, h, w, g.last), *cat_g = r.buf("cat_g", 2, h, w, CG);
+    float *gtok = r.buf("gtok_a", 1, 2 * h + 1, w, CG), *gtok2 = r.buf("gtok_b", 1, 2 * h + 1, w, CG);
+    if (r.bad) return -1;
+    ATM_DO(r.conv(m->last[0], f3, f3cs, 2 * h, 2 * w, g0, g.last, 2, 3));
+    ATM_DO(r.conv(m->last[1], g0, g.last, h, w, cat_g + (CG - g.last), CG, 2, 3));
+    ATM_DO(run_fusion(r, m->gf, fine, g.hid[2], g.hid[2], f3, f3cs, g.hid[3], cat_g, CG, h, w, gtok));
+    return run_motion(r, m->glo, m->gh, gtok, gtok2, h, w, CG, g.global_head, 12, out5, lab_h, lab_w);
+}
+
+// mode: 0 = "Off (fastest)", 1 = "On", 2 = "On with Ensemble (slowest)"
+int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int W, int mode, float* out, hipStream_t st) {
     const Cfg& g = kCfg[m->variant];
     const int CL = g.local_c, CG = g.global_c;      // the local / global token widths
     const int rcs = r8(CL / 4 + kMotion + 15);      // the refinement net's input: 76 -> 80 / 116 -> 120 floats per pixel
     const int Hp = m->Hp, Wp = m->Wp, top = (Hp - H) / 2, left = (Wp - W) / 2;
-    const int hs[5] = {Hp, Hp / 2, Hp / 4, Hp / 8, Hp / 16}, wsz[5] = {Wp, Wp / 2, Wp / 4, Wp / 8, Wp / 16};
+    const int hs[7] = {Hp, Hp / 2, Hp / 4, Hp / 8, Hp / 16, Hp / 32, Hp / 64}, wsz[7] = {Wp, Wp / 2, Wp / 4, Wp / 8, Wp / 16, Wp / 32, Wp / 64};
     const int h8 = hs[3], w8 = wsz[3], h16 = hs[4], w16 = wsz[4];
     Run r{m, st};
     // padded frames and their x0.5 pyramids (bilinear, align_corners=True)
@@ -558,36 +737,46 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
     for (int i = 1; i < 4; ++i) ATM_DO(vfi_resize_bilinear_ac(pyr[i - 1], 8, pyr[i], 8, 2, hs[i - 1], wsz[i - 1], hs[i], wsz[i], 3, 1.0f, st));
     // feature extraction on both frames; the 1/8 map lands in the last hid[3] channels of the local fusion's concat buffer
     float* cat_l = r.buf("cat_l", 2, h8, w8, CL);
-    float* feat[3];
-    {
-        const float* x = pyr[0];
-        int xcs = 8;
-        const char *an[4] = {"fe_a0", "fe_a1", "fe_a2", "fe_a3"}, *fn[3] = {"fe_f0", "fe_f1", "fe_f2"};
-        for (int i = 0; i < 4; ++i) {
-            const int hi = i ? hs[i - 1] : Hp, wi = i ? wsz[i - 1] : Wp, c = g.hid[i];
-            float* a = r.buf(an[i], 2, hs[i], wsz[i], c);
-            float* f = i < 3 ? r.buf(fn[i], 2, hs[i], wsz[i], c) : cat_l + (CL - g.hid[3]);
-            if (r.bad) return -1;
-            ATM_DO(r.conv(m->fe[i][0], x, xcs, hi, wi, a, c, 2, 3));
-            ATM_DO(r.conv(m->fe[i][1], a, c, hs[i], wsz[i], f, i < 3 ? c : CL, 2, 3));
-            if (i < 3) feat[i] = f;
-            x = f, xcs = i < 3 ? c : CL;
-        }
-    }
-    const float* f3 = cat_l + (CL - g.hid[3]);
+    if (r.bad) return -1;
+    float* feat[4] = {r.buf("fe_f0", 2, hs[0], wsz[0], g.hid[0]), r.buf("fe_f1", 2, hs[1], wsz[1], g.hid[1]), r.buf("fe_f2", 2, hs[2], wsz[2], g.hid[2]),
+                      cat_l + (CL - g.hid[3])};
+    const int fcs[4] = {g.hid[0], g.hid[1], g.hid[2], CL};
+    if (r.bad) return -1;
+    ATM_DO(run_features(r, pyr[0], hs, wsz, 0, feat, fcs));
+    const float* f3 = feat[3];
     float *tok = r.buf("tok_a", 1, 2 * h8 + 1, w8, CL), *tok2 = r.buf("tok_b", 1, 2 * h8 + 1, w8, CL);
     if (r.bad) return -1;
     ATM_DO(run_fusion(r, m->lf, feat[1], g.hid[1], g.hid[1], feat[2], g.hid[2], g.hid[2], cat_l, CL, h8, w8, tok));
     const float *src0 = pyr[0], *src1 = pyr[0] + (size_t)Hp * Wp * 8;      // what the last synthesis step warps
-    if (global_motion) {
-        float *g0 = r.buf("gl_a", 2, h16, w16, g.last), *cat_g = r.buf("cat_g", 2, h16, w16, CG);
-        float *gtok = r.buf("gtok_a", 1, 2 * h16 + 1, w16, CG), *gtok2 = r.buf("gtok_b", 1, 2 * h16 + 1, w16, CG);
+    if (mode) {
         float* g5 = r.buf("gl_out5", 1, h16, w16, 8);
         if (r.bad) return -1;
-        ATM_DO(r.conv(m->last[0], f3, CL, h8, w8, g0, g.last, 2, 3));
-        ATM_DO(r.conv(m->last[1], g0, g.last, h16, w16, cat_g + (CG - g.last), CG, 2, 3));
-        ATM_DO(run_fusion(r, m->gf, feat[2], g.hid[2], g.hid[2], f3, CL, g.hid[3], cat_g, CG, h16, w16, gtok));
-        ATM_DO(run_motion(r, m->glo, m->gh, gtok, gtok2, h16, w16, CG, g.global_head, 12, g5));
+        ATM_DO(run_global(r, feat[2], f3, CL, h16, w16, g5));
+        if (mode == 2) {
+            // multiscale_global_motion_ensemble (network_lite.py:556-597): level 0 is g5 (the reference recomputes the same features from the
+            // same input); levels 1 and 2 run the feature extractor and the global branch on pyr[1] / pyr[2], the x0.5 images it feeds them.
+            // The shifted block of a level whose map pads to the previous level's layout is masked with that level's pad regions, as the
+            // reference's cached mask makes it (attention.py:279-305; tests/atm_ensemble_restated.py: mask_level).
+            float* lev[3] = {g5, nullptr, nullptr};
+            int lab = 0;      // the level whose map the shifted block's pad labels come from
+            for (int k = 1; k <= 2; ++k) {
+                const int hk = hs[4 + k], wk = wsz[4 + k];
+                if (round_up(hk, 12) != round_up(hs[3 + k], 12) || round_up(wk, 12) != round_up(wsz[3 + k], 12)) lab = k;
+                static const char *fn[2][4] = {{"e1_fe_f0", "e1_fe_f1", "e1_fe_f2", "e1_fe_f3"}, {"e2_fe_f0", "e2_fe_f1", "e2_fe_f2", "e2_fe_f3"}};
+                float* ef[4];
+                for (int i = 0; i < 4; ++i) ef[i] = r.buf(fn[k - 1][i], 2, hs[k + i], wsz[k + i], g.hid[i]);
+                lev[k] = r.buf("ens_out5", 1, hk, wk, 8);
+                if (r.bad) return -1;
+                ATM_DO(run_features(r, pyr[k], hs, wsz, k, ef, g.hid));
+                ATM_DO(run_global(r, ef[2], ef[3], g.hid[3], hk, wk, lev[k], hs[4 + lab], wsz[4 + lab]));
+            }
+            float *part = r.buf("ens_partial", 1, 1, 1, (int)vfi_atm_alignment_scratch_floats(Hp, Wp)), *sel = r.buf("ens_sel5", 1, h16, w16, 8);
+            if (r.bad) return -1;
+            for (int k = 0; k < 3; ++k) ATM_DO(vfi_atm_alignment_loss(pyr[0], 8, Hp, Wp, lev[k], 8, hs[4 + k], wsz[4 + k], part, m->ens_rec + 4 + k, st));
+            ATM_DO(vfi_atm_select_flow(m->ens_rec + 4, lev[0], lev[1], lev[2], 8, h16, w16, sel, 8, m->ens_rec, st));
+            m->ens_stream = st, m->ens_ran = true;
+            g5 = sel;      // channels 0..3: the winner's flows; the global-level mask logit is not read
+        }
         // the global flows, x2 per level up to full resolution; the tokens and every pyramid level are warped by them
         float* fl[4];
         const char* fl_names[4] = {"gl_fl0", "gl_fl1", "gl_fl2", "gl_fl3"};
@@ -823,6 +1012,7 @@ vfi_atm_t* vfi_atm_create_variant(const float* const* tensors, const int64_t* nu
     m->up3d = deconv(2 * hid, hid);
     m->rh[0] = conv(hid, 2 * hid, 3, 1, true);
     m->rh[1] = conv(3, hid, 3, 1, true);
+    m->ens_rec = m->upload(nullptr, 8);
     if (!cur.finish() || m->failed) {
         vfi_atm_destroy(m);
         return nullptr;
@@ -839,16 +1029,44 @@ int vfi_atm_release_workspace(vfi_atm_t* m) {
 
 int64_t vfi_atm_workspace_bytes(const vfi_atm_t* m) { return m ? m->ws.bytes() : 0; }
 
-int vfi_atm_forward(vfi_atm_t* m, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream) {
-    VFI_REQUIRE(m && frame0_dev && frame1_dev && out_dev && C >= 3 && H > 0 && W > 0 && (global_motion == 0 || global_motion == 1),
-                "vfi_atm_forward: bad arguments (global_motion %d: 0 off, 1 on; the multi-scale ensemble is not built)", global_motion);
+namespace {
+
+// the size guard and the workspace key shared by the two entry points; `who` names the caller in the refusal
+int atm_enter(vfi_atm_t* m, const char* who, int H, int W) {
     const int Hp = atm_pad64(H), Wp = atm_pad64(W);
     VFI_REQUIRE((int64_t)Hp * Wp <= vfi_atm_object_max_padded_pixels(m),
-                "vfi_atm_forward: a %dx%d frame (padded %dx%d) is over the size limit of %s: Hp * Wp * %d bytes must stay below 2 GiB for the layers' "
-                "index arithmetic (1088x1920 fits)", H, W, Hp, Wp, kCfg[m->variant].name, kCfg[m->variant].px_floats * 4);
+                "%s: a %dx%d frame (padded %dx%d) is over the size limit of %s: Hp * Wp * %d bytes must stay below 2 GiB for the layers' "
+                "index arithmetic (1088x1920 fits)", who, H, W, Hp, Wp, kCfg[m->variant].name, kCfg[m->variant].px_floats * 4);
     if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp) && m->ws.release()) return -1;
     m->Hp = Hp, m->Wp = Wp;
+    return 0;
+}
+
+}  // namespace
+
+int vfi_atm_forward(vfi_atm_t* m, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream) {
+    VFI_REQUIRE(m && frame0_dev && frame1_dev && out_dev && C >= 3 && H > 0 && W > 0 && (global_motion == 0 || global_motion == 1),
+                "vfi_atm_forward: bad arguments (global_motion %d: 0 off, 1 on; the multi-scale ensemble is vfi_atm_forward_ensemble's)", global_motion);
+    if (const int rc = atm_enter(m, "vfi_atm_forward", H, W)) return rc;
     return atm_forward(m, frame0_dev, frame1_dev, C, H, W, global_motion, out_dev, (hipStream_t)stream);
 }
+
+int vfi_atm_forward_ensemble(vfi_atm_t* m, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, float* out_dev, void* stream) {
+    VFI_REQUIRE(m && frame0_dev && frame1_dev && out_dev && C >= 3 && H > 0 && W > 0, "vfi_atm_forward_ensemble: bad arguments");
+    if (const int rc = atm_enter(m, "vfi_atm_forward_ensemble", H, W)) return rc;
+    return atm_forward(m, frame0_dev, frame1_dev, C, H, W, 2, out_dev, (hipStream_t)stream);
+}
+
+#ifdef VFI_TEST_TAPS      // include/vfi_hip_test_atm.h: only in libvfi_hip_test.so
+int vfi_atm_ensemble_record(vfi_atm_t* m, float* losses, int* level) {
+    VFI_REQUIRE(m && losses && level, "vfi_atm_ensemble_record: bad arguments");
+    VFI_REQUIRE(m->ens_ran, "vfi_atm_ensemble_record: no ensemble forward has run on this object");
+    float rec[4];
+    VFI_CHECK_HIP(hipStreamSynchronize(m->ens_stream));
+    VFI_CHECK_HIP(hipMemcpy(rec, m->ens_rec, sizeof(rec), hipMemcpyDeviceToHost));
+    losses[0] = rec[0], losses[1] = rec[1], losses[2] = rec[2], *level = (int)rec[3];
+    return 0;
+}
+#endif  // VFI_TEST_TAPS
 
 }  // extern "C"

@@ -758,6 +758,14 @@ int64_t vfi_amt_workspace_bytes(const vfi_amt_t* net);
  * (:207-208; the relative_coord buffer is not read: atm_spec.load_file checks that it holds exactly these offsets). */
 int vfi_atm_window_attention(const float* q_dev, int q_cs, const float* k_dev, int k_cs, const float* v_dev, int v_cs, int64_t pad_token,
                              float* out_dev, int out_cs, float* offsets_dev, int h, int w, int C, int window, int shift, int cross, void* stream);
+/* The same with the nine centre-pad regions of the mask taken from a label_h x label_w map centred in the padded layout instead of the h x w
+ * map itself (both must pad to the same window multiple; label = own is vfi_atm_window_attention).  This is what the reference's shifted
+ * block does inside an ensemble forward: it keeps the mask of its first call and re-uses it while the padded map has as many positions
+ * (:279-305), so a level whose map pads to the previous level's layout is masked with that level's pad regions.  Tokens, the roll and the
+ * nine shift regions are the h x w map's. */
+int vfi_atm_window_attention_labels(const float* q_dev, int q_cs, const float* k_dev, int k_cs, const float* v_dev, int v_cs, int64_t pad_token,
+                                    float* out_dev, int out_cs, float* offsets_dev, int h, int w, int label_h, int label_w, int C, int window,
+                                    int shift, int cross, void* stream);
 /* AttentionToMotion.mlp over the heads (:143-146, :209-211): out[f * out_frame_stride + p * out_cs + coord] = w2 . gelu(w0 offsets[f][p][:, coord]
  * + b0) + b2 for both frames, tokens p < tokens_per_frame and coord 0 (x), 1 (y); w0 [4][8], b0 [4], w2 [4], b2 [1] on the device. */
 int vfi_atm_motion_mlp(const float* offsets_dev, const float* w0_dev, const float* b0_dev, const float* w2_dev, const float* b2_dev, float* out_dev,
@@ -781,6 +789,25 @@ int vfi_atm_blend_warps(const float* src0_dev, const float* src1_dev, int src_cs
 /* The last step (:421, :524-525, InputPadder.unpad): out [H,W,3] = clamp(I_t + 2 sigmoid(res) - 1, 0, 1) cropped at (pad_top, pad_left) */
 int vfi_atm_refine_out(const float* it_dev, int it_cs, const float* res_dev, int res_cs, float* out_dev, int Hp, int Wp, int pad_top, int pad_left, int H,
                        int W, void* stream);
+/* The ensemble's score, fused (Network.global_alignmentness, network_lite.py:540-554): loss_dev[0] = mean over [3,Hp,Wp] of |flow_warp(frame 0,
+ * flow0) - flow_warp(frame 1, flow1)|.  pair_dev [2,Hp,Wp,pair_cs]: the two frames, channels 0..2; motion_dev [h,w,motion_cs]: a coarse
+ * motion map, channels 0..3 = flow0 xy, flow1 xy; Hp = f h and Wp = f w with one whole factor f.  Per full-resolution pixel the four flow
+ * channels are interpolated (upsample_flow: F.interpolate align_corners=True, source coordinate = (h - 1) / (Hp - 1) * y, scale 0 for a
+ * one-pixel side, so h = 1 or w = 1 gives a constant; values x f), both frames are sampled at pixel + flow with the device function
+ * vfi_atm_blend_warps uses, and |a - b| is summed over the channels: no full-resolution flow map or warped image is written.  The sum is
+ * deterministic: a fixed tree inside each 256-pixel workgroup (wave shuffles, then LDS), one float per workgroup into scratch_dev
+ * (vfi_atm_alignment_scratch_floats(Hp, Wp) floats), and a one-workgroup second launch that adds them in index order in double.  No float
+ * atomics; the grid depends on the frame size alone, so the same input gives the same bits on every run and every device. */
+int vfi_atm_alignment_loss(const float* pair_dev, int pair_cs, int Hp, int Wp, const float* motion_dev, int motion_cs, int h, int w, float* scratch_dev,
+                           float* loss_dev, void* stream);
+int64_t vfi_atm_alignment_scratch_floats(int Hp, int Wp);
+/* The ensemble's choice on the device (multiscale_global_motion_ensemble, :583-597): level = the first of 0, 1, 2 whose loss equals the
+ * smallest of losses_dev[0..2] (Python's min, then the == chain: ties go to the lower level).  motion{k}_dev [h16 >> k, w16 >> k, motion_cs]
+ * (h16, w16 >= 4; multiples of 4 in the network).  Channels 0..3 of out_dev [h16,w16,out_cs] = the chosen map's flows resized x 1 / 2 / 4 (upsample_flow:
+ * align_corners=True, values x factor: vfi_resize_bilinear_ac's arithmetic; level 0 is copied); channels 4.. of out_dev are not written.
+ * record_dev (nullable) [4]: the three losses and the level (as a float).  No host synchronisation. */
+int vfi_atm_select_flow(const float* losses_dev, const float* motion0_dev, const float* motion1_dev, const float* motion2_dev, int motion_cs, int h16,
+                        int w16, float* out_dev, int out_cs, float* record_dev, void* stream);
 
 typedef struct vfi_atm vfi_atm_t;
 /* The 232 weight tensors of ATM-lite in atm_spec.weight_shapes() order = the state dict of network_lite.Network without its four relative_coord
@@ -793,7 +820,8 @@ vfi_atm_t* vfi_atm_create_variant(const float* const* tensors, const int64_t* nu
 void vfi_atm_destroy(vfi_atm_t* net);
 /* Network.forward_normal (network_lite.py:425-538)["I_t"] for ONE pair: frames [H,W,C>=3] fp32 (not written) are padded to multiples of 64
  * (centred, replicate: InputPadder(dims, 64), atm/__init__.py:11-34, :62-68), out_dev [H,W,3] is the un-padded result, clamped to [0, 1].
- * global_motion: 1 = "On", 0 = "Off (fastest)" (:76-80); the multi-scale ensemble is not built.  A frame whose padded size exceeds
+ * global_motion: 1 = "On", 0 = "Off (fastest)" (:76-80); the multi-scale ensemble is vfi_atm_forward_ensemble's, and any other value
+ * is refused here.  A frame whose padded size exceeds
  * vfi_atm_max_padded_pixels() = (2^31 - 1) / 320 = 6 710 886 pixels is refused before any launch: the widest per-image buffer (the refinement
  * net's input, 76 channels padded to 80) has 320 bytes per padded pixel and the layers index an image with 32 bits (1088 x 1920 fits).  That
  * is ATM-lite's limit; the limit that vfi_atm_forward applies is the object's own, vfi_atm_object_max_padded_pixels(net): for ATM-base
@@ -801,6 +829,18 @@ void vfi_atm_destroy(vfi_atm_t* net);
  * channels (its input is 116 channels padded to 120, the last transposed convolution's taps r8(4 * 101) / 4 = 102 floats per full-resolution
  * pixel, the 4 C MLP buffers 1536 / 64): 1472 x 2560 fits, 2176 x 3840 does not. */
 int vfi_atm_forward(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream);
+/* Network.forward_global_ensemble (network_lite.py:599-704; network_base.py has the same code)["I_t"] for ONE pair: "On with Ensemble
+ * (slowest)".  Frames and out_dev as vfi_atm_forward's.  The global branch (feature extractor, last_feat_extract, global fusion, two ATM blocks,
+ * motion head) runs on the padded pair at scales 1, 1/2 and 1/4: level 0 is what "On" computes (the forward's own features are reused: the
+ * reference recomputes them from the same input), levels 1 and 2 run on the x0.5 pyramid images the forward already has.  The three flow pairs
+ * are scored (vfi_atm_alignment_loss), the winner is chosen and resized to the 1/16 map on the device (vfi_atm_select_flow), and the forward
+ * continues as "On" does; the global-level I_t and mask, which the reference does not compute here either, are not made.  One C call, no
+ * host synchronisation.  The shifted global block's mask follows the reference's cached one (vfi_atm_window_attention_labels).  Serves both
+ * variants at every size "On" serves, 64x64 included (global maps of 4x4, 2x2 and 1x1 tokens).  The size limit is
+ * vfi_atm_object_max_padded_pixels(net), as for "On": the ensemble adds no wider per-image buffer (its features are at most hid[0] <= 24
+ * floats per pixel of the HALF-resolution image, its token buffers live on the 1/32 and 1/64 maps, the scoring writes one float per 256
+ * pixels).  The workspace grows by those buffers (vfi_atm_workspace_bytes reports it). */
+int vfi_atm_forward_ensemble(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, float* out_dev, void* stream);
 int64_t vfi_atm_max_padded_pixels(void);
 int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* net);
 int vfi_atm_release_workspace(vfi_atm_t* net);

@@ -1,12 +1,13 @@
-"""Device-resident ATM-lite or ATM-base at 1080p (one vfi_atm_forward per new frame), seeded weights.
+"""Device-resident ATM-lite or ATM-base at 1080p (one vfi_atm_forward / vfi_atm_forward_ensemble per new frame), seeded weights.
 
-    python tools/atm_bench.py [--variant lite|base] [--iters 5] [--height 1080 --width 1920] [--no-parity] [--out profiles/atm_bench.json]
+    python tools/atm_bench.py [--variant lite|base] [--iters 5] [--height 1080 --width 1920] [--no-parity] [--no-ensemble] [--out profiles/atm_bench.json]
 
-Prints one JSON line (and writes it to --out: lite's result is the file's top level, base's its "base" entry; the other one is kept).  Per global-motion mode ("On", "Off (fastest)"): ms per new frame, the median of `iters`
+Prints one JSON line (and writes it to --out: lite's result is the file's top level, base's its "base" entry; the other one is kept).  Per global-motion mode ("On", "Off (fastest)" and, unless --no-ensemble, "On with Ensemble (slowest)" with the losses and the level it chose and
+its time over the same run's "On" time): ms per new frame, the median of `iters`
 forward calls timed with device events around the call (frames already on the device, workspace allocated by two warm-up calls); the
 workspace size; the library's per-kernel event trace (vfi_trace_*) of one extra call: the share of the new kernels (atm_attn_cross,
 atm_attn_self, atm_motion_mlp, atm_dwconv, atm_gather_taps, atm_depth_to_space, atm_blend, atm_out) and of the layer objects; and, unless
---no-parity, the in-run parity of the timed frame against the float32 restatement (tests/atm_restated.py, tests/atm_base_restated.py) on the
+--no-parity, the in-run parity of the timed frame against the float32 restatement (tests/atm_restated.py, tests/atm_base_restated.py, tests/atm_ensemble_restated.py) on the
 CPU: max |d| over every pixel, asserted <= 1e-3."""
 import argparse
 import ctypes as C
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--no-parity", action="store_true", help="skip the CPU restatement of the timed frame")
+    ap.add_argument("--no-ensemble", action="store_true", help="skip the ensemble leg")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "atm_bench needs the GPU"
@@ -36,10 +38,11 @@ def main():
 
     load_package()
     import atm_base_restated
+    import atm_ensemble_restated
     import atm_restated
     import cain_restated
     from cfi_amd import _lib, ckpt
-    from cfi_amd.atm import AtmEngine, padded_size
+    from cfi_amd.atm import ENSEMBLE, AtmEngine, padded_size
     from cfi_amd.atm_spec import seeded_state_dict
 
     H, W = args.height, args.width
@@ -50,10 +53,15 @@ def main():
     restated = atm_restated
     if args.variant == "base":      # opt-in: the tool turns the key on for itself
         restated, ckpt.load_config = atm_base_restated, atm_base_restated.config_with(True)
+    if not args.no_ensemble:
+        _lib.use_test_build()      # the ensemble's record is a test tap (include/vfi_hip_test_atm.h); the kernels are the product library's objects
     eng = AtmEngine(seeded_state_dict(atm_restated.SEED, args.variant), args.variant)
     lib = _lib.load()
     torch.set_num_threads(max(1, min(32, os.cpu_count() or 1)))
-    for mode, gm in atm_restated.MODES.items():
+    modes = dict(atm_restated.MODES)
+    if not args.no_ensemble:
+        modes[atm_ensemble_restated.ENSEMBLE] = ENSEMBLE
+    for mode, gm in modes.items():
         out = torch.empty((H, W, 3), device="cuda")
         call = lambda: eng.forward(f[0], f[1], gm, out)      # noqa: E731
         for _ in range(2):
@@ -90,10 +98,17 @@ def main():
         r["trace_layer_objects_share"] = round(sum(v[1] for k, v in rows.items() if k.startswith(("conv", "deconv"))) / total, 3)
         r["trace_rows"] = {k: [v[0], round(v[1], 3)] for k, v in sorted(rows.items(), key=lambda kv: -kv[1][1])[:12]}
         print(f"{mode}: {r['ms_per_frame']} ms per frame, workspace {r['workspace_bytes']} bytes", file=sys.stderr, flush=True)
+        if gm == ENSEMBLE:
+            r["losses"], r["level"] = eng.ensemble_record()
+            r["over_on"] = round(r["ms_per_frame"] / res["On"]["ms_per_frame"], 3)
         if not args.no_parity:
             x = frames.permute(0, 3, 1, 2).contiguous()
             with torch.no_grad():
-                want = restated.atm_frame(restated.state_dict_as(torch.float32), x[0:1], x[1:2], gm)[0].permute(1, 2, 0)
+                if gm == ENSEMBLE:
+                    sd32 = atm_ensemble_restated.state_dict_as(args.variant, torch.float32)
+                    want = atm_ensemble_restated.ensemble_frame(args.variant, sd32, x[0:1], x[1:2])[0].permute(1, 2, 0)
+                else:
+                    want = restated.atm_frame(restated.state_dict_as(torch.float32), x[0:1], x[1:2], gm)[0].permute(1, 2, 0)
             r["parity_max_abs_vs_float32_restatement"] = float((out.cpu() - want).abs().max())
             assert r["parity_max_abs_vs_float32_restatement"] <= atm_restated.TOL, r
         res[mode] = r
