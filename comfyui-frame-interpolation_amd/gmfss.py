@@ -550,7 +550,7 @@ class GMFSSEngine(OpsEngine):
                     self._ax(flow, 0, df, 0, flow, 0, 4)
                     self._ax(xin, 7, dm, 0, xin, 7, 1)
                 for k in (0, 1):                        # warped_img0 = warp(img0, flow[:, :2]), warped_img1 = warp(img1, flow[:, 2:4])
-                    self._c("vfi_warp_rife", _p(x7, 3 * k), 8, _p(flow, 2 * k), 4, _p(xin, 3 * k), 8, 1, Hq, Wq, 3)
+                    self._warp(x7, 3 * k, 3, flow, 2 * k, xin, 3 * k)
             rife = self._t("r_out", 1, Hh, Wh, 3)
             self._c("vfi_rife40_output", _p(xin), 8, _p(xin, 7), 8, None, 0, _p(rife), 1, Hq, Wq, Hh, Wh)
             self._ax(rife, 0, None, 0, dst, doff, 3)

@@ -26,75 +26,27 @@ import typing
 
 import torch
 
-from . import _lib
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .lanes import lane_set
 from .lanes import configure as configure_lanes
 from .ifrnet_spec import CKPT_NAMES, CONFIG, check_state_dict, decoder_io, kind_of
+from .opsengine import OpsEngine, _cs, _p
 from .schedule import InterpolationStateList, generic_output_plan
 
 MODEL_TYPE = "ifrnet"
 
 
-def _p(t, off=0):
-    return t.data_ptr() + 4 * off
-
-
-def _cs(c):
-    """physical channel stride of a c-channel activation"""
-    return (c + 7) // 8 * 8
-
-
-class _Layer:
-    """Conv2d 3x3 (+PReLU) or ConvTranspose2d(4,2,1) of the checkpoint as a vfi_conv layer object."""
-
-    def __init__(self, lib, w, b, slopes=None, kind=0, stride=1, chan_map=None, cin_phys=None):
-        w = w.detach().to("cpu", torch.float32).contiguous()
-        b = b.detach().to("cpu", torch.float32).contiguous()
-        pr = slopes.detach().to("cpu", torch.float32).contiguous() if slopes is not None else None
-        cout, cin = (w.shape[0], w.shape[1]) if kind == 0 else (w.shape[1], w.shape[0])
-        self.cin_phys = cin_phys or _cs(cin)
-        cm = (C.c_int * cin)(*chan_map) if chan_map is not None else None
-        self.lib, self.kind, self.stride, self.act, self.cout = lib, kind, stride, 3 if pr is not None else 0, cout
-        self.h = lib.vfi_conv_create_ex(kind, w.data_ptr(), b.data_ptr(), cout, cin, w.shape[2], stride, 0, cm, self.cin_phys,
-                                        pr.data_ptr() if pr is not None else None)
-        if not self.h:
-            raise RuntimeError("vfi_conv_create_ex failed: " + _lib.last_error())
-
-    def __call__(self, src, soff, dst, doff, res=None):
-        n, hin, win, cs = src.shape
-        want = (hin * 2, win * 2) if self.kind == 1 else (hin // self.stride, win // self.stride)
-        assert tuple(dst.shape[1:3]) == want and dst.shape[0] == n, (src.shape, dst.shape, want)
-        _lib.check(self.lib.vfi_conv_forward_ex(self.h, _p(src, soff), cs, hin, win, _p(dst, doff), dst.shape[-1], n, self.act, 0.0, 0.0,
-                                                0.0, _p(res) if res is not None else None, res.shape[-1] if res is not None else 0,
-                                                _lib.stream_ptr()), "vfi_conv_forward_ex")
-
-    def close(self):
-        if self.h:
-            self.lib.vfi_conv_destroy(self.h)
-            self.h = None
-
-
-class IFRNetEngine:
+class IFRNetEngine(OpsEngine):
     """IRFNet_L / IRFNet_S forward on the device.  ``forward`` takes N frame pairs that share one working-resolution
     factor; ``prepare`` / ``render`` adapt it to the (pair, timestep) loop shared with the M2M node."""
 
-    def __init__(self, state_dict, kind, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("IFRNet VFI (HIP): no GPU visible; this node has no CPU fallback")
-        self.lib = lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        _lib.check(lib.vfi_init(self.device.index or 0), "vfi_init")
+    def __init__(self, state_dict, kind, device=None, _test_backend=None):
+        super().__init__(device, _test_backend, pooled=False)      # every named scratch tensor stays until release_workspace()
         check_state_dict(state_dict, kind)
         self.kind, sd = kind, state_dict
         self.widths, self.k0, self.side = CONFIG[kind]
-        self.layers = []
         self.embt = 1.0
-
-        def mk(*a, **k):
-            l = _Layer(lib, *a, **k)
-            self.layers.append(l)
-            return l
+        mk = self._layer
 
         def convrelu(p, **k):
             return mk(sd[p + ".0.weight"], sd[p + ".0.bias"], sd[p + ".1.weight"], **k)
@@ -126,58 +78,22 @@ class IFRNetEngine:
                 c3=convrelu(p + ".1.conv3"), c4=convrelu(p + ".1.conv4", **sidek),
                 c5=mk(sd[p + ".1.conv5.weight"], sd[p + ".1.conv5.bias"], sd[p + ".1.prelu.weight"]),
                 up=mk(sd[p + ".2.weight"], sd[p + ".2.bias"], None, kind=1, stride=2))
-        self.scratch = {}
         self._pair = None
-
-    def close(self):
-        for l in self.layers:
-            l.close()
-        self.layers = []
-        self.release_workspace()
 
     def release_workspace(self):
         """Drop the activations; the packed weights stay on the device."""
-        self.scratch = {}
+        super().release_workspace()
         self._pair = None
 
-    def workspace_bytes(self):
-        return sum(t.numel() * t.element_size() for t in self.scratch.values())
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # noqa: BLE001 — interpreter shutdown
-            pass
-
     # ------------------------------------------------------------------------------------------------
-    def _t(self, name, *shape):
-        key = (name,) + tuple(shape)
-        if key not in self.scratch:
-            self.scratch[key] = torch.zeros(shape, dtype=torch.float32, device=self.device)
-        return self.scratch[key]
-
-    def _ax(self, a, aoff, b, boff, out, ooff, c, alpha=1.0, beta=1.0):
-        px = a.shape[0] * a.shape[1] * a.shape[2]
-        _lib.check(self.lib.vfi_axpby(_p(a, aoff), a.shape[-1], _p(b, boff) if b is not None else None, b.shape[-1] if b is not None else 0,
-                                      _p(out, ooff), out.shape[-1], px, c, alpha, beta, _lib.stream_ptr()), "vfi_axpby")
-
-    def _warp(self, src, c, flow, foff, dst, doff):
-        _lib.check(self.lib.vfi_warp_rife(_p(src), src.shape[-1], _p(flow, foff), flow.shape[-1], _p(dst, doff), dst.shape[-1],
-                                          src.shape[0], src.shape[1], src.shape[2], c, _lib.stream_ptr()), "vfi_warp_rife")
-
-    def _up2(self, src, dst, c):
-        """dst[..., :c] = 2.0 * resize(src[..., :c], 2.0)  (the x2 is exact in fp32, so it commutes with the resize)"""
-        _lib.check(self.lib.vfi_resize_bilinear(_p(src), src.shape[-1], _p(dst), dst.shape[-1], src.shape[0], src.shape[1], src.shape[2],
-                                                dst.shape[1], dst.shape[2], c, 2.0, _lib.stream_ptr()), "vfi_resize_bilinear")
-
-    def _resize(self, src, soff, dst, doff, c, ratio, post):
-        _lib.check(self.lib.vfi_resize_bilinear_ratio(_p(src, soff), src.shape[-1], _p(dst, doff), dst.shape[-1], src.shape[0], src.shape[1],
-                                                      src.shape[2], dst.shape[1], dst.shape[2], c, ratio, ratio, post, _lib.stream_ptr()),
-                   "vfi_resize_bilinear_ratio")
+    def _resize_ratio(self, src, soff, dst, doff, c, ratio, post):
+        """resize(): F.interpolate(scale_factor=1 / ratio) * post  (the base's ``_resize`` is the one with a target size; the x2 steps use it)"""
+        self._c("vfi_resize_bilinear_ratio", _p(src, soff), src.shape[-1], _p(dst, doff), dst.shape[-1], src.shape[0], src.shape[1], src.shape[2],
+                dst.shape[1], dst.shape[2], c, ratio, ratio, post)
 
     def _side(self, layer, buf, c, windowed, tmp):
         """buf[..., c-side:c] = convrelu(buf[..., c-side:c])   (ResBlock.forward, IFRNet_L_arch.py:115-121)"""
-        layer(buf, c - self.side if windowed else 0, tmp, 0)
+        self._conv(layer, buf, c - self.side if windowed else 0, tmp, 0)
         self._ax(tmp, 0, None, 0, buf, c - self.side, self.side)
 
     def _decoder(self, d, din, target):
@@ -187,13 +103,13 @@ class IFRNetEngine:
         c, cs = L["c"], _cs(L["c"])
         x, a, b, y = (self._t(f"dec_{k}", n, h, w, cs) for k in "xaby")
         tmp = self._t("dec_t", n, h, w, _cs(self.side))
-        L["conv0"](din, 0, x, 0)
-        L["c1"](x, 0, a, 0)
+        self._conv(L["conv0"], din, 0, x, 0)
+        self._conv(L["c1"], x, 0, a, 0)
         self._side(L["c2"], a, c, L["windowed"], tmp)
-        L["c3"](a, 0, b, 0)
+        self._conv(L["c3"], a, 0, b, 0)
         self._side(L["c4"], b, c, L["windowed"], tmp)
-        L["c5"](b, 0, y, 0, res=x)        # prelu(x + conv5(out))
-        L["up"](y, 0, target, 0)
+        self._conv(L["c5"], b, 0, y, 0, res=x)        # prelu(x + conv5(out))
+        self._conv(L["up"], y, 0, target, 0)
 
     @staticmethod
     def geometry(H, W, sf):
@@ -208,7 +124,6 @@ class IFRNetEngine:
     def forward(self, frames0, frames1, sf, embt, out):
         """IRFNet.forward(img0, img1, scale_factor=sf, timestep=embt) for N pairs; frames: lists of [H,W,C>=3] fp32 device
         tensors; out [N,H,W,3] device tensor (already clamped to [0,1] by the network)."""
-        lib, st = self.lib, _lib.stream_ptr()
         N = len(frames0)
         H, W, Cc = frames0[0].shape
         sf = float(sf)
@@ -219,19 +134,20 @@ class IFRNetEngine:
         if Hf < H or Wf < W:
             raise RuntimeError(f"IFRNet: resizing {hs}x{ws} back by 1/{sf} gives {Hf}x{Wf}, smaller than the {H}x{W} frame; "
                                f"the reference fails here too (frame does not fit the output tensor)")
-        assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (N, H, W, 3)
+        on_dev = lambda t: t.device.type == self.device.type   # noqa: E731
+        assert on_dev(out) and out.is_contiguous() and tuple(out.shape) == (N, H, W, 3)
         img = self._t("img", 2 * N, Hp, Wp, 4)
         for n in range(N):
             f0, f1 = frames0[n], frames1[n]
-            assert f0.is_cuda and f0.is_contiguous() and f1.is_contiguous() and f0.shape == f1.shape == (H, W, Cc) and Cc >= 3
-            _lib.check(lib.vfi_ifrnet_prep(f0.data_ptr(), f1.data_ptr(), Cc, H, W, _p(img[n]), _p(img[N + n]), Hp, Wp, st), "vfi_ifrnet_prep")
+            assert on_dev(f0) and on_dev(f1) and f0.is_contiguous() and f1.is_contiguous() and f0.shape == f1.shape == (H, W, Cc) and Cc >= 3
+            self._c("vfi_ifrnet_prep", f0.data_ptr(), f1.data_ptr(), Cc, H, W, _p(img[n]), _p(img[N + n]), Hp, Wp)
         cm, mean = self._t("cm", 2 * N, 4), self._t("mean", max(N, 1))
         rm = self._t("rowmean", 2 * N, Hp, 4)     # row means first (one block per row), then the mean of the rows
-        _lib.check(lib.vfi_pool_mean(_p(img), 4, _p(rm), 4, 2 * N, Hp, Wp, 4, 1, st), "vfi_pool_mean")
-        _lib.check(lib.vfi_pool_mean(_p(rm), 4, _p(cm), 4, 2 * N, Hp, 1, 4, 0, st), "vfi_pool_mean")
-        _lib.check(lib.vfi_ifrnet_center(_p(img), _p(cm), _p(mean), N, Hp * Wp, st), "vfi_ifrnet_center")
+        self._c("vfi_pool_mean", _p(img), 4, _p(rm), 4, 2 * N, Hp, Wp, 4, 1)
+        self._c("vfi_pool_mean", _p(rm), 4, _p(cm), 4, 2 * N, Hp, 1, 4, 0)
+        self._c("vfi_ifrnet_center", _p(img), _p(cm), _p(mean), N, Hp * Wp)
         r = self._t("r", 2 * N, hs, ws, 8)
-        self._resize(img, 0, r, 0, 3, 1.0 / sf, 1.0)
+        self._resize_ratio(img, 0, r, 0, 3, 1.0 / sf, 1.0)
         # ---- encoder, both images as one batch of 2N
         feats, x = [], r
         for lvl, c in enumerate(self.widths):
@@ -240,11 +156,10 @@ class IFRNetEngine:
             first, second = self.enc[lvl]
             if first is None:
                 wt, bs, sl = self.head
-                _lib.check(lib.vfi_conv7x7s2_prelu(_p(x), x.shape[-1], _p(wt), _p(bs), _p(sl), c, _p(a), a.shape[-1], 2 * N, x.shape[1],
-                                                   x.shape[2], st), "vfi_conv7x7s2_prelu")
+                self._c("vfi_conv7x7s2_prelu", _p(x), x.shape[-1], _p(wt), _p(bs), _p(sl), c, _p(a), a.shape[-1], 2 * N, x.shape[1], x.shape[2])
             else:
-                first(x, 0, a, 0)
-            second(a, 0, f, 0)
+                self._conv(first, x, 0, a, 0)
+            self._conv(second, a, 0, f, 0)
             feats.append(f)
             x = f
         # ---- decoder 4: cat(f0_4, f1_4, embt)
@@ -254,7 +169,7 @@ class IFRNetEngine:
         self._ax(feats[3][:N], 0, None, 0, din, 0, c4)
         self._ax(feats[3][N:], 0, None, 0, din, c4, c4)
         vals = (C.c_float * N)(*([float(embt)] * N))
-        _lib.check(lib.vfi_fill_items(_p(din, 2 * c4), din.shape[-1], 1, N, h * w, vals, st), "vfi_fill_items")
+        self._c("vfi_fill_items", _p(din, 2 * c4), din.shape[-1], 1, N, h * w, vals)
         flow_src = None     # tensor whose channels 0:4 hold the previous level's up_flow
         for d, lvl in ((4, 3), (3, 2), (2, 1), (1, 0)):
             if d < 4:
@@ -262,10 +177,10 @@ class IFRNetEngine:
                 f = self.widths[lvl]
                 if flow_src is not None:   # up_flow = out[:, 0:4] + 2.0 * resize(previous up_flow, 2.0)
                     tf = self._t("tf", N, din.shape[1], din.shape[2], 4)
-                    self._up2(flow_src, tf, 4)
+                    self._resize(flow_src, 0, tf, 0, 4, 2.0)     # (the x2 is exact in fp32, so it commutes with the resize)
                     self._ax(din, 0, tf, 0, din, 0, 4)
-                self._warp(feats[lvl][:N], f, din, 0, din, 4 + f)
-                self._warp(feats[lvl][N:], f, din, 2, din, 4 + 2 * f)
+                self._warp(feats[lvl][:N], 0, f, din, 0, din, 4 + f)
+                self._warp(feats[lvl][N:], 0, f, din, 2, din, 4 + 2 * f)
             if d > 1:
                 fn = self.widths[lvl - 1]
                 target = self._t(f"d{d - 1}in", N, din.shape[1] * 2, din.shape[2] * 2, _cs(4 + 3 * fn))
@@ -277,15 +192,14 @@ class IFRNetEngine:
         out1 = din
         # up_flow_1 = out1[:, 0:4] + 2.0 * resize(up_flow_2, 2.0); up_mask_1 = sigmoid(out1[:, 4:5])
         tf = self._t("tf", N, hs, ws, 4)
-        self._up2(flow_src, tf, 4)
+        self._resize(flow_src, 0, tf, 0, 4, 2.0)
         self._ax(out1, 0, tf, 0, out1, 0, 4)
-        _lib.check(lib.vfi_sigmoid(_p(out1, 4), 8, 1, N * hs * ws, st), "vfi_sigmoid")
+        self._c("vfi_sigmoid", _p(out1, 4), 8, 1, N * hs * ws)
         fin = self._t("fin", N, Hf, Wf, 8)
         inv = 1.0 / sf
-        self._resize(out1, 0, fin, 0, 4, 1.0 / inv, inv)       # resize(up_flow, 1/sf) * (1/sf)
-        self._resize(out1, 4, fin, 4, 4, 1.0 / inv, 1.0)       # mask, residual
-        _lib.check(lib.vfi_ifrnet_output(_p(img[:N]), _p(img[N:]), _p(fin), _p(mean), out.data_ptr(), N, Hp, Wp, Hf, Wf, H, W, st),
-                   "vfi_ifrnet_output")
+        self._resize_ratio(out1, 0, fin, 0, 4, 1.0 / inv, inv)       # resize(up_flow, 1/sf) * (1/sf)
+        self._resize_ratio(out1, 4, fin, 4, 4, 1.0 / inv, 1.0)       # mask, residual
+        self._c("vfi_ifrnet_output", _p(img[:N]), _p(img[N:]), _p(fin), _p(mean), out.data_ptr(), N, Hp, Wp, Hf, Wf, H, W)
         return out
 
     # (pair, timestep) interface of m2m.run_plan: the node's timestep is forward()'s scale_factor, self.embt its timestep

@@ -237,7 +237,7 @@ class IFUNetEngine(OpsEngine):
                         self._ax(flow, 0, delta, 0, flow2, 0, 4)                   # flow2 = flow + flow_d
                         self._ax(flow, 0, flow2, 0, flow, 0, 4, 0.5, 0.5)
                 for k in (0, 1):   # warped_img0 = warp(img0, flow[:, :2]), warped_img1 = warp(img1, flow[:, 2:4]); same slots in both variants
-                    self._c("vfi_warp_rife", _p(x17, 3 * k), 24, _p(flow, 2 * k), 4, _p(x17, 7 + 3 * k), 24, 1, Hp, Wp, 3)
+                    self._warp(x17, 3 * k, 3, flow, 2 * k, x17, 7 + 3 * k)
                 self._ax(x17, 7, None, 0, x17e, 7, 6)
             mask = self._t("rr_mask", 1, Hp, Wp, 8)              # a stage's outputs are requested here first, so that they outlive its scope
             stage(self._rrdbnet, x17, flow)
@@ -341,7 +341,7 @@ class IFUNetEngine(OpsEngine):
             else:
                 self._ax(flow, 0, df, 0, flow, 0, 2)
                 self._ax(mask, 0, dm, 0, mask, 0, 1)
-            self._c("vfi_warp_rife", _p(y, 0), 16, _p(flow), 2, _p(y, 6), 16, 1, Hp, Wp, 3)     # warped_img0 = warp(img0, flow)
+            self._warp(y, 0, 3, flow, 0, y, 6)     # warped_img0 = warp(img0, flow)
             self._ax(mask, 0, None, 0, y, 9, 1)
         h, w = Hp // 4, Wp // 4
         fdown = T("rs_fdown", 1, h, w, 2)
@@ -354,7 +354,7 @@ class IFUNetEngine(OpsEngine):
             self._conv(c0, src, 0, a, 0)
             self._conv(c1, a, 0, bq, 0)
             if k == 0:
-                self._c("vfi_warp_rife", _p(bq), 32, _p(fdown), 2, _p(cat, 0), 64, 1, h, w, 32)
+                self._warp(bq, 0, 32, fdown, 0, cat, 0)
             else:
                 self._ax(bq, 0, None, 0, cat, 32, 32)
         d1, d2 = T("rs_d1", 1, Hp // 2, Wp // 2, 32), T("rs_d2", 1, Hp, Wp, 8)

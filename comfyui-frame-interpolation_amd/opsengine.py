@@ -1,4 +1,4 @@
-"""Shared plumbing of the op-by-op engines (GMFSS Fortuna, IFUNet): a backend (libvfi_hip.so on the current GPU — or, in the CPU
+"""Shared plumbing of the four op-by-op engines (GMFSS Fortuna, IFUNet, IFRNet, RIFE 4.0): a backend (libvfi_hip.so on the current GPU — or, in the CPU
 orchestration tests only, the test double handed in through ``_test_backend``), scratch tensors, vfi_conv layer objects built
 from checkpoint tensors, and thin wrappers around the generic C-ABI calls.  Every ``torch.cat`` of the reference becomes a
 channel window of a pre-allocated NHWC tensor: wrappers take (tensor, channel offset) pairs."""
@@ -28,13 +28,8 @@ class _Device:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         _lib.check(self.lib.vfi_init(self.device.index or 0), "vfi_init")
 
-    @staticmethod
-    def stream():
-        return _lib.stream_ptr()
-
-    @staticmethod
-    def last_error():
-        return _lib.last_error()
+    stream = staticmethod(_lib.stream_ptr)      # (bound directly: every library call of an eager engine passes through here)
+    last_error = staticmethod(_lib.last_error)
 
 
 class _Pool:
@@ -285,7 +280,7 @@ class OpsEngine:
         if not h:
             raise RuntimeError("vfi_conv_create_ex failed: " + self.be.last_error())
         self.handles.append(h)
-        return dict(h=h, kind=kind, stride=stride, cout=cout, cin=cin, k=int(w.shape[2]), act=3 if pr is not None else 0)
+        return dict(h=h, kind=kind, stride=stride, cout=cout, cin=cin, cin_phys=cin_phys, k=int(w.shape[2]), act=3 if pr is not None else 0)
 
     def _conv(self, L, src, soff, dst, doff, act=None, slope=0.0, res=None):
         n, hin, win, cs = src.shape
@@ -305,6 +300,10 @@ class OpsEngine:
     def _resize(self, src, soff, dst, doff, c, mul=1.0):
         self._c("vfi_resize_bilinear", _p(src, soff), src.shape[-1], _p(dst, doff), dst.shape[-1], src.shape[0], src.shape[1], src.shape[2],
                 dst.shape[1], dst.shape[2], c, mul)
+
+    def _warp(self, src, soff, c, flow, foff, dst, doff):
+        self._c("vfi_warp_rife", _p(src, soff), src.shape[-1], _p(flow, foff), flow.shape[-1], _p(dst, doff), dst.shape[-1], src.shape[0], src.shape[1],
+                src.shape[2], c)
 
     def close(self):
         for h in self.handles:

@@ -16,76 +16,30 @@ widgets land on ``IFNet.forward``'s ``training`` / ``fastmode`` parameters (rife
 architecture only, change the result: ``training=False`` enables the scale doubling (:598-607), ``fastmode=False`` the
 refinement (:725-730).  The scale list is doubled IN PLACE and therefore stays doubled for the rest of the node call.
 """
-import ctypes as C
-
 import torch
 
-from . import _lib
+from .opsengine import OpsEngine, _p
 from .rife_spec import check_state_dict
 
 BLOCK_C = (192, 128, 96, 64)
 
 
-def _p(t, off=0):
-    return t.data_ptr() + 4 * off
-
-
-class _L:
-    """conv (+PReLU) / deconv (+PReLU) layer of the checkpoint."""
-
-    def __init__(self, lib, sd, wkey, bkey, pkey=None, kind=0, stride=1, chan_map=None, cin_phys=None):
-        w = sd[wkey].detach().to("cpu", torch.float32).contiguous()
-        b = sd[bkey].detach().to("cpu", torch.float32).contiguous()
-        pr = sd[pkey].detach().to("cpu", torch.float32).contiguous() if pkey else None
-        cout, cin = (w.shape[0], w.shape[1]) if kind == 0 else (w.shape[1], w.shape[0])
-        self.cin_phys = cin_phys or (cin + 7) // 8 * 8
-        cm = (C.c_int * cin)(*chan_map) if chan_map is not None else None
-        self.lib, self.kind, self.stride, self.act = lib, kind, stride, 3 if pr is not None else 0
-        self.h = lib.vfi_conv_create_ex(kind, w.data_ptr(), b.data_ptr(), cout, cin, w.shape[2], stride, 0, cm, self.cin_phys,
-                                        pr.data_ptr() if pr is not None else None)
-        if not self.h:
-            raise RuntimeError("vfi_conv_create_ex failed: " + _lib.last_error())
-
-    def __call__(self, src, soff, dst, doff, act=None):
-        n, hin, win, cs = src.shape
-        want = (hin * 2, win * 2) if self.kind == 1 else (hin // self.stride, win // self.stride)
-        assert tuple(dst.shape[1:3]) == want and dst.shape[0] == n, (src.shape, dst.shape, want)
-        _lib.check(self.lib.vfi_conv_forward_ex(self.h, _p(src, soff), cs, hin, win, _p(dst, doff), dst.shape[-1], n,
-                                                self.act if act is None else act, 0.0, 0.0, 0.0, None, 0, _lib.stream_ptr()),
-                   "vfi_conv_forward_ex")
-
-    def close(self):
-        if self.h:
-            self.lib.vfi_conv_destroy(self.h)
-            self.h = None
-
-
-class Rife40Engine:
-    def __init__(self, state_dict, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("RIFE VFI (HIP): no GPU visible; this node has no CPU fallback")
-        self.lib = lib = _lib.load()
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        _lib.check(lib.vfi_init(self.device.index or 0), "vfi_init")
+class Rife40Engine(OpsEngine):
+    def __init__(self, state_dict, device=None, _test_backend=None):
+        super().__init__(device, _test_backend, pooled=False)      # every named scratch tensor stays until release_workspace()
         check_state_dict(state_dict, "4.0")
-        sd = state_dict
-        self.layers = []
+        sd, mk = state_dict, self._layer
 
-        def cp(p, stride=1, **k):
-            l = _L(lib, sd, p + ".0.weight", p + ".0.bias", p + ".1.weight", stride=stride, **k)
-            self.layers.append(l)
-            return l
+        def cp(p, stride=1, **k):   # conv(): Conv2d + PReLU
+            return mk(sd[p + ".0.weight"], sd[p + ".0.bias"], sd[p + ".1.weight"], stride=stride, **k)
 
-        def dc(p, **k):
-            l = _L(lib, sd, p + ".0.weight", p + ".0.bias", p + ".1.weight", kind=1, stride=2, **k)
-            self.layers.append(l)
-            return l
+        def dc(p, **k):             # deconv(): ConvTranspose2d(4, 2, 1) + PReLU
+            return mk(sd[p + ".0.weight"], sd[p + ".0.bias"], sd[p + ".1.weight"], kind=1, stride=2, **k)
 
         self.blocks = []
         for b in range(4):
             p = f"block{b}."
-            last = _L(lib, sd, p + "lastconv.weight", p + "lastconv.bias", None, kind=1, stride=2)
-            self.layers.append(last)
+            last = mk(sd[p + "lastconv.weight"], sd[p + "lastconv.bias"], kind=1, stride=2)
             self.blocks.append((cp(p + "conv0.0", 2, cin_phys=8 if b == 0 else 16), cp(p + "conv0.1", 2),
                                 [cp(p + f"convblock.{i}") for i in range(8)], last))
         # Contextnet: the first conv reads the image out of the (img0 | img1 | t) tensor, one layer object per image
@@ -99,79 +53,57 @@ class Rife40Engine:
             return list(range(n, 2 * n)) + list(range(n))
 
         self.up = [dc("unet.up0"), dc("unet.up1", chan_map=swap(128)), dc("unet.up2", chan_map=swap(64)), dc("unet.up3", chan_map=swap(32))]
-        self.uconv = _L(lib, sd, "unet.conv.weight", "unet.conv.bias")
-        self.layers.append(self.uconv)
+        self.uconv = mk(sd["unet.conv.weight"], sd["unet.conv.bias"])
         self.cfg = None
 
-    def close(self):
-        for l in self.layers:
-            l.close()
-        self.layers = []
+    def release_workspace(self):
+        """Drop the activations (``configure`` brings them back); the packed weights stay on the device."""
+        super().release_workspace()
+        self.cfg = self.img = self.xin = self.flow = self.df = self.dm = self.amax = None
 
     # ------------------------------------------------------------------------------------------------
-    def _z(self, *shape):
-        return torch.zeros(shape, dtype=torch.float32, device=self.device)
-
     def configure(self, H, W, B):
         if self.cfg == (H, W, B):
             return
-        torch.cuda.synchronize(self.device)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.release_workspace()           # one shape at a time: the tensors of the previous one go first
         self.Hp, self.Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
-        Hp, Wp, z = self.Hp, self.Wp, self._z
-        self.img = z(B, Hp, Wp, 8)       # (img0 3 | img1 3 | timestep | 0): block-0 input
-        self.xin = z(B, Hp, Wp, 8)       # (warped img0 3 | warped img1 3 | timestep | mask): input of blocks 1..3 (+ flow)
-        self.flow = z(B, Hp, Wp, 4)
-        self.df = z(B, Hp, Wp, 4)
-        self.dm = z(B, Hp, Wp, 1)
-        self.amax = z(2)
-        self.scratch = {}
+        Hp, Wp = self.Hp, self.Wp
+        self.img = self._t("img", B, Hp, Wp, 8)       # (img0 3 | img1 3 | timestep | 0): block-0 input
+        self.xin = self._t("xin", B, Hp, Wp, 8)       # (warped img0 3 | warped img1 3 | timestep | mask): input of blocks 1..3 (+ flow)
+        self.flow = self._t("flow", B, Hp, Wp, 4)
+        self.df = self._t("df", B, Hp, Wp, 4)
+        self.dm = self._t("dm", B, Hp, Wp, 1)
+        self.amax = self._t("amax", 2)
         self.cfg = (H, W, B)
-
-    def _tmp(self, name, h, w, c):
-        key = (name, h, w, c)
-        if key not in self.scratch:
-            self.scratch[key] = self._z(self.cfg[2], h, w, c)
-        return self.scratch[key]
-
-    def _resize(self, src, soff, dst, doff, c, mul=1.0):
-        _lib.check(self.lib.vfi_resize_bilinear(_p(src, soff), src.shape[-1], _p(dst, doff), dst.shape[-1], src.shape[0], src.shape[1],
-                                                src.shape[2], dst.shape[1], dst.shape[2], c, mul, _lib.stream_ptr()), "vfi_resize_bilinear")
-
-    def _warp(self, src, soff, c, flow, foff, dst, doff):
-        _lib.check(self.lib.vfi_warp_rife(_p(src, soff), src.shape[-1], _p(flow, foff), flow.shape[-1], _p(dst, doff), dst.shape[-1],
-                                          src.shape[0], src.shape[1], src.shape[2], c, _lib.stream_ptr()), "vfi_warp_rife")
-
-    def _ax(self, a, aoff, b, boff, out, ooff, c, alpha=1.0, beta=1.0):
-        px = a.shape[0] * a.shape[1] * a.shape[2]
-        _lib.check(self.lib.vfi_axpby(_p(a, aoff), a.shape[-1], _p(b, boff) if b is not None else None, b.shape[-1] if b is not None else 0,
-                                      _p(out, ooff), out.shape[-1], px, c, alpha, beta, _lib.stream_ptr()), "vfi_axpby")
 
     def _block(self, i, x, n_img, has_flow, scale):
         """IFBlock.forward (rife_arch.py:237-261): results in self.df (flow delta * 2*scale) and self.dm (mask delta)."""
-        Hp, Wp = self.Hp, self.Wp
+        Hp, Wp, B = self.Hp, self.Wp, self.cfg[2]
         hs, ws = int(round(Hp / scale)), int(round(Wp / scale))
         if hs * scale != Hp or ws * scale != Wp or hs % 4 or ws % 4:
             raise RuntimeError(f"RIFE 4.0: block scale {scale} does not divide the padded size {Hp}x{Wp} (the reference fails here too)")
         c00, c01, cb, last = self.blocks[i]
         c = BLOCK_C[i]
-        xs = self._tmp("xs", hs, ws, c00.cin_phys)
+        xs = self._t("xs", B, hs, ws, c00["cin_phys"])
         self._resize(x, 0, xs, 0, n_img)
         if has_flow:
             self._resize(self.flow, 0, xs, 8, 4, 1.0 / scale)
-        a = self._tmp("a", hs // 2, ws // 2, c // 2)
-        f = self._tmp("f", hs // 4, ws // 4, c)
-        p, q = self._tmp("p", hs // 4, ws // 4, c), self._tmp("q", hs // 4, ws // 4, c)
-        c00(xs, 0, a, 0)
-        c01(a, 0, f, 0)
+        a = self._t("a", B, hs // 2, ws // 2, c // 2)
+        f = self._t("f", B, hs // 4, ws // 4, c)
+        p, q = self._t("p", B, hs // 4, ws // 4, c), self._t("q", B, hs // 4, ws // 4, c)
+        self._conv(c00, xs, 0, a, 0)
+        self._conv(c01, a, 0, f, 0)
         cur = f
         for k in range(8):
             nxt = p if k % 2 == 0 else q
-            cb[k](cur, 0, nxt, 0)
+            self._conv(cb[k], cur, 0, nxt, 0)
             cur = nxt
         self._ax(cur, 0, f, 0, p if cur is q else q, 0, c)          # convblock(feat) + feat
         r = p if cur is q else q
-        t = self._tmp("t", hs // 2, ws // 2, 8)
-        last(r, 0, t, 0)
+        t = self._t("t", B, hs // 2, ws // 2, 8)
+        self._conv(last, r, 0, t, 0)
         self._resize(t, 0, self.df, 0, 4, scale * 2.0)
         self._resize(t, 4, self.dm, 0, 1)
 
@@ -182,16 +114,14 @@ class Rife40Engine:
     def forward(self, frames0, frames1, timesteps, scale_list, training, fastmode, out):
         """frames0/1: lists of [H,W,C>=3] device tensors, one pair per task; scale_list: the node's LIST (doubled in place when
         the reference would); out [B,H,W,3] device tensor, clamped to [0,1] like the node's output."""
-        lib, st = self.lib, _lib.stream_ptr()
         B = len(timesteps)
         H, W = frames0[0].shape[:2]
         assert self.cfg is not None and self.cfg[:2] == (H, W) and self.cfg[2] == B, (self.cfg, H, W, B)
         Hp, Wp = self.Hp, self.Wp
         for b in range(B):
             f0, f1 = frames0[b], frames1[b]
-            assert f0.is_cuda and f0.is_contiguous() and f1.is_contiguous() and f0.shape == f1.shape
-            _lib.check(lib.vfi_rife40_prep(f0.data_ptr(), f1.data_ptr(), f0.shape[2], H, W, float(timesteps[b]), _p(self.img[b]),
-                                           Hp, Wp, st), "vfi_rife40_prep")
+            assert f0.device.type == self.device.type and f0.is_contiguous() and f1.is_contiguous() and f0.shape == f1.shape
+            self._c("vfi_rife40_prep", f0.data_ptr(), f1.data_ptr(), f0.shape[2], H, W, float(timesteps[b]), _p(self.img[b]), Hp, Wp)
         self._ax(self.img, 6, None, 0, self.xin, 6, 1)              # timestep plane of the later blocks' input
 
         def block0():
@@ -205,8 +135,8 @@ class Rife40Engine:
             self._block(i, self.xin, 8, True, scale_list[i])
             if i == 1 and not training:
                 px = B * Hp * Wp
-                _lib.check(lib.vfi_absmax(_p(self.df, 0), 4, 2, px, _p(self.amax, 0), st), "vfi_absmax")
-                _lib.check(lib.vfi_absmax(_p(self.df, 2), 4, 2, px, _p(self.amax, 1), st), "vfi_absmax")
+                self._c("vfi_absmax", _p(self.df, 0), 4, 2, px, _p(self.amax, 0))
+                self._c("vfi_absmax", _p(self.df, 2), 4, 2, px, _p(self.amax, 1))
                 m = self.amax.cpu()
                 if float(m[0]) > 32 and float(m[1]) > 32:
                     for k in range(4):
@@ -219,29 +149,29 @@ class Rife40Engine:
         res = None
         if not fastmode:
             res = self._refine()
-        _lib.check(lib.vfi_rife40_output(_p(self.xin), 8, _p(self.xin, 7), 8, _p(res) if res is not None else None, 4, out.data_ptr(),
-                                         B, Hp, Wp, H, W, st), "vfi_rife40_output")
+        self._c("vfi_rife40_output", _p(self.xin), 8, _p(self.xin, 7), 8, _p(res) if res is not None else None, 4, out.data_ptr(),
+                B, Hp, Wp, H, W)
         return out
 
     def _refine(self):
         """Contextnet on both images + Unet (rife_arch.py:278-342,725-730) -> sigmoid output [B,Hp,Wp,4] (3 used)."""
-        Hp, Wp = self.Hp, self.Wp
+        Hp, Wp, B = self.Hp, self.Wp, self.cfg[2]
         hw = [(Hp >> j, Wp >> j) for j in range(5)]
-        u = [self._tmp("u0", Hp, Wp, 24)] + [self._tmp(f"u{j}", *hw[j], 64 << (j - 1)) for j in range(1, 5)]
-        fl = [self.flow] + [self._tmp(f"fl{j}", *hw[j], 4) for j in range(1, 5)]
+        u = [self._t("u0", B, Hp, Wp, 24)] + [self._t(f"u{j}", B, *hw[j], 64 << (j - 1)) for j in range(1, 5)]
+        fl = [self.flow] + [self._t(f"fl{j}", B, *hw[j], 4) for j in range(1, 5)]
         for j in range(1, 5):
             self._resize(fl[j - 1], 0, fl[j], 0, 4, 0.5)
         for k in range(2):
             x = None
             for j in range(1, 5):
                 cw = 8 << j                                         # 16, 32, 64, 128 context channels
-                t = self._tmp("ct", *hw[j], cw)
-                y = self._tmp("cy", *hw[j], cw)
+                t = self._t("ct", B, *hw[j], cw)
+                y = self._t("cy", B, *hw[j], cw)
                 if j == 1:
-                    self.ctx1[k](self.img, 0, t, 0)
+                    self._conv(self.ctx1[k], self.img, 0, t, 0)
                 else:
-                    self.ctx[j][0](x, 0, t, 0)
-                self.ctx[j][1](t, 0, y, 0)
+                    self._conv(self.ctx[j][0], x, 0, t, 0)
+                self._conv(self.ctx[j][1], t, 0, y, 0)
                 self._warp(y, 0, cw, fl[j], 2 * k, u[j], 2 * cw + cw * k)   # slots after the 2*cw channels of s_{j-1}
                 x = y
         # Unet
@@ -251,16 +181,16 @@ class Rife40Engine:
         self._ax(self.flow, 0, None, 0, u[0], 13, 4)
         for j in range(4):
             cw = 32 << j
-            t = self._tmp("dt", *hw[j + 1], cw)
-            self.down[j][0](u[j], 0, t, 0)
-            self.down[j][1](t, 0, u[j + 1], 0)
-        self.up[0](u[4], 0, u[3], 128)                              # x over the consumed context slots: [s2 | x]
-        self.up[1](u[3], 0, u[2], 64)
-        self.up[2](u[2], 0, u[1], 32)
-        uf = self._tmp("uf", Hp, Wp, 16)
-        self.up[3](u[1], 0, uf, 0)
-        res = self._tmp("res", Hp, Wp, 4)
-        self.uconv(uf, 0, res, 0, act=4)
+            t = self._t("dt", B, *hw[j + 1], cw)
+            self._conv(self.down[j][0], u[j], 0, t, 0)
+            self._conv(self.down[j][1], t, 0, u[j + 1], 0)
+        self._conv(self.up[0], u[4], 0, u[3], 128)                  # x over the consumed context slots: [s2 | x]
+        self._conv(self.up[1], u[3], 0, u[2], 64)
+        self._conv(self.up[2], u[2], 0, u[1], 32)
+        uf = self._t("uf", B, Hp, Wp, 16)
+        self._conv(self.up[3], u[1], 0, uf, 0)
+        res = self._t("res", B, Hp, Wp, 4)
+        self._conv(self.uconv, uf, 0, res, 0, act=4)
         return res
 
 

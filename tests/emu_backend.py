@@ -1,7 +1,7 @@
 """TEST DOUBLE of the C ABI (include/vfi_hip.h) for orchestration tests on the CPU — test infrastructure only.
 
-The GMFSS engine (comfyui-frame-interpolation_amd/gmfss.py) talks to its backend through raw pointers, like any client of
-libvfi_hip.so.  This backend serves those calls on HOST memory so that the engine's orchestration (layer wiring, channel
+The op-by-op engines (comfyui-frame-interpolation_amd/opsengine.py: GMFSS, IFUNet, IFRNet, RIFE 4.0) talk to their backend through
+raw pointers, like any client of libvfi_hip.so.  This backend serves those calls on HOST memory so that an engine's orchestration (layer wiring, channel
 windows, batch layout, schedule) can be checked against the oracle without a GPU:
   * the GMFSS kernels of csrc/gmfss_ops.hip: the real per-element bodies, through tests/hostcheck (same entry points);
   * the older entry points the engine also uses (layer objects, resize, axpby, warps, the summation splat, ...): small torch
@@ -15,6 +15,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import gen_ops_restated
 import hostcheck
 from oracle import m2m_oracle, rife_oracle
 
@@ -233,11 +234,67 @@ class EmuLib:
         return 0
 
     def vfi_rife40_output(self, w01_ptr, w_cs, mask_ptr, m_cs, res_ptr, r_cs, out_ptr, b, hp, wp, h, w, stream):
-        assert not res_ptr
         w01 = view(w01_ptr, b, hp, wp, w_cs, 6)
         m = torch.sigmoid(view(mask_ptr, b, hp, wp, m_cs, 1))
-        y = (w01[..., 0:3] * m + w01[..., 3:6] * (1 - m)).clamp(0, 1)
-        view(out_ptr, b, h, w, 3, 3).copy_(y[:, :h, :w])
+        y = w01[..., 0:3] * m + w01[..., 3:6] * (1 - m)
+        if res_ptr:                                    # the Unet refinement
+            y = y + (view(res_ptr, b, hp, wp, r_cs, 3) * 2 - 1)
+        view(out_ptr, b, h, w, 3, 3).copy_(y.clamp(0, 1)[:, :h, :w])
+        return 0
+
+    def vfi_absmax(self, x_ptr, cs, c, pixels, out_ptr, stream):
+        view(out_ptr, 1, 1, 1, 1, 1)[0, 0, 0, 0] = view(x_ptr, 1, 1, pixels, cs, c).abs().max()
+        return 0
+
+    # ---- IFRNet building blocks (csrc/ifrnet_ops.hip; float64 statements of the same formulas: tests/gen_ops_restated.py) ---------
+    def vfi_ifrnet_prep(self, f0_ptr, f1_ptr, c, h, w, img0_ptr, img1_ptr, hp, wp, stream):
+        for f_ptr, img_ptr in ((f0_ptr, img0_ptr), (f1_ptr, img1_ptr)):
+            out = view(img_ptr, 1, hp, wp, 4, 4)
+            out.zero_()
+            out[0, :h, :w, 0:3] = view(f_ptr, 1, h, w, c, 3)[0]
+        return 0
+
+    def vfi_pool_mean(self, in_ptr, in_cs, out_ptr, out_cs, n, h, w, c, mode, stream):
+        x = view(in_ptr, n, h, w, in_cs, c)
+        y, rows = {0: (x.mean((1, 2)), 1), 1: (x.mean(2), h), 2: (x.mean(1), w)}[mode]
+        view(out_ptr, n, 1, rows, out_cs, c).copy_(y.reshape(n, 1, rows, c))
+        return 0
+
+    def vfi_ifrnet_center(self, img_ptr, cm_ptr, mean_ptr, n, pixels, stream):
+        cm = view(cm_ptr, 1, 1, 2 * n, 4, 3)[0, 0]
+        m = (cm[:n].sum(1) + cm[n:].sum(1)) / 6
+        view(mean_ptr, 1, 1, 1, n, n)[0, 0, 0] = m
+        view(img_ptr, 2 * n, 1, pixels, 4, 3).sub_(m.repeat(2).view(2 * n, 1, 1, 1))
+        return 0
+
+    def vfi_sigmoid(self, x_ptr, cs, c, pixels, stream):
+        x = view(x_ptr, 1, 1, pixels, cs, c)
+        x.copy_(torch.sigmoid(x))
+        return 0
+
+    def vfi_fill_items(self, out_ptr, cs, c, n, ppi, values, stream):
+        assert n <= 64
+        view(out_ptr, n, 1, ppi, cs, c)[:] = host_array(values, n).view(n, 1, 1, 1)
+        return 0
+
+    def vfi_resize_bilinear_ratio(self, in_ptr, in_cs, out_ptr, out_cs, n, hin, win, hout, wout, c, ratio_h, ratio_w, post_mul, stream):
+        x = view(in_ptr, n, hin, win, in_cs, c).double()
+        y = gen_ops_restated._resize(x, float(np.float32(ratio_h)), float(np.float32(ratio_w)), hout, wout, gen_ops_restated.R_RATIO)[0]
+        view(out_ptr, n, hout, wout, out_cs, c).copy_(y * float(np.float32(post_mul)))
+        return 0
+
+    def vfi_ifrnet_output(self, img0_ptr, img1_ptr, fin_ptr, mean_ptr, out_ptr, n, hp, wp, hf, wf, h, w, stream):
+        """the warp grid has the flow's size hf x wf, the images hp x wp (align_corners=True, border): gen_ops_restated.op_ifrnet_output"""
+        assert 0 < h <= min(hp, hf) and 0 < w <= min(wp, wf)
+        fin = view(fin_ptr, n, hf, wf, 8, 8).double()
+        X, Y = torch.arange(wf, dtype=torch.float64).view(1, 1, wf), torch.arange(hf, dtype=torch.float64).view(1, hf, 1)
+        warped = []
+        for k, ptr in enumerate((img0_ptr, img1_ptr)):
+            px, py = (X + fin[..., 2 * k]) * ((wp - 1) / (wf - 1)), (Y + fin[..., 2 * k + 1]) * ((hp - 1) / (hf - 1))
+            warped.append(gen_ops_restated.bilinear(view(ptr, n, hp, wp, 4, 3).double(), px, py, True)[0])
+        m = fin[..., 4:5]
+        y = m * warped[0] + (1 - m) * warped[1] + host_array(mean_ptr, n).double().view(n, 1, 1, 1) + fin[..., 5:8]
+        view(out_ptr, n, h, w, 3, 3).copy_(y.clamp(0, 1)[:, :h, :w])
         return 0
 
 

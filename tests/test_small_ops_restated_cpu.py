@@ -5,7 +5,7 @@ min-summand conditions and the 1 % cap on left-out occlusion bits hold for the c
 the launch-tail guards of the bodies are NOT exercised here: that is the GPU file's half.
 
 csrc/rife40_ops.hip has no host build: its four restatements are checked against oracle.rife_oracle.warp and the torch expressions
-of tests/emu_backend.py (and two more written here: |x| maximum, the output blend with a residual) within the same bounds.
+of tests/emu_backend.py (|x| maximum and the output blend with a residual among them) within the same bounds.
 
 Negative controls: each compares a case with a deliberately wrong restatement (a tap index off by one, a channel dropped from a
 window, a softmax / blend term omitted) and must fail — the bounds are tight enough to see them."""
@@ -25,9 +25,9 @@ def lib():
 
 
 class _Rife40Torch(emu_backend.EmuLib):
-    """the RIFE 4.0 entry points as torch expressions on host memory (fp32): emu_backend's, + vfi_absmax and the residual form"""
+    """the RIFE 4.0 entry points as torch expressions on host memory (fp32): emu_backend's"""
 
-    def __init__(self):          # no host library behind it: only the four entry points below are called
+    def __init__(self):          # no host library behind it: only the four RIFE 4.0 entry points are called
         pass
 
     def __getattribute__(self, name):
@@ -35,20 +35,6 @@ class _Rife40Torch(emu_backend.EmuLib):
         if not name.startswith("vfi_"):
             return fn
         return lambda *a: fn(*[x.value if isinstance(x, C.c_float) else x for x in a])
-
-    def vfi_absmax(self, x_ptr, cs, c, pixels, out_ptr, stream):
-        emu_backend.view(out_ptr, 1, 1, 1, 1, 1)[0, 0, 0, 0] = emu_backend.view(x_ptr, 1, 1, pixels, cs, c).abs().max()
-        return 0
-
-    def vfi_rife40_output(self, w01_ptr, w_cs, mask_ptr, m_cs, res_ptr, r_cs, out_ptr, b, hp, wp, h, w, stream):
-        if not res_ptr:
-            return emu_backend.EmuLib.vfi_rife40_output(self, w01_ptr, w_cs, mask_ptr, m_cs, res_ptr, r_cs, out_ptr, b, hp, wp, h, w, stream)
-        w01 = emu_backend.view(w01_ptr, b, hp, wp, w_cs, 6)
-        m = torch.sigmoid(emu_backend.view(mask_ptr, b, hp, wp, m_cs, 1))
-        y = w01[..., 0:3] * m + w01[..., 3:6] * (1 - m)
-        y = torch.clamp(y + (emu_backend.view(res_ptr, b, hp, wp, r_cs, 3) * 2 - 1), 0, 1)
-        emu_backend.view(out_ptr, b, h, w, 3, 3).copy_(y[:, :h, :w])
-        return 0
 
 
 @pytest.mark.parametrize("case", so.BODY_CASES, ids=lambda c: c.id)
