@@ -18,6 +18,7 @@ _LAZY = {
     "FLAVR_VFI": ("flavr", "FLAVR_VFI"),
     "AMT_VFI": ("amt", "AMT_VFI"),
     "ATM_VFI": ("atm", "ATM_VFI"),
+    "XVFI": ("xvfi", "XVFI"),
     "MakeInterpolationStateList": ("schedule", "MakeInterpolationStateList"),
     "InterpolationStateList": ("schedule", "InterpolationStateList"),
 }
@@ -66,6 +67,10 @@ def _node_class_mappings():
         from .atm import ATM_VFI
 
         extra["ATM VFI"] = ATM_VFI
+    if "xvfi" in extra_nodes():
+        from .xvfi import XVFI
+
+        extra["XVFI VFI"] = XVFI
     return {
         "RIFE VFI": RIFE_VFI,
         "FILM VFI": FILM_VFI,
@@ -84,9 +89,10 @@ def _node_class_mappings():
 # "atm" is not a key.  ATM VFI serves atm-vfi-lite.pt (ATM-lite) with global motion "On" or "Off (fastest)", and atm-vfi-base.pt /
 # atm-vfi-base-pct.pt (ATM-base) only when config.yaml's atm_base key is on as well (atm_spec.atm_base_enabled).
 # AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled).
+# XVFI's key is "xvfi" (the reference's class is XVFI; upstream never registered it, so the node's name "XVFI VFI" follows the other nodes').
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
                "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)"),
-               "atm_vfi": ("ATM VFI", "ATM VFI (MI355X HIP)")}
+               "atm_vfi": ("ATM VFI", "ATM VFI (MI355X HIP)"), "xvfi": ("XVFI VFI", "XVFI VFI (MI355X HIP)")}
 
 
 def extra_nodes():

@@ -259,6 +259,20 @@ PROTOTYPES = {
     "vfi_atm_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
     "vfi_atm_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_atm_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "vfi_xvfi_bicubic_down": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_xvfi_bwarp": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p]),
+    "vfi_xvfi_cfr": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_xvfi_assemble": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p]),
+    "vfi_xvfi_blend_out": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_xvfi_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int]),
+    "vfi_xvfi_destroy": (None, [C.c_void_p]),
+    "vfi_xvfi_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "vfi_xvfi_level0_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vfi_xvfi_max_padded_pixels": (C.c_int64, []),
+    "vfi_xvfi_release_workspace": (C.c_int, [C.c_void_p]),
+    "vfi_xvfi_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_m2m_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
     "vfi_m2m_destroy": (None, [C.c_void_p]),
     "vfi_m2m_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -34,7 +34,9 @@ EXTRA_FLAGS = {"conv_wino.hip": ["-fno-slp-vectorize"],
                # the lookup's coordinates are coord + flow * scale with two roundings, as torch computes them; dots and convolutions call fmaf
                "amt_net.hip": ["-ffp-contract=off"],
                # ATM: `score * scale + mask` and the warps' grid coordinates round as torch rounds them; dots and convolutions call fmaf
-               "atm_net.hip": ["-ffp-contract=off"]}
+               "atm_net.hip": ["-ffp-contract=off"],
+               # XVFI: a splat target is the single product t * flow, so that floor() sees what torch sees; the warps' grid coordinates likewise
+               "xvfi_net.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

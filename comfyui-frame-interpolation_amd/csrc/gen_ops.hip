@@ -10,6 +10,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -167,6 +168,27 @@ __global__ void axpby4_kernel(const float* __restrict__ a, int a_cs, const float
     *(float4*)(out + (size_t)p * out_cs + 4 * g) = v;
 }
 
+// ---- space-to-depth of the zero-padded image, in front of the 4x4 stride-2 layer form -------------------------------------------
+// out[n, Y, X, (2 py + px) C + c] = in[n, 2 Y - 1 + py, 2 X - 1 + px, c] (zero outside the image) for Y <= H / 2, X <= W / 2: tap (ky, kx) of
+// Conv2d(k = 4, stride 2, pad 1) at output (y, x) reads row 2 y - 1 + ky = 2 (y + (ky >> 1)) - 1 + (ky & 1), so over this image the layer
+// is a 2x2 stride-1 convolution with 4 C channels whose taps start at the output pixel.  One thread per float4.
+__global__ void s2d_pad1_kernel(const float* __restrict__ in, int in_cs, float* __restrict__ out, int N, int H, int W, int C4) {
+    const int Hs = H / 2 + 1, Ws = W / 2 + 1;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)N * Hs * Ws * 4 * C4) return;
+    const int q = (int)(idx % C4);
+    long p = idx / C4;
+    const int par = (int)(p & 3);
+    p >>= 2;
+    const int X = (int)(p % Ws);
+    p /= Ws;
+    const int Y = (int)(p % Hs), n = (int)(p / Hs);
+    const int iy = 2 * Y - 1 + (par >> 1), ix = 2 * X - 1 + (par & 1);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = *(const float4*)(in + ((size_t)((size_t)n * H + iy) * W + ix) * in_cs + 4 * q);
+    ((float4*)out)[idx] = v;
+}
+
 }  // namespace vfi
 
 using namespace vfi;
@@ -188,7 +210,27 @@ struct vfi_conv {
     int stride = 1, pad_mode = 0, kind = 0;  // kind 0: Conv2d, 1: ConvTranspose2d(4, 2, 1), 2: nearest x2 up-sampling + Conv2d(2, 'same') (vfi_conv_create_up2x2)
     unsigned char* tapmask = nullptr;         // kind 2: taps of every 64-channel N block's parity
     bool odd_ok = false;                      // 3x3 stride-2 layer that takes odd input sizes (vfi_conv_accept_odd)
+    int cin_src = 0;                          // 4x4 stride-2 layer (kh == 4): channels of the caller's input window; Cin_p = 4 * cin_src is the
+                                              //   space-to-depth image's (s2d_pad1_kernel), over which the layer is a 2x2 stride-1 one (taps == 4)
 };
+
+// the space-to-depth image of a 4x4 stride-2 layer's input, per (device, stream): grow-only, kept for the life of the process (an
+// outgrown block is retired, not freed, as the split-K workspace is: conv_mfma2.hip)
+static int s2d_workspace(hipStream_t s, size_t floats, float** out) {
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, std::pair<float*, size_t>> table;
+    int dev = 0;
+    VFI_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto& w = table[{dev, s}];
+    if (w.second < floats) {
+        w.first = nullptr, w.second = 0;
+        VFI_CHECK_HIP(hipMalloc((void**)&w.first, floats * sizeof(float)));
+        w.second = floats;
+    }
+    *out = w.first;
+    return 0;
+}
 
 static unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
 
@@ -328,7 +370,8 @@ static bool upload(float** dst, const std::vector<float>& v) {
 
 vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_host, int Cout, int Cin, int k, int stride,
                                int pad_mode, const int* chan_map, int Cin_phys, const float* prelu_host) {
-    const bool conv_ok = kind == 0 && ((k == 3 && (stride == 1 || stride == 2)) || (k == 2 && stride == 2) || (k == 1 && stride == 1));
+    const bool s2d = kind == 0 && k == 4 && stride == 2 && pad_mode == 0;      // Conv2d(4, 2, 1): the polyphase form
+    const bool conv_ok = kind == 0 && ((k == 3 && (stride == 1 || stride == 2)) || (k == 2 && stride == 2) || (k == 1 && stride == 1) || s2d);
     const bool deconv_ok = kind == 1 && k == 4 && stride == 2;
     if (!w_host || Cout <= 0 || Cin <= 0 || !(conv_ok || deconv_ok) || Cin_phys % 8 || Cin_phys < Cin || pad_mode < 0 || pad_mode > 2 ||
         (pad_mode == 2 && !(kind == 0 && k == 3))) {
@@ -341,12 +384,13 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
     c->Cout = Cout;
     c->Cout_p = round_up(Cout, 32);
     c->Cin = Cin;
-    c->Cin_p = Cin_phys;
+    c->Cin_p = s2d ? 4 * Cin_phys : Cin_phys;
+    c->cin_src = s2d ? Cin_phys : 0;
     c->kh = c->kw = k;
-    c->taps = kind == 1 ? 4 : k * k;
+    c->taps = kind == 1 || s2d ? 4 : k * k;
     c->stride = stride;
     c->pad_mode = pad_mode;
-    const int cin8 = Cin_phys / 8, ngrp = kind == 1 ? 4 : 1;
+    const int cin8 = c->Cin_p / 8, ngrp = kind == 1 ? 4 : 1;
     std::vector<float> wp((size_t)ngrp * c->taps * cin8 * c->Cout_p * 8, 0.f), bp((size_t)ngrp * c->Cout_p, 0.f);
     for (int ci = 0; ci < Cin; ++ci) {
         const int pc = chan_map ? chan_map[ci] : ci;
@@ -356,7 +400,14 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
             return nullptr;
         }
         for (int co = 0; co < Cout; ++co) {
-            if (kind == 0) {
+            if (s2d) {
+                // tap (ky, kx) = (2 a + py, 2 b + px): 2x2 tap (a, b) of channel (2 py + px) * Cin_phys + pc of the space-to-depth image
+                for (int ky = 0; ky < 4; ++ky)
+                    for (int kx = 0; kx < 4; ++kx) {
+                        const int t = (ky >> 1) * 2 + (kx >> 1), sc = ((ky & 1) * 2 + (kx & 1)) * Cin_phys + pc;
+                        wp[(((size_t)t * cin8 + sc / 8) * c->Cout_p + co) * 8 + (sc & 7)] = w_host[(((size_t)co * Cin + ci) * 4 + ky) * 4 + kx];
+                    }
+            } else if (kind == 0) {
                 for (int t = 0; t < c->taps; ++t)
                     wp[(((size_t)t * cin8 + pc / 8) * c->Cout_p + co) * 8 + (pc & 7)] = w_host[((size_t)co * Cin + ci) * c->taps + t];
             } else {
@@ -414,8 +465,9 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
                         int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs, void* stream) {
     VFI_REQUIRE(c && in_dev && out_dev && N > 0 && Hin > 0 && Win > 0, "vfi_conv_forward_ex: bad arguments");
     VFI_REQUIRE(c->pad_mode != 2 || (Hin >= 2 && Win >= 2), "vfi_conv_forward_ex: reflection padding needs at least 2x2 pixels (%dx%d)", Hin, Win);
-    VFI_REQUIRE(in_cs >= c->Cin_p && in_cs % 4 == 0 && ((uintptr_t)in_dev & 15) == 0,
-                "vfi_conv_forward_ex: input window must hold %d channels, 16-byte aligned (in_cs=%d)", c->Cin_p, in_cs);
+    const int cin_win = c->cin_src ? c->cin_src : c->Cin_p;
+    VFI_REQUIRE(in_cs >= cin_win && in_cs % 4 == 0 && ((uintptr_t)in_dev & 15) == 0,
+                "vfi_conv_forward_ex: input window must hold %d channels, 16-byte aligned (in_cs=%d)", cin_win, in_cs);
     VFI_REQUIRE(act != 3 || c->prelu, "vfi_conv_forward_ex: act 3 (per-channel PReLU) needs slopes given at create time");
     // a 3x3 stride-2 layer opted in through vfi_conv_accept_odd takes odd sizes (nn.Conv2d(k=3, s=2, p=1): ceil(Hin/2) rows; the direct
     // kernels bound their input reads by Hin / Win, so the missing last row / column reads as padding); every other one stays even-only
@@ -456,7 +508,29 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
         a.Hout = (Hin + c->stride - 1) / c->stride;     // = Hin / stride for the even sizes
         a.Wout = (Win + c->stride - 1) / c->stride;
         a.tap_y0 = a.tap_x0 = c->kh == 3 ? -1 : 0;
-        snprintf(name, sizeof(name), "conv%dx%ds%d_%dto%d", c->kh, c->kw, c->stride, c->Cin_p, c->Cout);
+        snprintf(name, sizeof(name), "conv%dx%ds%d_%dto%d", c->kh, c->kw, c->stride, cin_win, c->Cout);
+    }
+    if (c->cin_src) {
+        // Conv2d(4, 2, 1) in its polyphase form: the space-to-depth image of the padded input ((Hin / 2 + 1) x (Win / 2 + 1) pixels of
+        // 4 * cin_src channels), then the 2x2 stride-1 direct kernel over it; the kernel bounds its loads by Hin / Win and its tiles and
+        // stores by Hout / Wout, so the image's extra row and column are read as the taps' far side and no output is made for them
+        const int Hs = Hin / 2 + 1, Ws = Win / 2 + 1;
+        VFI_REQUIRE((long)N * Hs * Ws * 4 * (c->cin_src / 4) / 256 < 0x7fffffffL, "vfi_conv_forward_ex: %d x %dx%d is too large for the 4x4 stride-2 form", N, Hin, Win);
+        float* sd = nullptr;
+        if (int rc = s2d_workspace((hipStream_t)stream, (size_t)N * Hs * Ws * c->Cin_p, &sd)) return rc;
+        {
+            TraceScope ts("conv4x4s2_s2d", (hipStream_t)stream);
+            hipLaunchKernelGGL(s2d_pad1_kernel, dim3(nblk((long)N * Hs * Ws * c->Cin_p / 4)), dim3(256), 0, (hipStream_t)stream, in_dev, in_cs, sd, N, Hin, Win,
+                               c->cin_src / 4);
+            VFI_CHECK_HIP(hipGetLastError());
+        }
+        a.in = sd, a.in_cs = c->Cin_p, a.Hin = Hs, a.Win = Ws, a.tap_y0 = a.tap_x0 = 0;
+        static const bool by_shape4 = getenv("VFI_TRACE_SHAPES") != nullptr;
+        if (by_shape4) snprintf(name + strlen(name), sizeof(name) - strlen(name), "@%dx%dx%d", N, a.Hout, a.Wout);
+        static std::map<std::string, const char*> names4;
+        auto it4 = names4.find(name);
+        if (it4 == names4.end()) it4 = names4.emplace(name, strdup(name)).first;
+        return conv_launch(a, 1, false, -1, (hipStream_t)stream, it4->second);
     }
     static const bool by_shape = getenv("VFI_TRACE_SHAPES") != nullptr;      // per-shape trace rows: append the OUTPUT size and batch
     if (by_shape) snprintf(name + strlen(name), sizeof(name) - strlen(name), "@%dx%dx%d", N, c->kind == 1 ? 2 * Hin : a.Hout, c->kind == 1 ? 2 * Win : a.Wout);

@@ -846,6 +846,56 @@ int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* net);
 int vfi_atm_release_workspace(vfi_atm_t* net);
 int64_t vfi_atm_workspace_bytes(const vfi_atm_t* net);
 
+/* ---- XVFI (vfi_models/xvfi/xvfi_arch.py XVFInet, inference path): the kernels beside the layer objects ------------------------------------------ */
+
+/* F.interpolate(x, scale_factor=1/l, mode='bicubic', align_corners=False) for l = 2, 4, 8, ... (VFInet.forward :156): at these ratios a fixed
+ * separable 4-tap filter, taps -3/32, 19/32, 19/32, -3/32 over rows / columns l i + l / 2 - 2 .. l i + l / 2 + 1 clamped to the image.  in
+ * [N,H,W,in_cs], a C-channel window; out [N,H/l,W/l,out_cs]; l must divide H and W.  (The reference computes this pyramid at every level and,
+ * at inference, uses level 0 only, which is the frame itself: vfi_xvfi_forward does not call it.) */
+int vfi_xvfi_bicubic_down(const float* in_dev, int in_cs, float* out_dev, int out_cs, int N, int H, int W, int C, int l, void* stream);
+/* VFInet.bwarp (:240-268): grid_sample(x, grid, bilinear, zeros, align_corners=True) at pixel + flow, the position taken through the
+ * reference's normalise / grid_sample's un-normalise in fp32, times the gate that is 0 where the all-ones image sampled the same way is below
+ * 0.999.  Image n of in / flow / out starts n * in_ns / flow_ns / out_ns floats behind image 0 (so the two directions of a pair may be channel
+ * windows of one tensor); in_swap != 0 samples the partner image n ^ 1.  flow = [dx, dy].  A non-finite position gives 0. */
+int vfi_xvfi_bwarp(const float* in_dev, int in_cs, int64_t in_ns, int in_swap, const float* flow_dev, int flow_cs, int64_t flow_ns, float* out_dev,
+                   int out_cs, int64_t out_ns, int N, int H, int W, int C, void* stream);
+/* Complementary Flow Reversal (:183-198): flow_dev [h,w,flow_cs] = (flow_01 xy, flow_10 xy), z_dev [h,w,z_cs] = the two importance logits;
+ * out_dev [h,w,out_cs] = (flow_t0 xy, flow_t1 xy): both z_fwarp splats (:320-415: Gaussian corner weights around floor(t flow) resp.
+ * floor((1 - t) flow), weighted by sigmoid(z) + 1e-5), the numerators of Eq. (1) / (2), norm_l and the division where norm_l > 0.
+ * Deterministic: a gather per target cell, the contributing sources visited in row-major order, no floating-point atomics.  The search
+ * window is the range of floor(t flow) over the sources that reach the image at all (one single-workgroup pass; scratch_dev >= 32 bytes), so
+ * the cost is (range_y + 2) (range_x + 2) sources per cell and direction; a non-finite or out-of-image target contributes nothing. */
+int vfi_xvfi_cfr(const float* flow_dev, int flow_cs, const float* z_dev, int z_cs, float t, float* out_dev, int out_cs, void* scratch_dev, int h, int w,
+                 void* stream);
+/* Level 0's RefineUNet input in one pass (:213-221), out_dev [scale h, scale w, out_cs]: channels 0 .. 256 / scale^2 = pixel_shuffle(cat(feat0,
+ * feat1, warped0, warped1), scale) from feat_dev / warped_dev [2,h,w,.] (64 channels each), then frame 0, frame 1 (img_dev [2, scale h, scale w,
+ * img_cs]), bwarp(frame 0, flow_t0), bwarp(frame 1, flow_t1), flow_t0, flow_t1 with flow_t* = scale * F.interpolate(flow_dev's channels 0..1 /
+ * 2..3, scale_factor=scale, 'bilinear', align_corners=False).  scale 2 or 4. */
+int vfi_xvfi_assemble(const float* feat_dev, int feat_cs, const float* warped_dev, int warped_cs, const float* flow_dev, int flow_cs, const float* img_dev,
+                      int img_cs, float* out_dev, int out_cs, int h, int w, int scale, void* stream);
+/* The occlusion blend plus residual (:222-226) and the node's crop: out [H,W,3] = ((1 - t) occ0 w0 + t occ1 w1) / ((1 - t) occ0 + t occ1) + res with
+ * occ0 = sigmoid(refine[0]), occ1 = 1 - occ0, res = refine[1..3]; warped_dev = (w0 rgb | w1 rgb) per pixel of the padded Hp x Wp frame.  Not clamped. */
+int vfi_xvfi_blend_out(const float* refine_dev, int refine_cs, const float* warped_dev, int warped_cs, float t, float* out_dev, int Hp, int Wp, int H, int W,
+                       void* stream);
+
+typedef struct vfi_xvfi vfi_xvfi_t;
+/* The state_dict tensors of XVFInet in xvfi_spec.xvfi_shapes() order, aliased keys included (72 for module_scale_factor 2, 74 for 4; fp32 host
+ * memory, copied); S_tst = the lowest scale level at inference.  Replaces XVFInet(args).load_state_dict (vfi_models/xvfi/__init__.py:25-37). */
+vfi_xvfi_t* vfi_xvfi_create(const float* const* tensors, const int64_t* numels, int n_tensors, int scale, int S_tst);
+void vfi_xvfi_destroy(vfi_xvfi_t* net);
+/* model(I0, I1, t) of the node for ONE pair and one timestep (xvfi/__init__.py:39-46, :84-114; XVFInet.forward with is_training=False): frames
+ * [H,W,C>=3] fp32 (not written) are zero-padded at the bottom / right to multiples of 2^S_tst * scale * 4, out_dev [H,W,3] is the cropped
+ * result, not clamped.  The features of both frames at every level, the level flows and level 0's flow_l_tmp do not depend on t: they are
+ * computed when the pair differs from the one the object holds (compared bit for bit on the device; one stream synchronisation) and kept while t
+ * varies.  A frame whose padded size exceeds vfi_xvfi_max_padded_pixels() = (2^31 - 1) / 320 = 6 710 886 pixels is refused before any launch:
+ * the widest per-image buffer (the RefineUNet's input at scale 2) has 80 floats per padded pixel and the layers index an image with 32 bits. */
+int vfi_xvfi_forward(vfi_xvfi_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, float t, float* out_dev, void* stream);
+/* out_dev [Hp / scale, Wp / scale, 6] = level 0's flow_l_tmp (:177) of the pair the object holds */
+int vfi_xvfi_level0_flow(vfi_xvfi_t* net, float* out_dev, void* stream);
+int64_t vfi_xvfi_max_padded_pixels(void);
+int vfi_xvfi_release_workspace(vfi_xvfi_t* net);
+int64_t vfi_xvfi_workspace_bytes(const vfi_xvfi_t* net);
+
 #ifdef __cplusplus
 }
 #endif
