@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .amt_spec import CKPT_VARIANT, amt_shapes, check_state_dict, load_file, variant_of_ckpt
 from .ckpt import cached_engine, engine_call, load_file_from_direct_url
-from .netengine import NetEngine, WorkspaceBytes
+from .netengine import NetEngine, WorkspaceBytes, check_frames, padded_to
 from .nodeloop import run_plan
 from .schedule import InterpolationStateList, generic_output_plan
 
@@ -33,7 +33,7 @@ MAX_PADDED_PIXELS_G = ((1 << 31) - 1) // (G_FLOATS_PER_PADDED_PIXEL * 4)
 
 def padded_size(H, W):
     """InputPadder(dims, 16) (amt_arch.py:194-200): the sides rounded up to multiples of 16"""
-    return H + (((H // 16) + 1) * 16 - H) % 16, W + (((W // 16) + 1) * 16 - W) % 16
+    return padded_to(H, 16), padded_to(W, 16)
 
 
 def check_frame_size(H, W, variant=None):
@@ -63,9 +63,7 @@ class AmtEngine(WorkspaceBytes, NetEngine):
 
     def forward(self, frame0, frame1, ts, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written), ts: timesteps in (0, 1) -> [len(ts),H,W,3]."""
-        H, W, Cc = frame0.shape
-        for f in (frame0, frame1):
-            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        H, W, Cc = check_frames(frame0, frame1)
         check_frame_size(H, W, self.variant)
         ts = [float(t) for t in ts]
         assert ts, "ts: at least one timestep"

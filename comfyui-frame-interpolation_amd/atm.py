@@ -19,7 +19,7 @@ from . import _lib
 from .atm_spec import CKPT_NAMES, VARIANTS, atm_ensemble_enabled, check_ckpt_name, check_state_dict, load_file, weight_shapes
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film import film_schedule
-from .netengine import NetEngine, WorkspaceBytes
+from .netengine import NetEngine, WorkspaceBytes, check_frames, padded_to
 from .nodeloop import run_plan
 from .schedule import InterpolationStateList, film_output_plan
 
@@ -36,7 +36,7 @@ MAX_PADDED_PIXELS_BASE = ((1 << 31) - 1) // (BASE_FLOATS_PER_PADDED_PIXEL * 4)  
 
 def padded_size(H, W):
     """InputPadder(dims, 64) (atm/__init__.py:13-17): the sides rounded up to multiples of 64"""
-    return H + (((H // 64) + 1) * 64 - H) % 64, W + (((W // 64) + 1) * 64 - W) % 64
+    return padded_to(H, 64), padded_to(W, 64)
 
 
 def check_frame_size(H, W, variant="lite"):
@@ -86,9 +86,7 @@ class AtmEngine(WorkspaceBytes, NetEngine):
 
     def forward(self, frame0, frame1, global_motion=True, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
-        H, W, Cc = frame0.shape
-        for f in (frame0, frame1):
-            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        H, W, Cc = check_frames(frame0, frame1)
         check_frame_size(H, W, self.variant)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)

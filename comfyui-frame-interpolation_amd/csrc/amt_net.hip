@@ -4,7 +4,7 @@
 //   amt_pool2 / amt_lookup   the bidirectional correlation lookup WITHOUT the all-pairs volume (BidirCorrBlock, :1076-1141)
 //   conv7x7                  7x7 stride-1 zero-padded convolution for thin layers (convf1, AMT-L's comb_block)
 //   amt_warps / amt_out      multi_flow_combine around comb_block (:869-902), clamp and un-pad
-//   amt_pad / amt_mean_* / amt_center   InputPadder's centred replicate pad, mean_ over the padded pair (deterministic), its subtraction
+//   amt_mean_* / amt_center  mean_ over the padded pair (deterministic), its subtraction; the pad itself is net_object.h's pad_frame_pair
 //   amt_upsample_lrelu       leaky_relu(bilinear x2 / x4 up-sampling) in one pass: AMT-G's update*_high blocks after their commuted convc1
 //   amt_add / amt_warp       residual sums, channel-window and stride-2 copies; amt_arch.warp of a feature window (rife_warp.h's taps)
 //
@@ -23,8 +23,6 @@ namespace {
 
 constexpr int kLevels = 4, kRadius = 3, kWin = 2 * kRadius + 1, kNb = kWin + 1;   // 7x7 taps from an 8x8 integer neighbourhood
 constexpr int kMaxD = 256;
-
-inline int nblk(long n, int per) { return (int)((n + per - 1) / per); }
 
 // out [hin/2][win/2][D] = avg_pool2d(in [hin][win][D], 2, stride 2): odd rows / columns at the end are dropped
 __global__ void amt_pool2_kernel(const float* __restrict__ in, float* __restrict__ out, int hin, int win, int D4) {
@@ -235,18 +233,6 @@ __global__ void amt_out_kernel(const float* __restrict__ warps, int warps_cs, co
     }
 }
 
-// centred replicate pad of an [H,W,C>=3] frame into channels 0..2 of img [Hp,Wp,8] (InputPadder(dims, 16), :194-211); blockIdx.y = frame
-__global__ void amt_pad_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W, float* __restrict__ img, int Hp,
-                               int Wp, int top, int left) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)Hp * Wp) return;
-    const int X = (int)(idx % Wp), Y = (int)(idx / Wp);
-    const int sx = min(max(X - left, 0), W - 1), sy = min(max(Y - top, 0), H - 1);
-    const float* s = (blockIdx.y ? f1 : f0) + ((size_t)sy * W + sx) * C;
-    float* o = img + ((size_t)blockIdx.y * Hp * Wp + idx) * 8;
-    o[0] = s[0], o[1] = s[1], o[2] = s[2];
-}
-
 // mean_ over the three colour channels of both padded frames (:1206), deterministic: kMeanSlots fixed slots in double, summed in order
 constexpr int kMeanSlots = 256;
 __global__ __launch_bounds__(256) void amt_mean_partial_kernel(const float* __restrict__ img, long pixels, double* __restrict__ part) {
@@ -336,8 +322,6 @@ __global__ void amt_upsample_lrelu_kernel(const float* __restrict__ in, int in_c
     if (V == 4) *(float4*)o = *(const float4*)r;
     else o[0] = r[0];
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 }  // namespace vfi
@@ -470,11 +454,9 @@ struct Cfg {
 // (amt.py's MAX_PADDED_PIXELS_G is derived from the same 88; tests/test_gpu_amt_g.py asserts that the two limits agree.)
 // AMT-G's widest buffer is decoder1's ResBlock at half resolution: r8(3 * 84) + 8 + r8(84) = 352 channels = 88 floats per padded pixel
 // (gru.0's input in update2_high, r8(188 + 4 + 84) = 280 channels, is 70).  AMT-S / AMT-L keep their 64.
-const Cfg kCfg[3] = {{{20, 32, 44, 56}, 20, 3, 84, 3, 76, 20, 64, 0, 68, 32, 3, {32, 64, 96}, {1, 2, 2}, 3, 64, 213, "S"},
-                     {{48, 64, 72, 128}, 48, 5, 128, 7, 128, 48, 256, 160, 124, 64, 3, {64, 72, 128}, {1, 2, 2}, 3, 64, 207, "L"},
-                     {{84, 96, 112, 128}, 84, 5, 128, 7, 192, 64, 256, 192, 188, 64, 4, {64, 112, 160, 160}, {1, 2, 2, 1}, 5, 88, 259, "G"}};
-
-inline int r8(int c) { return (c + 7) & ~7; }
+const Cfg kCfg[3] = {{{20, 32, 44, 56}, 20, 3, 84, 3, 76, 20, 64, 0, 68, 32, 3, {32, 64, 96}, {1, 2, 2}, 3, 64, 213, "AMT-S"},
+                     {{48, 64, 72, 128}, 48, 5, 128, 7, 128, 48, 256, 160, 124, 64, 3, {64, 72, 128}, {1, 2, 2}, 3, 64, 207, "AMT-L"},
+                     {{84, 96, 112, 128}, 84, 5, 128, 7, 192, 64, 256, 192, 188, 64, 4, {64, 112, 160, 160}, {1, 2, 2, 1}, 5, 88, 259, "AMT-G"}};
 
 struct Conv7 {      // a vfi_conv7x7 layer: packed weights, bias, PReLU slopes (nullable) on the device
     float *w = nullptr, *b = nullptr, *pr = nullptr;
@@ -500,7 +482,7 @@ struct Upd {
 
 }  // namespace
 
-struct vfi_amt : NetObject {
+struct vfi_amt : PaddedNet {
     int variant = 0;      // 0 AMT-S, 1 AMT-L, 2 AMT-G
     Stem fe_stem, py_stem;
     EncBlk blk[8];
@@ -510,26 +492,11 @@ struct vfi_amt : NetObject {
     Upd upd[5];           // update4, 3[_low], 2[_low]; AMT-G: update3_high, update2_high
     vfi_conv_t *cb0 = nullptr, *cb2 = nullptr;
     Conv7 cb7[2];
-    int Hp = 0, Wp = 0;
 };
 
 namespace {
 
-struct Run {      // one forward call: the scratch tensors by name and the launches' stream
-    vfi_amt* m;
-    hipStream_t st;
-    bool bad = false;
-    float* buf(const char* name, int n, int h, int w, int c) {
-        Ten* t = nullptr;
-        if (bad || m->ws.tmp(name, n, h, w, c, &t)) {
-            bad = true;
-            return nullptr;
-        }
-        return t->p;
-    }
-    int conv(const vfi_conv_t* L, const float* in, int ics, int h, int w, float* out, int ocs, int N, int act, const float* res = nullptr, int rcs = 0) {
-        return vfi_conv_forward_ex(L, in, ics, h, w, out, ocs, N, act, act == 1 ? 0.1f : 0.f, 0.f, 0.f, res, rcs, st);
-    }
+struct Run : NetRun<vfi_amt> {      // act 1 is LeakyReLU(0.1): amt_forward sets `leaky`
     // out = a (sub-sampled by step) [+ b]
     int add(const float* a, int a_cs, int a_w, int step, const float* b, int b_cs, float* out, int out_cs, int h, int w, int C, int reps = 1) {
         hipLaunchKernelGGL(amt_add_kernel, dim3(nblk((long)h * w, 256)), dim3(256), 0, st, a, a_cs, a_w, step, b, b_cs, out, out_cs, h, w, C, reps);
@@ -557,11 +524,6 @@ struct Run {      // one forward call: the scratch tensors by name and the launc
     }
 };
 
-#define AMT_DO(x)          \
-    do {                   \
-        if (x) return -1;  \
-    } while (0)
-
 // a decoder's convblock (:824-857): convrelu, ResBlock with side channels (:762-799), ConvTranspose2d.  The ResBlock's side-channel
 // layers read the last `skip` channels of x1 / x3 as a window and write behind the main channels (offset off); conv3 / conv5 were created
 // with a channel map over that layout, so no cat is ever made.
@@ -569,12 +531,12 @@ int run_decoder(Run& r, const Dec& d, int skip, const float* din, int din_cs, in
     const int c8 = r8(d.c), off = c8 + 8, xcs = off + r8(skip), so = d.c - skip;
     float *r0 = r.buf("dec_r0", 1, h, w, c8), *x1 = r.buf("dec_x1", 1, h, w, xcs), *x3 = r.buf("dec_x3", 1, h, w, xcs), *r5 = r.buf("dec_r5", 1, h, w, c8);
     if (r.bad) return -1;
-    AMT_DO(r.conv(d.c0, din, din_cs, h, w, r0, c8, 1, 3));
-    AMT_DO(r.conv(d.rb[0], r0, c8, h, w, x1, xcs, 1, 3));
-    AMT_DO(r.conv(d.rb[1], x1 + so, xcs, h, w, x1 + off, xcs, 1, 3));
-    AMT_DO(r.conv(d.rb[2], x1, xcs, h, w, x3, xcs, 1, 3));
-    AMT_DO(r.conv(d.rb[3], x3 + so, xcs, h, w, x3 + off, xcs, 1, 3));
-    AMT_DO(r.conv(d.rb[4], x3, xcs, h, w, r5, c8, 1, 3, r0, c8));
+    VFI_DO(r.conv(d.c0, din, din_cs, h, w, r0, c8, 1, 3));
+    VFI_DO(r.conv(d.rb[0], r0, c8, h, w, x1, xcs, 1, 3));
+    VFI_DO(r.conv(d.rb[1], x1 + so, xcs, h, w, x1 + off, xcs, 1, 3));
+    VFI_DO(r.conv(d.rb[2], x1, xcs, h, w, x3, xcs, 1, 3));
+    VFI_DO(r.conv(d.rb[3], x3 + so, xcs, h, w, x3 + off, xcs, 1, 3));
+    VFI_DO(r.conv(d.rb[4], x3, xcs, h, w, r5, c8, 1, 3, r0, c8));
     return r.conv(d.up, r5, c8, h, w, out, out_cs, 1, 0);
 }
 
@@ -583,16 +545,16 @@ int run_decoder(Run& r, const Dec& d, int skip, const float* din, int din_cs, in
 int update_tail(Run& r, const Cfg& g, const Upd& U, const float* flow, int flow_cs, int ch, int h, int w, float* inp, int inp_cs, float* cf, int cf_cs,
                 float* fa, float* h1, float* h2, float* h3, float* dn, float* df) {
     const int hcs = r8(g.hid), cdo = g.cd2 ? g.cd2 : g.cd;
-    AMT_DO(vfi_conv7x7(flow, flow_cs, U.f1.w, U.f1.b, nullptr, 0.1f, 1, 4, 2 * g.fd, fa, 2 * g.fd, 1, h, w, r.st));
-    AMT_DO(r.conv(U.f2, fa, 2 * g.fd, h, w, cf + cdo, cf_cs, 1, 1));
+    VFI_DO(vfi_conv7x7(flow, flow_cs, U.f1.w, U.f1.b, nullptr, 0.1f, 1, 4, 2 * g.fd, fa, 2 * g.fd, 1, h, w, r.st));
+    VFI_DO(r.conv(U.f2, fa, 2 * g.fd, h, w, cf + cdo, cf_cs, 1, 1));
     // (writes channels 0 .. fc of inp, directly in front of the flow window: the layer objects store exactly Cout channels, never Cout
     // rounded up, see the `co < a.Cout` guards of conv_mfma*.hip / conv_wino.hip)
-    AMT_DO(r.conv(U.cv, cf, cf_cs, h, w, inp, inp_cs, 1, 1));
-    AMT_DO(r.conv(U.g0, inp, inp_cs, h, w, h1, hcs, 1, 1));
-    AMT_DO(r.conv(U.g2, h1, hcs, h, w, h2, hcs, 1, 0));
-    AMT_DO(r.conv(U.fh0, h2, hcs, h, w, h1, hcs, 1, 1));
-    AMT_DO(r.conv(U.fh2, h1, hcs, h, w, dn, r8(ch), 1, 0));
-    AMT_DO(r.conv(U.wh0, h2, hcs, h, w, h3, hcs, 1, 1));
+    VFI_DO(r.conv(U.cv, cf, cf_cs, h, w, inp, inp_cs, 1, 1));
+    VFI_DO(r.conv(U.g0, inp, inp_cs, h, w, h1, hcs, 1, 1));
+    VFI_DO(r.conv(U.g2, h1, hcs, h, w, h2, hcs, 1, 0));
+    VFI_DO(r.conv(U.fh0, h2, hcs, h, w, h1, hcs, 1, 1));
+    VFI_DO(r.conv(U.fh2, h1, hcs, h, w, dn, r8(ch), 1, 0));
+    VFI_DO(r.conv(U.wh0, h2, hcs, h, w, h3, hcs, 1, 1));
     return r.conv(U.wh2, h3, hcs, h, w, df, 8, 1, 0);
 }
 
@@ -602,13 +564,13 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
     const int Hp = m->Hp, Wp = m->Wp, top = (Hp - H) / 2, left = (Wp - W) / 2;
     const long P = (long)Hp * Wp;
     const int h8 = Hp / 8, w8 = Wp / 8, D = g.D;
-    Run r{m, st};
+    Run r{{m, st, 0.1f}};
     // ---- once per pair ----
     float* img = r.buf("img", 2, Hp, Wp, 8);
     float* mean = r.buf("mean", 1, 1, 1, 4 + 2 * kMeanSlots);
     if (r.bad) return -1;
     double* part = (double*)(mean + 4);
-    hipLaunchKernelGGL(amt_pad_kernel, dim3(nblk(P, 256), 2), dim3(256), 0, st, f0, f1, C, H, W, img, Hp, Wp, top, left);
+    VFI_DO(pad_frame_pair(f0, f1, C, H, W, img, Hp, Wp, top, left, true, st));      // InputPadder(dims, 16) (:194-211): centred, replicate
     hipLaunchKernelGGL(amt_mean_partial_kernel, dim3(kMeanSlots), dim3(256), 0, st, (const float*)img, 2 * P, part);
     hipLaunchKernelGGL(amt_mean_final_kernel, dim3(1), dim3(1), 0, st, (const double*)part, 2 * P, mean);
     hipLaunchKernelGGL(amt_center_kernel, dim3(nblk(2 * P, 256)), dim3(256), 0, st, img, 2 * P, (const float*)mean);
@@ -619,8 +581,8 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
         int h = Hp / 2, w = Wp / 2;
         float* e1 = r.buf("fe_e1", 2, h, w, 64);
         if (r.bad) return -1;
-        AMT_DO(vfi_conv7x7s2_prelu(img, 8, m->fe_stem.w, m->fe_stem.b, m->fe_stem.slope, 64, e1, 64, 2, Hp, Wp, st));
-        AMT_DO(r.norm(e1, 64, g.e1, (long)h * w, 1, nullptr, 0, 0, e1, 64));
+        VFI_DO(vfi_conv7x7s2_prelu(img, 8, m->fe_stem.w, m->fe_stem.b, m->fe_stem.slope, 64, e1, 64, 2, Hp, Wp, st));
+        VFI_DO(r.norm(e1, 64, g.e1, (long)h * w, 1, nullptr, 0, 0, e1, 64));
         const float* x = e1;
         int xcs = 64;
         for (int k = 0; k < 2 * g.n_enc; ++k) {
@@ -631,34 +593,34 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
                 const int c4 = c / 4;
                 float *y1 = r.buf("fe_y1", 2, h, w, c4), *y2 = r.buf("fe_y2", 2, ho, wo, c4);
                 if (r.bad) return -1;
-                AMT_DO(r.conv(B.c1, x, xcs, h, w, y1, c4, 2, 0));
-                AMT_DO(r.norm(y1, c4, c4, (long)h * w, 1, nullptr, 0, 0, y1, c4));
-                AMT_DO(r.conv(B.c2, y1, c4, h, w, y2, c4, 2, 0));
-                AMT_DO(r.norm(y2, c4, c4, (long)ho * wo, 1, nullptr, 0, 0, y2, c4));
-                AMT_DO(r.conv(B.c3, y2, c4, ho, wo, y3, c, 2, 0));
+                VFI_DO(r.conv(B.c1, x, xcs, h, w, y1, c4, 2, 0));
+                VFI_DO(r.norm(y1, c4, c4, (long)h * w, 1, nullptr, 0, 0, y1, c4));
+                VFI_DO(r.conv(B.c2, y1, c4, h, w, y2, c4, 2, 0));
+                VFI_DO(r.norm(y2, c4, c4, (long)ho * wo, 1, nullptr, 0, 0, y2, c4));
+                VFI_DO(r.conv(B.c3, y2, c4, ho, wo, y3, c, 2, 0));
             } else {
                 float* y1 = r.buf("fe_y1", 2, ho, wo, c);
                 if (r.bad) return -1;
-                AMT_DO(r.conv(B.c1, x, xcs, h, w, y1, c, 2, 0));
-                AMT_DO(r.norm(y1, c, c, (long)ho * wo, 1, nullptr, 0, 0, y1, c));
-                AMT_DO(r.conv(B.c2, y1, c, ho, wo, y3, c, 2, 0));
+                VFI_DO(r.conv(B.c1, x, xcs, h, w, y1, c, 2, 0));
+                VFI_DO(r.norm(y1, c, c, (long)ho * wo, 1, nullptr, 0, 0, y1, c));
+                VFI_DO(r.conv(B.c2, y1, c, ho, wo, y3, c, 2, 0));
             }
             const float* res = x;
             int res_cs = xcs;
             if (B.ds) {      // Conv2d(cin, c, 1, stride 2) + norm: the two frames sub-sampled as one image of 2 ho rows
                 float *sub = r.buf("fe_sub", 2, ho, wo, B.cin), *dsn = r.buf("fe_ds", 2, ho, wo, c);
                 if (r.bad) return -1;
-                AMT_DO(r.add(x, xcs, w, 2, nullptr, 0, sub, B.cin, 2 * ho, wo, B.cin));
-                AMT_DO(r.conv(B.ds, sub, B.cin, ho, wo, dsn, c, 2, 0));
-                AMT_DO(r.norm(dsn, c, c, (long)ho * wo, 0, nullptr, 0, 0, dsn, c));
+                VFI_DO(r.add(x, xcs, w, 2, nullptr, 0, sub, B.cin, 2 * ho, wo, B.cin));
+                VFI_DO(r.conv(B.ds, sub, B.cin, ho, wo, dsn, c, 2, 0));
+                VFI_DO(r.norm(dsn, c, c, (long)ho * wo, 0, nullptr, 0, 0, dsn, c));
                 res = dsn, res_cs = c;
             }
             float* xn = r.buf(k % 2 ? "fe_xb" : "fe_xa", 2, ho, wo, c);
             if (r.bad) return -1;
-            AMT_DO(r.norm(y3, c, c, (long)ho * wo, 1, res, res_cs, 1, xn, c));
+            VFI_DO(r.norm(y3, c, c, (long)ho * wo, 1, res, res_cs, 1, xn, c));
             x = xn, xcs = c, h = ho, w = wo;
         }
-        AMT_DO(r.conv(m->fe_out, x, xcs, h8, w8, fmap, D, 2, 0));
+        VFI_DO(r.conv(m->fe_out, x, xcs, h8, w8, fmap, D, 2, 0));
     }
     const float *fm0 = fmap, *fm1 = fmap + (size_t)h8 * w8 * D;
     size_t npool = 0;
@@ -666,8 +628,8 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
     float* pool = r.buf("pool", 2, 1, 1, (int)(npool * D));
     if (r.bad) return -1;
     float *pool0 = pool, *pool1 = pool + npool * D;
-    AMT_DO(vfi_amt_pool_features(fm0, h8, w8, D, pool0, st));
-    AMT_DO(vfi_amt_pool_features(fm1, h8, w8, D, pool1, st));
+    VFI_DO(vfi_amt_pool_features(fm0, h8, w8, D, pool0, st));
+    VFI_DO(vfi_amt_pool_features(fm1, h8, w8, D, pool1, st));
     // pyramid encoder over both frames
     float* pyr[4];
     int pcs[4];
@@ -679,28 +641,28 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             float* a = r.buf("py_a", 2, h / 2, w / 2, pcs[i]);
             pyr[i] = r.buf("py_p", 2, h / 2, w / 2, pcs[i]);
             if (r.bad) return -1;
-            if (basic && i == 0) AMT_DO(vfi_conv7x7s2_prelu(img, 8, m->py_stem.w, m->py_stem.b, m->py_stem.slope, m->py_stem.cout, a, pcs[0], 2, Hp, Wp, st));
-            else AMT_DO(r.conv(m->py0[i], x, xcs, h, w, a, pcs[i], 2, 3));
+            if (basic && i == 0) VFI_DO(vfi_conv7x7s2_prelu(img, 8, m->py_stem.w, m->py_stem.b, m->py_stem.slope, m->py_stem.cout, a, pcs[0], 2, Hp, Wp, st));
+            else VFI_DO(r.conv(m->py0[i], x, xcs, h, w, a, pcs[i], 2, 3));
             h /= 2, w /= 2;
-            AMT_DO(r.conv(m->py1[i], a, pcs[i], h, w, pyr[i], pcs[i], 2, 3));
+            VFI_DO(r.conv(m->py1[i], a, pcs[i], h, w, pyr[i], pcs[i], 2, 3));
             x = pyr[i], xcs = pcs[i];
         }
     }
     const int h16 = Hp / 16, w16 = Wp / 16, c3 = g.ch[3], din4_cs = r8(2 * c3 + 1);
     float* din4 = r.buf("din4", 1, h16, w16, din4_cs);
     if (r.bad) return -1;
-    AMT_DO(r.copy(pyr[3], pcs[3], din4, din4_cs, h16, w16, c3));
-    AMT_DO(r.copy(pyr[3] + (size_t)h16 * w16 * pcs[3], pcs[3], din4 + c3, din4_cs, h16, w16, c3));
+    VFI_DO(r.copy(pyr[3], pcs[3], din4, din4_cs, h16, w16, c3));
+    VFI_DO(r.copy(pyr[3] + (size_t)h16 * w16 * pcs[3], pcs[3], din4 + c3, din4_cs, h16, w16, c3));
     // ---- per timestep ----
     const int hcs = r8(g.hid), cdo = g.cd2 ? g.cd2 : g.cd, cf_cs = r8(cdo + g.fd);
     for (int ti = 0; ti < n_t; ++ti) {
         const float embt = ts[ti];
         const float s1 = 1.0f / embt, s0 = 1.0f / (1.0f - embt);
-        AMT_DO(vfi_fill_items(din4 + 2 * c3, din4_cs, 1, 1, (int64_t)h16 * w16, &embt, st));
+        VFI_DO(vfi_fill_items(din4 + 2 * c3, din4_cs, 1, 1, (int64_t)h16 * w16, &embt, st));
         int ocs = r8(g.ch[2] + 4);
         float* o = r.buf("dec_out", 1, h8, w8, ocs);
         if (r.bad) return -1;
-        AMT_DO(run_decoder(r, m->dec[0], g.skip, din4, din4_cs, h16, w16, o, ocs));
+        VFI_DO(run_decoder(r, m->dec[0], g.skip, din4, din4_cs, h16, w16, o, ocs));
         float *fl = o, *ft = o + 4;      // (flow0, flow1) and the hidden feature of the current level
         int fcs = ocs;
         for (int s = 0; s < 3; ++s) {
@@ -712,7 +674,7 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             if (down != 1) {
                 float* t = r.buf("flow_d", 1, h8, w8, 4);
                 if (r.bad) return -1;
-                AMT_DO(r.resize(fl, fcs, h, w, t, 4, h8, w8, 4, (float)down, 1.0f / (float)down));
+                VFI_DO(r.resize(fl, fcs, h, w, t, 4, h8, w8, 4, (float)down, 1.0f / (float)down));
                 fd = t, fd_cs = 4;
             }
             float* corr = r.buf("corr", 1, h8, w8, 2 * kLevels * kWin * kWin);
@@ -721,28 +683,28 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             float *h1 = r.buf("upd_h1", 1, h8, w8, hcs), *h2 = r.buf("upd_h2", 1, h8, w8, hcs), *h3 = r.buf("upd_h3", 1, h8, w8, hcs);
             float *dn = r.buf("upd_dn", 1, h8, w8, r8(ch)), *df = r.buf("upd_df", 1, h8, w8, 8);
             if (r.bad) return -1;
-            AMT_DO(vfi_amt_corr_lookup(fm0, fm1, pool1, fd + 2, fd_cs, s1, h8, w8, D, corr, 392, st));
-            AMT_DO(vfi_amt_corr_lookup(fm1, fm0, pool0, fd, fd_cs, s0, h8, w8, D, corr + 196, 392, st));
+            VFI_DO(vfi_amt_corr_lookup(fm0, fm1, pool1, fd + 2, fd_cs, s1, h8, w8, D, corr, 392, st));
+            VFI_DO(vfi_amt_corr_lookup(fm1, fm0, pool0, fd, fd_cs, s0, h8, w8, D, corr + 196, 392, st));
             // the update block (:969-1073) at 1/8 resolution
-            if (down != 1) AMT_DO(r.resize(ft, fcs, h, w, inp + g.fc + 4, inp_cs, h8, w8, ch, (float)down, 1.0f));
-            else AMT_DO(r.copy(ft, fcs, inp + g.fc + 4, inp_cs, h8, w8, ch));
-            AMT_DO(r.copy(fd, fd_cs, inp + g.fc, inp_cs, h8, w8, 4));
+            if (down != 1) VFI_DO(r.resize(ft, fcs, h, w, inp + g.fc + 4, inp_cs, h8, w8, ch, (float)down, 1.0f));
+            else VFI_DO(r.copy(ft, fcs, inp + g.fc + 4, inp_cs, h8, w8, ch));
+            VFI_DO(r.copy(fd, fd_cs, inp + g.fc, inp_cs, h8, w8, 4));
             if (basic) {
                 float* c1 = r.buf("upd_c1", 1, h8, w8, g.cd);
                 if (r.bad) return -1;
-                AMT_DO(r.conv(U.c1, corr, 392, h8, w8, c1, g.cd, 1, 1));
-                AMT_DO(r.conv(U.c2, c1, g.cd, h8, w8, cf, cf_cs, 1, 1));
+                VFI_DO(r.conv(U.c1, corr, 392, h8, w8, c1, g.cd, 1, 1));
+                VFI_DO(r.conv(U.c2, c1, g.cd, h8, w8, cf, cf_cs, 1, 1));
             } else {
-                AMT_DO(r.conv(U.c1, corr, 392, h8, w8, cf, cf_cs, 1, 1));
+                VFI_DO(r.conv(U.c1, corr, 392, h8, w8, cf, cf_cs, 1, 1));
             }
-            AMT_DO(update_tail(r, g, U, fd, fd_cs, ch, h8, w8, inp, inp_cs, cf, cf_cs, fa, h1, h2, h3, dn, df));
+            VFI_DO(update_tail(r, g, U, fd, fd_cs, ch, h8, w8, inp, inp_cs, cf, cf_cs, fa, h1, h2, h3, dn, df));
             const float *dnu = dn, *dfu = df;
             int dnu_cs = r8(ch), dfu_cs = 8;
             if (down != 1) {
                 float *a = r.buf("upd_dnu", 1, h, w, r8(ch)), *b = r.buf("upd_dfu", 1, h, w, 4);
                 if (r.bad) return -1;
-                AMT_DO(r.resize(dn, r8(ch), h8, w8, a, r8(ch), h, w, ch, 1.0f / (float)down, 1.0f));
-                AMT_DO(r.resize(df, 8, h8, w8, b, 4, h, w, 4, 1.0f / (float)down, (float)down));
+                VFI_DO(r.resize(dn, r8(ch), h8, w8, a, r8(ch), h, w, ch, 1.0f / (float)down, 1.0f));
+                VFI_DO(r.resize(df, 8, h8, w8, b, 4, h, w, 4, 1.0f / (float)down, (float)down));
                 dnu = a, dfu = b, dfu_cs = 4;
             }
             // the next decoder's input: ft + dft | warp(f0_lvl, flow0) | warp(f1_lvl, flow1) | flow0 + dflow0 | flow1 + dflow1
@@ -752,8 +714,8 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
             ocs = r8(dc.cout);
             float *on = r.buf("dec_out", 1, 2 * h, 2 * w, ocs), *up = r.buf("flow_up", 1, 2 * h, 2 * w, 4);
             if (r.bad) return -1;
-            AMT_DO(r.add(ft, fcs, w, 1, dnu, dnu_cs, din, din_cs, h, w, ch));
-            AMT_DO(r.add(fl, fcs, w, 1, dfu, dfu_cs, din + 3 * ch, din_cs, h, w, 4));
+            VFI_DO(r.add(ft, fcs, w, 1, dnu, dnu_cs, din, din_cs, h, w, ch));
+            VFI_DO(r.add(fl, fcs, w, 1, dfu, dfu_cs, din + 3 * ch, din_cs, h, w, 4));
             if (G && down != 1) {
                 // update3_high / update2_high (:1537-1543, :1558-1564) at this level's own resolution, on the sums just written (ft + dft,
                 // the four flow channels) and on the SAME lookup output.  The reference resizes the 392 lookup channels and then applies
@@ -766,24 +728,24 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
                 float *h1h = r.buf("upd_h1", 1, h, w, hcs), *h2h = r.buf("upd_h2", 1, h, w, hcs), *h3h = r.buf("upd_h3", 1, h, w, hcs);
                 float *dnh = r.buf("upd_dn", 1, h, w, r8(ch)), *dfh = r.buf("upd_df", 1, h, w, 8);
                 if (r.bad) return -1;
-                AMT_DO(r.conv(UH.c1, corr, 392, h8, w8, c1lo, g.cd, 1, 0));
-                AMT_DO(vfi_amt_upsample_lrelu(c1lo, g.cd, c1, g.cd, 1, h8, w8, g.cd, down, 0.1f, st));
-                AMT_DO(r.conv(UH.c2, c1, g.cd, h, w, cfh, cf_cs, 1, 1));
-                AMT_DO(r.copy(din, din_cs, inph + g.fc + 4, inp_cs, h, w, ch));
-                AMT_DO(r.copy(din + 3 * ch, din_cs, inph + g.fc, inp_cs, h, w, 4));
-                AMT_DO(update_tail(r, g, UH, din + 3 * ch, din_cs, ch, h, w, inph, inp_cs, cfh, cf_cs, fah, h1h, h2h, h3h, dnh, dfh));
-                AMT_DO(r.add(din, din_cs, w, 1, dnh, r8(ch), din, din_cs, h, w, ch));
-                AMT_DO(r.add(din + 3 * ch, din_cs, w, 1, dfh, 8, din + 3 * ch, din_cs, h, w, 4));
+                VFI_DO(r.conv(UH.c1, corr, 392, h8, w8, c1lo, g.cd, 1, 0));
+                VFI_DO(vfi_amt_upsample_lrelu(c1lo, g.cd, c1, g.cd, 1, h8, w8, g.cd, down, 0.1f, st));
+                VFI_DO(r.conv(UH.c2, c1, g.cd, h, w, cfh, cf_cs, 1, 1));
+                VFI_DO(r.copy(din, din_cs, inph + g.fc + 4, inp_cs, h, w, ch));
+                VFI_DO(r.copy(din + 3 * ch, din_cs, inph + g.fc, inp_cs, h, w, 4));
+                VFI_DO(update_tail(r, g, UH, din + 3 * ch, din_cs, ch, h, w, inph, inp_cs, cfh, cf_cs, fah, h1h, h2h, h3h, dnh, dfh));
+                VFI_DO(r.add(din, din_cs, w, 1, dnh, r8(ch), din, din_cs, h, w, ch));
+                VFI_DO(r.add(din + 3 * ch, din_cs, w, 1, dfh, 8, din + 3 * ch, din_cs, h, w, 4));
             }
-            AMT_DO(r.warp(pyr[lvl], pcs[lvl], din + 3 * ch, din_cs, din + ch, din_cs, h, w, ch));
-            AMT_DO(r.warp(pyr[lvl] + (size_t)h * w * pcs[lvl], pcs[lvl], din + 3 * ch + 2, din_cs, din + 2 * ch, din_cs, h, w, ch));
-            AMT_DO(run_decoder(r, dc, g.skip, din, din_cs, h, w, on, ocs));
-            AMT_DO(r.resize(din + 3 * ch, din_cs, h, w, up, 4, 2 * h, 2 * w, 4, 0.5f, 2.0f));
+            VFI_DO(r.warp(pyr[lvl], pcs[lvl], din + 3 * ch, din_cs, din + ch, din_cs, h, w, ch));
+            VFI_DO(r.warp(pyr[lvl] + (size_t)h * w * pcs[lvl], pcs[lvl], din + 3 * ch + 2, din_cs, din + 2 * ch, din_cs, h, w, ch));
+            VFI_DO(run_decoder(r, dc, g.skip, din, din_cs, h, w, on, ocs));
+            VFI_DO(r.resize(din + 3 * ch, din_cs, h, w, up, 4, 2 * h, 2 * w, 4, 0.5f, 2.0f));
             if (s < 2) {
-                AMT_DO(r.add(on, ocs, 2 * w, 1, up, 4, on, ocs, 2 * h, 2 * w, 4));
+                VFI_DO(r.add(on, ocs, 2 * w, 1, up, 4, on, ocs, 2 * h, 2 * w, 4));
             } else {      // the num_flows flows of each direction take the up-sampled flow of theirs (:1262-1263)
-                AMT_DO(r.add(on, ocs, 2 * w, 1, up, 4, on, ocs, 2 * h, 2 * w, 2, g.nf));
-                AMT_DO(r.add(on + 2 * g.nf, ocs, 2 * w, 1, up + 2, 4, on + 2 * g.nf, ocs, 2 * h, 2 * w, 2, g.nf));
+                VFI_DO(r.add(on, ocs, 2 * w, 1, up, 4, on, ocs, 2 * h, 2 * w, 2, g.nf));
+                VFI_DO(r.add(on + 2 * g.nf, ocs, 2 * w, 1, up + 2, 4, on + 2 * g.nf, ocs, 2 * h, 2 * w, 2, g.nf));
             }
             fl = on, ft = on + 4, fcs = ocs;
         }
@@ -791,15 +753,15 @@ int amt_forward(vfi_amt* m, const float* f0, const float* f1, int C, int H, int 
         const int wr_cs = r8(3 * g.nf), mid_cs = r8(6 * g.nf);
         float *wr = r.buf("comb_in", 1, Hp, Wp, wr_cs), *mid = r.buf("comb_mid", 1, Hp, Wp, mid_cs), *cb = r.buf("comb_out", 1, Hp, Wp, 8);
         if (r.bad) return -1;
-        AMT_DO(vfi_amt_combine_warps(img, img + (size_t)P * 8, 8, fl, fcs, mean, g.nf, wr, wr_cs, Hp, Wp, st));
+        VFI_DO(vfi_amt_combine_warps(img, img + (size_t)P * 8, 8, fl, fcs, mean, g.nf, wr, wr_cs, Hp, Wp, st));
         if (basic) {
-            AMT_DO(vfi_conv7x7(wr, wr_cs, m->cb7[0].w, m->cb7[0].b, m->cb7[0].pr, 0.f, 3, 3 * g.nf, 6 * g.nf, mid, mid_cs, 1, Hp, Wp, st));
-            AMT_DO(vfi_conv7x7(mid, mid_cs, m->cb7[1].w, m->cb7[1].b, nullptr, 0.f, 0, 6 * g.nf, 3, cb, 8, 1, Hp, Wp, st));
+            VFI_DO(vfi_conv7x7(wr, wr_cs, m->cb7[0].w, m->cb7[0].b, m->cb7[0].pr, 0.f, 3, 3 * g.nf, 6 * g.nf, mid, mid_cs, 1, Hp, Wp, st));
+            VFI_DO(vfi_conv7x7(mid, mid_cs, m->cb7[1].w, m->cb7[1].b, nullptr, 0.f, 0, 6 * g.nf, 3, cb, 8, 1, Hp, Wp, st));
         } else {
-            AMT_DO(r.conv(m->cb0, wr, wr_cs, Hp, Wp, mid, mid_cs, 1, 3));
-            AMT_DO(r.conv(m->cb2, mid, mid_cs, Hp, Wp, cb, 8, 1, 0));
+            VFI_DO(r.conv(m->cb0, wr, wr_cs, Hp, Wp, mid, mid_cs, 1, 3));
+            VFI_DO(r.conv(m->cb2, mid, mid_cs, Hp, Wp, cb, 8, 1, 0));
         }
-        AMT_DO(vfi_amt_combine_out(wr, wr_cs, cb, 8, g.nf, out + (size_t)ti * H * W * 3, Hp, Wp, top, left, H, W, st));
+        VFI_DO(vfi_amt_combine_out(wr, wr_cs, cb, 8, g.nf, out + (size_t)ti * H * W * 3, Hp, Wp, top, left, H, W, st));
     }
     return 0;
 }
@@ -814,8 +776,8 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
     const bool known = variant >= 0 && variant <= 2;
     const int want = known ? kCfg[variant].n_tensors : 0;
     if (!tensors || !numels || !known || n_tensors != want) {
-        set_error("vfi_amt_create: expected the %d state_dict tensors of AMT-%s in amt_spec.amt_shapes() order (variant 0 = S, 1 = L, 2 = G), got %d "
-                  "(variant %d)", want, known ? kCfg[variant].name : "?", n_tensors, variant);
+        set_error("vfi_amt_create: expected the %d state_dict tensors of %s in amt_spec.amt_shapes() order (variant 0 = S, 1 = L, 2 = G), got %d "
+                  "(variant %d)", want, known ? kCfg[variant].name : "AMT-?", n_tensors, variant);
         return nullptr;
     }
     vfi_amt* m = new vfi_amt();
@@ -824,12 +786,8 @@ vfi_amt_t* vfi_amt_create(const float* const* tensors, const int64_t* numels, in
     const bool basic = variant >= 1, G = variant == 2;
     TensorCursor cur(tensors, numels, n_tensors, "vfi_amt_create");
     // Conv2d (kind 0) / ConvTranspose2d (kind 1) with bias, then the PReLU slopes where the layer has them
-    auto layer = [&](int kind, int cout, int cin, int k, int stride, bool prelu, const int* map = nullptr, int cin_phys = 0) -> vfi_conv_t* {
-        const float* w = cur.take((int64_t)cout * cin * k * k);
-        const float* b = cur.take(cout);
-        const float* p = prelu ? cur.take(cout) : nullptr;
-        if (!cur.ok()) return nullptr;
-        return m->add_layer(vfi_conv_create_ex(kind, w, b, cout, cin, k, stride, 0, map, cin_phys ? cin_phys : r8(cin), p));
+    auto layer = [&](int kind, int cout, int cin, int k, int stride, bool prelu, const int* map = nullptr, int cin_phys = 0) {
+        return m->read_layer(cur, kind, cout, cin, k, stride, true, prelu, map, cin_phys);
     };
     std::vector<float> tmp;
     // Conv2d(3, cout, 7, 2, 3) [+ PReLU] for vfi_conv7x7s2_prelu: [7][7][3][P], P = 64 with the missing output channels zero, or AMT-G's 84
@@ -965,14 +923,9 @@ int vfi_amt_forward(vfi_amt_t* m, const float* frame0_dev, const float* frame1_d
     VFI_REQUIRE(Hp >= 128 && Wp >= 128,
                 "vfi_amt_forward: a %dx%d frame (padded %dx%d): AMT needs padded sides of at least 128 pixels (below, the coarsest correlation level is "
                 "one pixel wide and the reference is all-NaN)", H, W, Hp, Wp);
-    const int pxf = kCfg[m->variant].px_floats;      // the variant's widest activation, floats per padded pixel
-    VFI_REQUIRE((long)Hp * Wp * pxf * 4 < 0x7fffffffL,
-                "vfi_amt_forward: a %dx%d frame (padded %dx%d) is over the size limit: Hp * Wp * %d bytes must stay below 2 GiB for the layers' index "
-                "arithmetic (1088x1920 fits)", H, W, Hp, Wp, pxf * 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp) && m->ws.release()) return -1;
-    m->Hp = Hp, m->Wp = Wp;
-    return amt_forward(m, frame0_dev, frame1_dev, C, H, W, ts_host, n_t, out_dev, st);
+    const Cfg& g = kCfg[m->variant];      // px_floats: the variant's widest activation, floats per padded pixel
+    if (const int rc = m->enter("vfi_amt_forward", g.name, H, W, Hp, Wp, g.px_floats)) return rc;
+    return amt_forward(m, frame0_dev, frame1_dev, C, H, W, ts_host, n_t, out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

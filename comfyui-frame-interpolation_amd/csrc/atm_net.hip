@@ -11,7 +11,7 @@
 //                       layer on the MFMA kernel (CrossScaleFeatureFusion.layers)
 //   atm_depth_to_space  ConvTranspose2d(k 2, s 2) = a 1x1 layer with 4 Cout outputs + this interleave
 //   atm_blend / atm_out the two synthesis steps
-//   atm_pad / atm_copy  InputPadder(64)'s centred replicate pad; channel-window copies with an optional per-channel PReLU
+//   atm_copy            channel-window copies with an optional per-channel PReLU (the pad is net_object.h's pad_frame_pair)
 //   atm_alignment_*     the ensemble's score ("On with Ensemble (slowest)", network_lite.py:540-554): flow up-sampling, both warps and the L1
 //                       mean in one pass over the full-resolution pair, summed in a fixed order in two launches (no atomics)
 //   atm_select_flow     the ensemble's choice and the winner's resize to the 1/16 map, on the device
@@ -31,10 +31,6 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kHeads = 8;
-
-inline int nblk(long n, int per) { return (int)((n + per - 1) / per); }
-inline int r8(int c) { return (c + 7) & ~7; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // One workgroup = one window of one frame and one head; four waves, each owning 16-query tiles.  Tokens are addressed in the un-padded maps:
 // slot (ty, tx) of window (wy, wx) sits at (r, c) = (wy WIN + ty, wx WIN + tx) of the rolled, padded layout, which is position ((r + shift) %
@@ -271,18 +267,6 @@ __global__ void atm_out_kernel(const float* __restrict__ it, int it_cs, const fl
         const float s = 1.0f / (1.0f + expf(-res[p * res_cs + c]));
         out[(size_t)idx * 3 + c] = fminf(fmaxf(it[p * it_cs + c] + (2.0f * s - 1.0f), 0.f), 1.f);
     }
-}
-
-// centred replicate pad of an [H,W,C>=3] frame into channels 0..2 of img [Hp,Wp,8] (InputPadder(dims, 64), atm/__init__.py:11-23); blockIdx.y = frame
-__global__ void atm_pad_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W, float* __restrict__ img, int Hp,
-                               int Wp, int top, int left) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)Hp * Wp) return;
-    const int X = (int)(idx % Wp), Y = (int)(idx / Wp);
-    const int sx = min(max(X - left, 0), W - 1), sy = min(max(Y - top, 0), H - 1);
-    const float* s = (blockIdx.y ? f1 : f0) + ((size_t)sy * W + sx) * C;
-    float* o = img + ((size_t)blockIdx.y * Hp * Wp + idx) * 8;
-    o[0] = s[0], o[1] = s[1], o[2] = s[2];
 }
 
 // out[p, c] = prelu(in[p, c]) over a channel window (slopes null: a copy)
@@ -571,7 +555,7 @@ struct Up {           // a level of upsample_pyramid
 
 }  // namespace
 
-struct vfi_atm : NetObject {
+struct vfi_atm : PaddedNet {
     vfi_conv_t* fe[4][2] = {};
     vfi_conv_t* last[2] = {};
     Fusion lf, gf;
@@ -580,7 +564,7 @@ struct vfi_atm : NetObject {
     Up up[3];
     vfi_conv_t *proj = nullptr, *down1 = nullptr, *down2[2] = {}, *down3[3] = {}, *up1d = nullptr, *up1c = nullptr, *up2d = nullptr, *up2c = nullptr,
                *up3d = nullptr, *rh[2] = {};
-    int Hp = 0, Wp = 0, variant = 0;
+    int variant = 0;
     // the ensemble's device record: [0..2] the three losses and [3] the chosen level as vfi_atm_select_flow wrote them, [4..6] the losses as the
     // scoring kernels wrote them; ens_ran: an ensemble forward has been enqueued on ens_stream
     float* ens_rec = nullptr;
@@ -590,26 +574,7 @@ struct vfi_atm : NetObject {
 
 namespace {
 
-#define ATM_DO(x)          \
-    do {                   \
-        if (x) return -1;  \
-    } while (0)
-
-struct Run {
-    vfi_atm* m;
-    hipStream_t st;
-    bool bad = false;
-    float* buf(const char* name, int n, int h, int w, int c) {
-        Ten* t = nullptr;
-        if (bad || m->ws.tmp(name, n, h, w, c, &t)) {
-            bad = true;
-            return nullptr;
-        }
-        return t->p;
-    }
-    int conv(const vfi_conv_t* L, const float* in, int ics, int h, int w, float* out, int ocs, int N, int act, const float* res = nullptr, int rcs = 0) {
-        return vfi_conv_forward_ex(L, in, ics, h, w, out, ocs, N, act, 0.f, 0.f, 0.f, res, rcs, st);
-    }
+struct Run : NetRun<vfi_atm> {
     int copy(const float* in, int ics, float* out, int ocs, long px, int C, const float* slopes = nullptr) {
         hipLaunchKernelGGL(atm_copy_kernel, dim3(nblk(px * C, 256)), dim3(256), 0, st, in, ics, slopes, out, ocs, px, C);
         VFI_CHECK_HIP(hipGetLastError());
@@ -619,7 +584,7 @@ struct Run {
     int deconv(const vfi_conv_t* L, int c, const float* in, int ics, int h, int w, float* out, int ocs) {
         float* t = buf("deconv_taps", 1, h, w, r8(4 * c));
         if (bad) return -1;
-        ATM_DO(conv(L, in, ics, h, w, t, r8(4 * c), 1, 3));
+        VFI_DO(conv(L, in, ics, h, w, t, r8(4 * c), 1, 3));
         return vfi_atm_depth_to_space2(t, r8(4 * c), out, ocs, 1, h, w, c, st);
     }
 };
@@ -630,13 +595,13 @@ int run_fusion(Run& r, const Fusion& F, const float* fine, int fine_cs, int c0, 
                float* tok) {
     float *t1 = r.buf("fus_taps1", 2, h, w, 9 * c1), *t0 = r.buf("fus_taps0", 2, h, w, 9 * c0), *pr = r.buf("fus_proj", 2, h, w, C);
     if (r.bad) return -1;
-    ATM_DO(vfi_atm_gather_taps(mid, mid_cs, t1, 9 * c1, 2, 2 * h, 2 * w, c1, 2, 1, r.st));
-    ATM_DO(r.conv(F.l[0], t1, 9 * c1, h, w, cat, C, 2, 0));
+    VFI_DO(vfi_atm_gather_taps(mid, mid_cs, t1, 9 * c1, 2, 2 * h, 2 * w, c1, 2, 1, r.st));
+    VFI_DO(r.conv(F.l[0], t1, 9 * c1, h, w, cat, C, 2, 0));
     for (int d = 1; d <= 2; ++d) {
-        ATM_DO(vfi_atm_gather_taps(fine, fine_cs, t0, 9 * c0, 2, 4 * h, 4 * w, c0, 4, d, r.st));
-        ATM_DO(r.conv(F.l[d], t0, 9 * c0, h, w, cat + c1 + (d - 1) * c0, C, 2, 0));
+        VFI_DO(vfi_atm_gather_taps(fine, fine_cs, t0, 9 * c0, 2, 4 * h, 4 * w, c0, 4, d, r.st));
+        VFI_DO(r.conv(F.l[d], t0, 9 * c0, h, w, cat + c1 + (d - 1) * c0, C, 2, 0));
     }
-    ATM_DO(r.conv(F.proj, cat, C, h, w, pr, C, 2, 0));
+    VFI_DO(r.conv(F.proj, cat, C, h, w, pr, C, 2, 0));
     return vfi_layernorm(pr, C, C, (int64_t)2 * h * w, F.nw, F.nb, tok, C, r.st);
 }
 
@@ -651,20 +616,20 @@ int run_block(Run& r, const Block& B, const float* tok, float* out, int h, int w
     const int M = kCfg[r.m->variant].mlp_ratio * C;      // Mlp's hidden width
     float *h1 = r.buf("blk_h1", 2, h, w, M), *h2 = r.buf("blk_h2", 2, h, w, M);
     if (r.bad) return -1;
-    ATM_DO(vfi_layernorm(tok, C, C, (int64_t)rows * w, B.n1w, B.n1b, xn, C, r.st));
+    VFI_DO(vfi_layernorm(tok, C, C, (int64_t)rows * w, B.n1w, B.n1b, xn, C, r.st));
     if (cross) {
-        ATM_DO(r.conv(B.q, xn, C, rows, w, qkv, 3 * C, 1, 0));
-        ATM_DO(r.conv(B.kv, xn, C, rows, w, qkv + C, 3 * C, 1, 0));
+        VFI_DO(r.conv(B.q, xn, C, rows, w, qkv, 3 * C, 1, 0));
+        VFI_DO(r.conv(B.kv, xn, C, rows, w, qkv + C, 3 * C, 1, 0));
     } else {
-        ATM_DO(r.conv(B.qkv, xn, C, rows, w, qkv, 3 * C, 1, 0));
+        VFI_DO(r.conv(B.qkv, xn, C, rows, w, qkv, 3 * C, 1, 0));
     }
-    ATM_DO(vfi_atm_window_attention_labels(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, ntok, ao, C, cross ? of : nullptr, h, w, lab_h ? lab_h : h,
+    VFI_DO(vfi_atm_window_attention_labels(qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, ntok, ao, C, cross ? of : nullptr, h, w, lab_h ? lab_h : h,
                                            lab_w ? lab_w : w, C, win, shift, cross, r.st));
-    if (cross) ATM_DO(vfi_atm_motion_mlp(of, B.m0w, B.m0b, B.m2w, B.m2b, mot, mot_cs, 2, (int64_t)h * w, r.st));
-    ATM_DO(r.conv(B.proj, ao, C, 2 * h, w, y, C, 1, 0, xn, C));      // norm1(x) + proj(attention): the residual is the NORMED token
-    ATM_DO(vfi_layernorm(y, C, C, ntok, B.n2w, B.n2b, t2, C, r.st));
-    ATM_DO(r.conv(B.fc1, t2, C, 2 * h, w, h1, M, 1, 0));
-    ATM_DO(vfi_atm_dwconv3x3_gelu(h1, M, B.dww, B.dwb, h2, M, 2, h, w, M, r.st));
+    if (cross) VFI_DO(vfi_atm_motion_mlp(of, B.m0w, B.m0b, B.m2w, B.m2b, mot, mot_cs, 2, (int64_t)h * w, r.st));
+    VFI_DO(r.conv(B.proj, ao, C, 2 * h, w, y, C, 1, 0, xn, C));      // norm1(x) + proj(attention): the residual is the NORMED token
+    VFI_DO(vfi_layernorm(y, C, C, ntok, B.n2w, B.n2b, t2, C, r.st));
+    VFI_DO(r.conv(B.fc1, t2, C, 2 * h, w, h1, M, 1, 0));
+    VFI_DO(vfi_atm_dwconv3x3_gelu(h1, M, B.dww, B.dwb, h2, M, 2, h, w, M, r.st));
     return r.conv(B.fc2, h2, M, 2 * h, w, out, C, 1, 0, y, C);
 }
 
@@ -675,13 +640,13 @@ int run_motion(Run& r, const Block* B, const Head& H, float* tok, float* tok2, i
     const int mcs = 2 * kHeads / 2 + 2 * C;      // 8 motion channels | frame 0 tokens | frame 1 tokens
     float *mh = r.buf("mh_in", 1, h, w, mcs), *a = r.buf("mh_a", 1, h, w, Ch), *b = r.buf("mh_b", 1, h, w, Ch);
     if (r.bad) return -1;
-    ATM_DO(run_block(r, B[0], tok, tok2, h, w, C, win, 0, true, mh, mcs));
-    ATM_DO(run_block(r, B[1], tok2, tok, h, w, C, win, win / 2, true, mh + 4, mcs, lab_h, lab_w));
+    VFI_DO(run_block(r, B[0], tok, tok2, h, w, C, win, 0, true, mh, mcs));
+    VFI_DO(run_block(r, B[1], tok2, tok, h, w, C, win, win / 2, true, mh + 4, mcs, lab_h, lab_w));
     const long px = (long)h * w;
-    ATM_DO(r.copy(tok, C, mh + 8, mcs, px, C));
-    ATM_DO(r.copy(tok + (size_t)px * C, C, mh + 8 + C, mcs, px, C));
-    ATM_DO(r.conv(H.c[0], mh, mcs, h, w, a, Ch, 1, 3));
-    ATM_DO(r.conv(H.c[1], a, Ch, h, w, b, Ch, 1, 3));
+    VFI_DO(r.copy(tok, C, mh + 8, mcs, px, C));
+    VFI_DO(r.copy(tok + (size_t)px * C, C, mh + 8 + C, mcs, px, C));
+    VFI_DO(r.conv(H.c[0], mh, mcs, h, w, a, Ch, 1, 3));
+    VFI_DO(r.conv(H.c[1], a, Ch, h, w, b, Ch, 1, 3));
     return r.conv(H.c[2], b, Ch, h, w, out5, 8, 1, 0);
 }
 
@@ -695,8 +660,8 @@ int run_features(Run& r, const float* x, const int* hs, const int* wsz, int firs
         const int hi = hs[first + (i ? i - 1 : 0)], wi = wsz[first + (i ? i - 1 : 0)], ho = hs[first + i], wo = wsz[first + i], c = g.hid[i];
         float* a = r.buf(an[first][i], 2, ho, wo, c);
         if (r.bad) return -1;
-        ATM_DO(r.conv(r.m->fe[i][0], x, xcs, hi, wi, a, c, 2, 3));
-        ATM_DO(r.conv(r.m->fe[i][1], a, c, ho, wo, f[i], fcs[i], 2, 3));
+        VFI_DO(r.conv(r.m->fe[i][0], x, xcs, hi, wi, a, c, 2, 3));
+        VFI_DO(r.conv(r.m->fe[i][1], a, c, ho, wo, f[i], fcs[i], 2, 3));
         x = f[i], xcs = fcs[i];
     }
     return 0;
@@ -712,9 +677,9 @@ int run_global(Run& r, const float* fine, const float* f3, int f3cs, int h, int 
     float *g0 = r.buf("gl_a", 2, h, w, g.last), *cat_g = r.buf("cat_g", 2, h, w, CG);
     float *gtok = r.buf("gtok_a", 1, 2 * h + 1, w, CG), *gtok2 = r.buf("gtok_b", 1, 2 * h + 1, w, CG);
     if (r.bad) return -1;
-    ATM_DO(r.conv(m->last[0], f3, f3cs, 2 * h, 2 * w, g0, g.last, 2, 3));
-    ATM_DO(r.conv(m->last[1], g0, g.last, h, w, cat_g + (CG - g.last), CG, 2, 3));
-    ATM_DO(run_fusion(r, m->gf, fine, g.hid[2], g.hid[2], f3, f3cs, g.hid[3], cat_g, CG, h, w, gtok));
+    VFI_DO(r.conv(m->last[0], f3, f3cs, 2 * h, 2 * w, g0, g.last, 2, 3));
+    VFI_DO(r.conv(m->last[1], g0, g.last, h, w, cat_g + (CG - g.last), CG, 2, 3));
+    VFI_DO(run_fusion(r, m->gf, fine, g.hid[2], g.hid[2], f3, f3cs, g.hid[3], cat_g, CG, h, w, gtok));
     return run_motion(r, m->glo, m->gh, gtok, gtok2, h, w, CG, g.global_head, 12, out5, lab_h, lab_w);
 }
 
@@ -726,15 +691,14 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
     const int Hp = m->Hp, Wp = m->Wp, top = (Hp - H) / 2, left = (Wp - W) / 2;
     const int hs[7] = {Hp, Hp / 2, Hp / 4, Hp / 8, Hp / 16, Hp / 32, Hp / 64}, wsz[7] = {Wp, Wp / 2, Wp / 4, Wp / 8, Wp / 16, Wp / 32, Wp / 64};
     const int h8 = hs[3], w8 = wsz[3], h16 = hs[4], w16 = wsz[4];
-    Run r{m, st};
+    Run r{{m, st}};
     // padded frames and their x0.5 pyramids (bilinear, align_corners=True)
     float* pyr[4];
     const char* pyr_names[4] = {"img0", "img1", "img2", "img3"};
     for (int i = 0; i < 4; ++i) pyr[i] = r.buf(pyr_names[i], 2, hs[i], wsz[i], 8);
     if (r.bad) return -1;
-    hipLaunchKernelGGL(atm_pad_kernel, dim3(nblk((long)Hp * Wp, 256), 2), dim3(256), 0, st, f0, f1, Cf, H, W, pyr[0], Hp, Wp, top, left);
-    VFI_CHECK_HIP(hipGetLastError());
-    for (int i = 1; i < 4; ++i) ATM_DO(vfi_resize_bilinear_ac(pyr[i - 1], 8, pyr[i], 8, 2, hs[i - 1], wsz[i - 1], hs[i], wsz[i], 3, 1.0f, st));
+    VFI_DO(pad_frame_pair(f0, f1, Cf, H, W, pyr[0], Hp, Wp, top, left, true, st));      // InputPadder(dims, 64) (atm/__init__.py:11-23): centred, replicate
+    for (int i = 1; i < 4; ++i) VFI_DO(vfi_resize_bilinear_ac(pyr[i - 1], 8, pyr[i], 8, 2, hs[i - 1], wsz[i - 1], hs[i], wsz[i], 3, 1.0f, st));
     // feature extraction on both frames; the 1/8 map lands in the last hid[3] channels of the local fusion's concat buffer
     float* cat_l = r.buf("cat_l", 2, h8, w8, CL);
     if (r.bad) return -1;
@@ -742,16 +706,16 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
                       cat_l + (CL - g.hid[3])};
     const int fcs[4] = {g.hid[0], g.hid[1], g.hid[2], CL};
     if (r.bad) return -1;
-    ATM_DO(run_features(r, pyr[0], hs, wsz, 0, feat, fcs));
+    VFI_DO(run_features(r, pyr[0], hs, wsz, 0, feat, fcs));
     const float* f3 = feat[3];
     float *tok = r.buf("tok_a", 1, 2 * h8 + 1, w8, CL), *tok2 = r.buf("tok_b", 1, 2 * h8 + 1, w8, CL);
     if (r.bad) return -1;
-    ATM_DO(run_fusion(r, m->lf, feat[1], g.hid[1], g.hid[1], feat[2], g.hid[2], g.hid[2], cat_l, CL, h8, w8, tok));
+    VFI_DO(run_fusion(r, m->lf, feat[1], g.hid[1], g.hid[1], feat[2], g.hid[2], g.hid[2], cat_l, CL, h8, w8, tok));
     const float *src0 = pyr[0], *src1 = pyr[0] + (size_t)Hp * Wp * 8;      // what the last synthesis step warps
     if (mode) {
         float* g5 = r.buf("gl_out5", 1, h16, w16, 8);
         if (r.bad) return -1;
-        ATM_DO(run_global(r, feat[2], f3, CL, h16, w16, g5));
+        VFI_DO(run_global(r, feat[2], f3, CL, h16, w16, g5));
         if (mode == 2) {
             // multiscale_global_motion_ensemble (network_lite.py:556-597): level 0 is g5 (the reference recomputes the same features from the
             // same input); levels 1 and 2 run the feature extractor and the global branch on pyr[1] / pyr[2], the x0.5 images it feeds them.
@@ -767,13 +731,13 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
                 for (int i = 0; i < 4; ++i) ef[i] = r.buf(fn[k - 1][i], 2, hs[k + i], wsz[k + i], g.hid[i]);
                 lev[k] = r.buf("ens_out5", 1, hk, wk, 8);
                 if (r.bad) return -1;
-                ATM_DO(run_features(r, pyr[k], hs, wsz, k, ef, g.hid));
-                ATM_DO(run_global(r, ef[2], ef[3], g.hid[3], hk, wk, lev[k], hs[4 + lab], wsz[4 + lab]));
+                VFI_DO(run_features(r, pyr[k], hs, wsz, k, ef, g.hid));
+                VFI_DO(run_global(r, ef[2], ef[3], g.hid[3], hk, wk, lev[k], hs[4 + lab], wsz[4 + lab]));
             }
             float *part = r.buf("ens_partial", 1, 1, 1, (int)vfi_atm_alignment_scratch_floats(Hp, Wp)), *sel = r.buf("ens_sel5", 1, h16, w16, 8);
             if (r.bad) return -1;
-            for (int k = 0; k < 3; ++k) ATM_DO(vfi_atm_alignment_loss(pyr[0], 8, Hp, Wp, lev[k], 8, hs[4 + k], wsz[4 + k], part, m->ens_rec + 4 + k, st));
-            ATM_DO(vfi_atm_select_flow(m->ens_rec + 4, lev[0], lev[1], lev[2], 8, h16, w16, sel, 8, m->ens_rec, st));
+            for (int k = 0; k < 3; ++k) VFI_DO(vfi_atm_alignment_loss(pyr[0], 8, Hp, Wp, lev[k], 8, hs[4 + k], wsz[4 + k], part, m->ens_rec + 4 + k, st));
+            VFI_DO(vfi_atm_select_flow(m->ens_rec + 4, lev[0], lev[1], lev[2], 8, h16, w16, sel, 8, m->ens_rec, st));
             m->ens_stream = st, m->ens_ran = true;
             g5 = sel;      // channels 0..3: the winner's flows; the global-level mask logit is not read
         }
@@ -785,35 +749,35 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
         const char* wp_names[4] = {"wimg0", "wimg1", "wimg2", "wimg3"};
         for (int i = 0; i < 4; ++i) wp[i] = r.buf(wp_names[i], 2, hs[i], wsz[i], 8);
         if (r.bad) return -1;
-        ATM_DO(vfi_resize_bilinear_ac(g5, 8, fl[3], 4, 1, h16, w16, h8, w8, 4, 2.0f, st));
+        VFI_DO(vfi_resize_bilinear_ac(g5, 8, fl[3], 4, 1, h16, w16, h8, w8, 4, 2.0f, st));
         const size_t p8 = (size_t)h8 * w8;
-        ATM_DO(vfi_flow_sample(tok, CL, fl[3], 4, tok2, CL, 1, h8, w8, CL, st));
-        ATM_DO(vfi_flow_sample(tok + p8 * CL, CL, fl[3] + 2, 4, tok2 + p8 * CL, CL, 1, h8, w8, CL, st));
+        VFI_DO(vfi_flow_sample(tok, CL, fl[3], 4, tok2, CL, 1, h8, w8, CL, st));
+        VFI_DO(vfi_flow_sample(tok + p8 * CL, CL, fl[3] + 2, 4, tok2 + p8 * CL, CL, 1, h8, w8, CL, st));
         float* t = tok;
         tok = tok2, tok2 = t;
         for (int i = 3; i >= 0; --i) {
             const size_t px = (size_t)hs[i] * wsz[i];
-            ATM_DO(vfi_flow_sample(pyr[i], 8, fl[i], 4, wp[i], 8, 1, hs[i], wsz[i], 3, st));
-            ATM_DO(vfi_flow_sample(pyr[i] + px * 8, 8, fl[i] + 2, 4, wp[i] + px * 8, 8, 1, hs[i], wsz[i], 3, st));
-            if (i) ATM_DO(vfi_resize_bilinear_ac(fl[i], 4, fl[i - 1], 4, 1, hs[i], wsz[i], hs[i - 1], wsz[i - 1], 4, 2.0f, st));
+            VFI_DO(vfi_flow_sample(pyr[i], 8, fl[i], 4, wp[i], 8, 1, hs[i], wsz[i], 3, st));
+            VFI_DO(vfi_flow_sample(pyr[i] + px * 8, 8, fl[i] + 2, 4, wp[i] + px * 8, 8, 1, hs[i], wsz[i], 3, st));
+            if (i) VFI_DO(vfi_resize_bilinear_ac(fl[i], 4, fl[i - 1], 4, 1, hs[i], wsz[i], hs[i - 1], wsz[i - 1], 4, 2.0f, st));
         }
         src0 = wp[0], src1 = wp[0] + (size_t)Hp * Wp * 8;
     }
     // local motion, feature enhancement
     float* o5 = r.buf("lo_out5", 1, h8, w8, 8);
     if (r.bad) return -1;
-    ATM_DO(run_motion(r, m->loc, m->lh, tok, tok2, h8, w8, CL, g.local_head, 8, o5));
-    ATM_DO(run_block(r, m->enh[0], tok, tok2, h8, w8, CL, 8, 0, false, nullptr, 0));
-    ATM_DO(run_block(r, m->enh[1], tok2, tok, h8, w8, CL, 8, 4, false, nullptr, 0));
+    VFI_DO(run_motion(r, m->loc, m->lh, tok, tok2, h8, w8, CL, g.local_head, 8, o5));
+    VFI_DO(run_block(r, m->enh[0], tok, tok2, h8, w8, CL, 8, 0, false, nullptr, 0));
+    VFI_DO(run_block(r, m->enh[1], tok2, tok, h8, w8, CL, 8, 4, false, nullptr, 0));
     // (warped frame 0 tokens | warped frame 1 tokens | the 5 motion channels), then the three up-sampling levels
     const int c0cs = r8(2 * CL + kMotion);
     float* fcat = r.buf("up_in", 1, h8, w8, c0cs);
     if (r.bad) return -1;
     {
         const size_t p8 = (size_t)h8 * w8;
-        ATM_DO(vfi_flow_sample(tok, CL, o5, 8, fcat, c0cs, 1, h8, w8, CL, st));
-        ATM_DO(vfi_flow_sample(tok + p8 * CL, CL, o5 + 2, 8, fcat + CL, c0cs, 1, h8, w8, CL, st));
-        ATM_DO(r.copy(o5, 8, fcat + 2 * CL, c0cs, (long)p8, kMotion));
+        VFI_DO(vfi_flow_sample(tok, CL, o5, 8, fcat, c0cs, 1, h8, w8, CL, st));
+        VFI_DO(vfi_flow_sample(tok + p8 * CL, CL, o5 + 2, 8, fcat + CL, c0cs, 1, h8, w8, CL, st));
+        VFI_DO(r.copy(o5, 8, fcat + 2 * CL, c0cs, (long)p8, kMotion));
     }
     float* R = r.buf("ref_in", 1, Hp, Wp, rcs);      // (feat local_c / 4 + 5 | im0 | warped 0 | im1 | warped 1 | I_t)
     float* lvl[3] = {nullptr, nullptr, R};
@@ -828,20 +792,20 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
             if (U.pre) {
                 float* p = r.buf(pn[i], 1, h, w, r8(U.cin));
                 if (r.bad) return -1;
-                ATM_DO(r.copy(x, xcs, p, r8(U.cin), (long)h * w, U.cin, U.pre));
+                VFI_DO(r.copy(x, xcs, p, r8(U.cin), (long)h * w, U.cin, U.pre));
                 x = p, xcs = r8(U.cin);
             }
             float *d = r.buf(dn[i], 1, 2 * h, 2 * w, ccs), *c = r.buf(cn[i], 1, 2 * h, 2 * w, ccs);
             if (i < 2) lvl[i] = r.buf(on[i], 1, 2 * h, 2 * w, ccs), lcs[i] = ccs;
             if (r.bad) return -1;
-            ATM_DO(r.deconv(U.de, U.c, x, xcs, h, w, d, ccs));
-            ATM_DO(r.conv(U.c1, d, ccs, 2 * h, 2 * w, c, ccs, 1, 3));
-            ATM_DO(r.conv(U.c2, c, ccs, 2 * h, 2 * w, lvl[i], lcs[i], 1, 0));
+            VFI_DO(r.deconv(U.de, U.c, x, xcs, h, w, d, ccs));
+            VFI_DO(r.conv(U.c1, d, ccs, 2 * h, 2 * w, c, ccs, 1, 3));
+            VFI_DO(r.conv(U.c2, c, ccs, 2 * h, 2 * w, lvl[i], lcs[i], 1, 0));
             x = lvl[i], xcs = lcs[i];
         }
     }
     const int fc = CL / 4 + kMotion;      // 61 / 101
-    ATM_DO(vfi_atm_blend_warps(src0, src1, 8, pyr[0], pyr[0] + (size_t)Hp * Wp * 8, 8, R + fc - kMotion, rcs, R + fc, rcs, Hp, Wp, st));
+    VFI_DO(vfi_atm_blend_warps(src0, src1, 8, pyr[0], pyr[0] + (size_t)Hp * Wp * 8, 8, R + fc - kMotion, rcs, R + fc, rcs, Hp, Wp, st));
     // residual refinement (network_lite.py:409-423), hidden width hd; concat buffers: c6 = (u0 | r0), c2 = (r1 | skip 1/2), c3 = (r2 | skip 1/4),
     // c4 = (u2 | r2), c5 = (u1 | r1)
     const int h2 = hs[1], w2 = wsz[1], h4 = hs[2], w4 = wsz[2];
@@ -850,24 +814,24 @@ int atm_forward(vfi_atm* m, const float* f0, const float* f1, int Cf, int H, int
     float *c5 = r.buf("rf_c5", 1, h2, w2, 2 * hd), *d2 = r.buf("rf_d2", 1, h4, w4, 2 * hd), *d3a = r.buf("rf_d3a", 1, h8, w8, 4 * hd), *d3b = r.buf("rf_d3b", 1, h8, w8, 4 * hd);
     float *u2 = r.buf("rf_u2", 1, h4, w4, 2 * hd), *u1 = r.buf("rf_u1", 1, h2, w2, 2 * hd), *rh = r.buf("rf_h", 1, Hp, Wp, hd), *res = r.buf("rf_res", 1, Hp, Wp, 8);
     if (r.bad) return -1;
-    ATM_DO(r.conv(m->proj, R, rcs, Hp, Wp, c6 + hd, 2 * hd, 1, 3));
-    ATM_DO(r.conv(m->down1, c6 + hd, 2 * hd, Hp, Wp, c2, s2, 1, 3));
-    ATM_DO(r.copy(lvl[1], lcs[1], c2 + hd, s2, (long)h2 * w2, CL / 2));
-    ATM_DO(r.conv(m->down2[0], c2, s2, h2, w2, d2, 2 * hd, 1, 3));
-    ATM_DO(r.conv(m->down2[1], d2, 2 * hd, h4, w4, c3, s3, 1, 3));
-    ATM_DO(r.copy(lvl[0], lcs[0], c3 + 2 * hd, s3, (long)h4 * w4, CL));
-    ATM_DO(r.copy(c3, s3, c4 + 2 * hd, 4 * hd, (long)h4 * w4, 2 * hd));
-    ATM_DO(r.copy(c2, s2, c5 + hd, 2 * hd, (long)h2 * w2, hd));
-    ATM_DO(r.conv(m->down3[0], c3, s3, h4, w4, d3a, 4 * hd, 1, 3));
-    ATM_DO(r.conv(m->down3[1], d3a, 4 * hd, h8, w8, d3b, 4 * hd, 1, 3));
-    ATM_DO(r.conv(m->down3[2], d3b, 4 * hd, h8, w8, d3a, 4 * hd, 1, 3));
-    ATM_DO(r.deconv(m->up1d, 2 * hd, d3a, 4 * hd, h8, w8, u2, 2 * hd));
-    ATM_DO(r.conv(m->up1c, u2, 2 * hd, h4, w4, c4, 4 * hd, 1, 3));
-    ATM_DO(r.deconv(m->up2d, 2 * hd, c4, 4 * hd, h4, w4, u1, 2 * hd));
-    ATM_DO(r.conv(m->up2c, u1, 2 * hd, h2, w2, c5, 2 * hd, 1, 3));
-    ATM_DO(r.deconv(m->up3d, hd, c5, 2 * hd, h2, w2, c6, 2 * hd));
-    ATM_DO(r.conv(m->rh[0], c6, 2 * hd, Hp, Wp, rh, hd, 1, 3));
-    ATM_DO(r.conv(m->rh[1], rh, hd, Hp, Wp, res, 8, 1, 3));
+    VFI_DO(r.conv(m->proj, R, rcs, Hp, Wp, c6 + hd, 2 * hd, 1, 3));
+    VFI_DO(r.conv(m->down1, c6 + hd, 2 * hd, Hp, Wp, c2, s2, 1, 3));
+    VFI_DO(r.copy(lvl[1], lcs[1], c2 + hd, s2, (long)h2 * w2, CL / 2));
+    VFI_DO(r.conv(m->down2[0], c2, s2, h2, w2, d2, 2 * hd, 1, 3));
+    VFI_DO(r.conv(m->down2[1], d2, 2 * hd, h4, w4, c3, s3, 1, 3));
+    VFI_DO(r.copy(lvl[0], lcs[0], c3 + 2 * hd, s3, (long)h4 * w4, CL));
+    VFI_DO(r.copy(c3, s3, c4 + 2 * hd, 4 * hd, (long)h4 * w4, 2 * hd));
+    VFI_DO(r.copy(c2, s2, c5 + hd, 2 * hd, (long)h2 * w2, hd));
+    VFI_DO(r.conv(m->down3[0], c3, s3, h4, w4, d3a, 4 * hd, 1, 3));
+    VFI_DO(r.conv(m->down3[1], d3a, 4 * hd, h8, w8, d3b, 4 * hd, 1, 3));
+    VFI_DO(r.conv(m->down3[2], d3b, 4 * hd, h8, w8, d3a, 4 * hd, 1, 3));
+    VFI_DO(r.deconv(m->up1d, 2 * hd, d3a, 4 * hd, h8, w8, u2, 2 * hd));
+    VFI_DO(r.conv(m->up1c, u2, 2 * hd, h4, w4, c4, 4 * hd, 1, 3));
+    VFI_DO(r.deconv(m->up2d, 2 * hd, c4, 4 * hd, h4, w4, u1, 2 * hd));
+    VFI_DO(r.conv(m->up2c, u1, 2 * hd, h2, w2, c5, 2 * hd, 1, 3));
+    VFI_DO(r.deconv(m->up3d, hd, c5, 2 * hd, h2, w2, c6, 2 * hd));
+    VFI_DO(r.conv(m->rh[0], c6, 2 * hd, Hp, Wp, rh, hd, 1, 3));
+    VFI_DO(r.conv(m->rh[1], rh, hd, Hp, Wp, res, 8, 1, 3));
     return vfi_atm_refine_out(R + fc + 12, rcs, res, 8, out, Hp, Wp, top, left, H, W, st);
 }
 
@@ -877,9 +841,9 @@ int atm_pad64(int n) { return n + (((n / 64) + 1) * 64 - n) % 64; }
 
 extern "C" {
 
-int64_t vfi_atm_max_padded_pixels(void) { return (int64_t)(0x7fffffffL / (kCfg[0].px_floats * 4)); }
+int64_t vfi_atm_max_padded_pixels(void) { return max_padded_pixels(kCfg[0].px_floats); }
 
-int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* m) { return m ? (int64_t)(0x7fffffffL / (kCfg[m->variant].px_floats * 4)) : 0; }
+int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* m) { return m ? max_padded_pixels(kCfg[m->variant].px_floats) : 0; }
 
 vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors) { return vfi_atm_create_variant(tensors, numels, n_tensors, 0); }
 
@@ -898,13 +862,7 @@ vfi_atm_t* vfi_atm_create_variant(const float* const* tensors, const int64_t* nu
     TensorCursor cur(tensors, numels, n_tensors, variant ? "vfi_atm_create (ATM-base)" : "vfi_atm_create (ATM-lite)");
     std::vector<float> tmp, tb, tp;
     // Conv2d(cin, cout, k, stride, padding k / 2) with bias [+ PReLU]
-    auto conv = [&](int cout, int cin, int k, int stride, bool prelu, bool bias = true) -> vfi_conv_t* {
-        const float* w = cur.take((int64_t)cout * cin * k * k);
-        const float* b = bias ? cur.take(cout) : nullptr;
-        const float* p = prelu ? cur.take(cout) : nullptr;
-        if (!cur.ok()) return nullptr;
-        return m->add_layer(vfi_conv_create_ex(0, w, b, cout, cin, k, stride, 0, nullptr, r8(cin), p));
-    };
+    auto conv = [&](int cout, int cin, int k, int stride, bool prelu, bool bias = true) { return m->read_layer(cur, 0, cout, cin, k, stride, bias, prelu); };
     // Conv2d(c, c, 3, stride s, dilation d, padding d) as a 1x1 layer over the gathered taps: input channel t c + ci
     auto tapconv = [&](int c) -> vfi_conv_t* {
         const float* w = cur.take((int64_t)c * c * 9);
@@ -1031,15 +989,10 @@ int64_t vfi_atm_workspace_bytes(const vfi_atm_t* m) { return m ? m->ws.bytes() :
 
 namespace {
 
-// the size guard and the workspace key shared by the two entry points; `who` names the caller in the refusal
+// the size guard and the workspace key of the two entry points; `who` names the caller in the refusal
 int atm_enter(vfi_atm_t* m, const char* who, int H, int W) {
-    const int Hp = atm_pad64(H), Wp = atm_pad64(W);
-    VFI_REQUIRE((int64_t)Hp * Wp <= vfi_atm_object_max_padded_pixels(m),
-                "%s: a %dx%d frame (padded %dx%d) is over the size limit of %s: Hp * Wp * %d bytes must stay below 2 GiB for the layers' "
-                "index arithmetic (1088x1920 fits)", who, H, W, Hp, Wp, kCfg[m->variant].name, kCfg[m->variant].px_floats * 4);
-    if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp) && m->ws.release()) return -1;
-    m->Hp = Hp, m->Wp = Wp;
-    return 0;
+    const Cfg& g = kCfg[m->variant];
+    return m->enter(who, g.name, H, W, atm_pad64(H), atm_pad64(W), g.px_floats);
 }
 
 }  // namespace

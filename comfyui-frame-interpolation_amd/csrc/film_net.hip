@@ -23,7 +23,6 @@ namespace {
 constexpr int PYR = 7, FUS = 5, SUB = 4, FILTERS = 64;
 const int kFlowFilters[4] = {32, 64, 128, 256};
 
-int r8(int n) { return (n + 7) / 8 * 8; }
 int feat_channels(int level) {   // 64, 192, 448, 960, 960, ...
     int s = 0;
     for (int j = 0; j <= std::min(level, SUB - 1); ++j) s += FILTERS << j;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/vfi_hip.h"
+#include "net_object.h"
 #include "vfi_common.h"
 
 namespace vfi {
@@ -187,6 +188,31 @@ __global__ void s2d_pad1_kernel(const float* __restrict__ in, int in_cs, float* 
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = *(const float4*)(in + ((size_t)((size_t)n * H + iy) * W + ix) * in_cs + 4 * q);
     ((float4*)out)[idx] = v;
+}
+
+// ---- the frame-in of the nets that pad a frame pair (net_object.h: pad_frame_pair) -----------------------------------------------
+// Copies only, no arithmetic; blockIdx.y = frame.  A border pixel takes the nearest frame pixel (replicate) or zero.
+namespace {
+__global__ void pad_pair_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W, float* __restrict__ img, int Hp,
+                                int Wp, int top, int left, int replicate) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)Hp * Wp) return;
+    const int x = (int)(idx % Wp) - left, y = (int)(idx / Wp) - top;
+    float* o = img + ((size_t)blockIdx.y * Hp * Wp + idx) * 8;
+    if (replicate || (x >= 0 && x < W && y >= 0 && y < H)) {
+        const float* s = (blockIdx.y ? f1 : f0) + ((size_t)min(max(y, 0), H - 1) * W + min(max(x, 0), W - 1)) * C;
+        o[0] = s[0], o[1] = s[1], o[2] = s[2];
+    } else {
+        o[0] = o[1] = o[2] = 0.f;
+    }
+}
+}  // namespace
+
+int pad_frame_pair(const float* f0, const float* f1, int C, int H, int W, float* img, int Hp, int Wp, int top, int left, bool replicate,
+                   hipStream_t st) {
+    hipLaunchKernelGGL(pad_pair_kernel, dim3(nblk((long)Hp * Wp, 256), 2), dim3(256), 0, st, f0, f1, C, H, W, img, Hp, Wp, top, left, (int)replicate);
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace vfi

@@ -1,6 +1,8 @@
-// What the whole-network objects (vfi_film, vfi_m2m, vfi_cain, vfi_sepconvnet, vfi_flavr) share: the checkpoint cursor of their create
-// functions, the workspace that owns their activations, and the base that owns their layers and device parameter blocks.  A net keeps
-// what is its own: the layer table, weight re-layouts, ensure_workspace's size arithmetic and the forward sequence.
+// What the whole-network objects share.  All eight (vfi_film, vfi_m2m, vfi_cain, vfi_sepconvnet, vfi_flavr, vfi_amt, vfi_atm, vfi_xvfi): the
+// checkpoint cursor and layer reader of their create functions, the workspace that owns their activations, and the base that owns their
+// layers and device parameter blocks.  The three whose activations are all named scratch tensors (AMT, ATM, XVFI) also share the run
+// context of a forward call, the frame-pair pad and the entry guard of a padded net.  A net keeps what is its own: the layer table, weight
+// re-layouts, its size arithmetic and the forward sequence.
 #pragma once
 #include <map>
 #include <string>
@@ -14,6 +16,16 @@
 #define VFI_INTERNAL __attribute__((visibility("hidden")))
 
 namespace vfi {
+
+inline int r8(int c) { return (c + 7) & ~7; }      // channel counts are padded to multiples of 8
+inline int nblk(long n, int per) { return (int)((n + per - 1) / per); }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// returns early on a failed launch or layer call
+#define VFI_DO(x)          \
+    do {                   \
+        if (x) return -1;  \
+    } while (0)
 
 struct VFI_INTERNAL Ten {   // [n][h][w][c] fp32
     float* p = nullptr;
@@ -151,6 +163,17 @@ struct VFI_INTERNAL NetObject {
         return L;
     }
 
+    // The next layer of the checkpoint, as it is: Conv2d (kind 0) / ConvTranspose2d (kind 1) weights, then the bias and the per-channel
+    // PReLU slopes where the layer has them.  map: logical -> physical input channels; cin_phys: the input's channel stride, r8(cin) if 0.
+    vfi_conv_t* read_layer(TensorCursor& cur, int kind, int cout, int cin, int k, int stride, bool bias, bool prelu, const int* map = nullptr,
+                           int cin_phys = 0) {
+        const float* w = cur.take((int64_t)cout * cin * k * k);
+        const float* b = bias ? cur.take(cout) : nullptr;
+        const float* p = prelu ? cur.take(cout) : nullptr;
+        if (!cur.ok()) return nullptr;
+        return add_layer(vfi_conv_create_ex(kind, w, b, cout, cin, k, stride, 0, map, cin_phys ? cin_phys : r8(cin), p));
+    }
+
     // device copy of src[0 .. floats); src == nullptr: the block is only allocated (a pack kernel fills it)
     float* upload(const float* src, size_t floats) {
         float* d = nullptr;
@@ -173,5 +196,54 @@ struct VFI_INTERNAL NetObject {
         for (float* p : params) (void)hipFree(p);
     }
 };
+
+// ---- nets that pad a frame pair and keep every activation as a named scratch tensor (AMT, ATM, XVFI) ----------------------------------
+
+// The layers index one image with 32 bits of bytes: the padded pixels a net may take whose widest buffer has px_floats floats per pixel.
+inline int64_t max_padded_pixels(int px_floats) { return 0x7fffffffLL / (px_floats * 4); }
+
+// Base of such a net: the padded size is the key of its workspace.
+struct VFI_INTERNAL PaddedNet : NetObject {
+    int Hp = 0, Wp = 0;
+
+    // The entry guard of a forward: an H x W frame padded to Hp x Wp is refused before any launch or allocation when it is over the size
+    // limit; the workspace is released when the padded size (or the caller's own part of the key, `rekey`) changed; the key is stored.
+    // who: the entry point, net: the model's name in the refusal.
+    int enter(const char* who, const char* net, int H, int W, int Hp_, int Wp_, int px_floats, bool rekey = false) {
+        VFI_REQUIRE((int64_t)Hp_ * Wp_ <= max_padded_pixels(px_floats),
+                    "%s: a %dx%d frame (padded %dx%d) is over the size limit of %s, %lld padded pixels: Hp * Wp * %d bytes must stay below 2 GiB "
+                    "for the layers' index arithmetic", who, H, W, Hp_, Wp_, net, (long long)max_padded_pixels(px_floats), px_floats * 4);
+        if (ws.live() && (Hp != Hp_ || Wp != Wp_ || rekey) && ws.release()) return -1;
+        Hp = Hp_, Wp = Wp_;
+        return 0;
+    }
+};
+
+// One forward call of such a net: the scratch tensors by name, the launches' stream and a sticky failure flag (a failed buf() makes every
+// later one fail, so a run asks for several and tests `bad` once).  leaky: the slope of act 1 (0: a ReLU).  A net's Run derives from
+// this and adds its own launches.
+template <class Net>
+struct VFI_INTERNAL NetRun {
+    Net* m;
+    hipStream_t st;
+    float leaky = 0.f;
+    bool bad = false;
+    float* buf(const char* name, int n, int h, int w, int c) {
+        Ten* t = nullptr;
+        if (bad || m->ws.tmp(name, n, h, w, c, &t)) {
+            bad = true;
+            return nullptr;
+        }
+        return t->p;
+    }
+    int conv(const vfi_conv_t* L, const float* in, int ics, int h, int w, float* out, int ocs, int N, int act, const float* res = nullptr, int rcs = 0) {
+        return vfi_conv_forward_ex(L, in, ics, h, w, out, ocs, N, act, act == 1 ? leaky : 0.f, 0.f, 0.f, res, rcs, st);
+    }
+};
+
+// Both frames' channels 0..2 ([H,W,C>=3]) into img [2,Hp,Wp,8] with the frame at (top, left); the border repeats the frame's edge
+// (replicate: InputPadder, AMT and ATM) or is zero (F.pad to the bottom / right with top = left = 0: XVFI).  gen_ops.hip.
+VFI_INTERNAL int pad_frame_pair(const float* f0, const float* f1, int C, int H, int W, float* img, int Hp, int Wp, int top, int left, bool replicate,
+                                hipStream_t st);
 
 }  // namespace vfi

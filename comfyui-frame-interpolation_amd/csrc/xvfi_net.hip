@@ -8,7 +8,7 @@
 //   xvfi_assemble       level 0 (:213-221): the x scale flow upscale, both image warps, pixel_shuffle of the four feature maps: the
 //                       RefineUNet's input in one pass
 //   xvfi_blend_out      the occlusion blend plus residual (:222-226) and the crop
-//   xvfi_pad / xvfi_same   the node's zero pad to the right / bottom; whether the object's cached pair is the pair it is given
+//   xvfi_same              whether the object's cached pair is the pair it is given (the node's zero pad is net_object.h's pad_frame_pair)
 //
 // Built with -ffp-contract=off (csrc/build.py): a splat target is the single fp32 product t * flow, and the warps' grid coordinates round
 // as torch rounds them.
@@ -23,9 +23,6 @@
 
 namespace vfi {
 namespace {
-
-inline int nblk(long n, int per) { return (int)((n + per - 1) / per); }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // torch's upsample_bicubic2d with A = -0.75 at the half-pixel phase every output of an even 1 / l reduction has: cubic_convolution2(1.5),
 // cubic_convolution1(0.5), cubic_convolution1(0.5), cubic_convolution2(1.5) = -3/32, 19/32, 19/32, -3/32; source rows l i + l / 2 - 2 ...
@@ -284,20 +281,6 @@ __global__ void xvfi_blend_kernel(const float* __restrict__ ro, int ro_cs, const
     for (int k = 0; k < 3; ++k) out[(size_t)idx * 3 + k] = (a * wv[k] + b * wv[3 + k]) / den + r[1 + k];
 }
 
-// F.pad(frames, (0, Wp - W, 0, Hp - H)) of both frames into channels 0..2 of img [2,Hp,Wp,8]; blockIdx.y = frame
-__global__ void xvfi_pad_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W, float* __restrict__ img, int Hp, int Wp) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)Hp * Wp) return;
-    const int X = (int)(idx % Wp), Y = (int)(idx / Wp);
-    float* o = img + ((size_t)blockIdx.y * Hp * Wp + idx) * 8;
-    if (X < W && Y < H) {
-        const float* s = (blockIdx.y ? f1 : f0) + ((size_t)Y * W + X) * C;
-        o[0] = s[0], o[1] = s[1], o[2] = s[2];
-    } else {
-        o[0] = o[1] = o[2] = 0.f;
-    }
-}
-
 // *differs |= 1 where a frame's bits are not the padded copy's: whether the features the object holds are this pair's (bit compare, so
 // that a NaN pixel equals itself)
 __global__ void xvfi_same_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W, const float* __restrict__ img, int Hp, int Wp,
@@ -405,55 +388,35 @@ struct Tower {      // Conv2d(4, 2, 1), Conv2d(4, 2, 1), up 2 + 3x3, up 2 + 3x3,
 
 }  // namespace
 
-struct vfi_xvfi : NetObject {
+struct vfi_xvfi : PaddedNet {
     int scale = 2, S = 1, nds = 1;      // module_scale_factor, S_tst, log2(scale)
     vfi_conv_t *cc = nullptr, *ext_ds = nullptr, *ext_c = nullptr, *rb[4] = {}, *ctx_ds = nullptr;
     Tower bottom, flow2, flow3;
     vfi_conv_t *flow1 = nullptr, *flow3_in = nullptr;
     vfi_conv_t *enc1 = nullptr, *enc2 = nullptr, *enc3 = nullptr, *dec0 = nullptr, *dec1 = nullptr, *dec2 = nullptr, *dec3 = nullptr;
-    int H = 0, W = 0, Hp = 0, Wp = 0;
+    int H = 0, W = 0;            // the frame size is part of the workspace key too: the kept pair is compared against the padded copy
     bool have_pair = false;      // the workspace holds the features, the level flows and flow_l_tmp of the pair whose padded copy is "img"
     int* flag_host = nullptr;    // pinned: xvfi_same_kernel's verdict
 };
 
 namespace {
 
-struct Run {
-    vfi_xvfi* m;
-    hipStream_t st;
-    bool bad = false;
-    float* buf(const char* name, int n, int h, int w, int c) {
-        Ten* t = nullptr;
-        if (bad || m->ws.tmp(name, n, h, w, c, &t)) {
-            bad = true;
-            return nullptr;
-        }
-        return t->p;
-    }
-    // act: 0 none, 1 ReLU
-    int conv(const vfi_conv_t* L, const float* in, int ics, int h, int w, float* out, int ocs, int N, int act, const float* res = nullptr, int rcs = 0) {
-        return vfi_conv_forward_ex(L, in, ics, h, w, out, ocs, N, act, 0.f, 0.f, 0.f, res, rcs, st);
-    }
+struct Run : NetRun<vfi_xvfi> {      // conv's act: 0 none, 1 ReLU
     int copy(const float* a, int a_cs, float* out, int out_cs, long px, int C) { return vfi_axpby(a, a_cs, nullptr, 0, out, out_cs, px, C, 1.f, 0.f, st); }
     int up2(const float* in, int ics, int h, int w, float* out, int ocs, int C) { return vfi_upsample_nearest(in, ics, out, ocs, 1, h, w, 2 * h, 2 * w, C, st); }
 };
-
-#define XV_DO(x)           \
-    do {                   \
-        if (x) return -1;  \
-    } while (0)
 
 // in [h,w,ics] -> out [h,w,8] (+ res); h, w multiples of 4.  UpsamplingNearest2d(2) is the nearest resize in front of its 3x3 layer, not fused.
 int run_tower(Run& r, const Tower& T, const float* in, int ics, int h, int w, float* out, const float* res = nullptr, int rcs = 0) {
     float *t1 = r.buf("tw_t1", 1, h / 2, w / 2, 2 * NF), *t2 = r.buf("tw_t2", 1, h / 4, w / 4, 4 * NF), *u1 = r.buf("tw_u1", 1, h / 2, w / 2, 4 * NF);
     float *t3 = r.buf("tw_t3", 1, h / 2, w / 2, 2 * NF), *u2 = r.buf("tw_u2", 1, h, w, 2 * NF), *t4 = r.buf("tw_t4", 1, h, w, NF);
     if (r.bad) return -1;
-    XV_DO(r.conv(T.d1, in, ics, h, w, t1, 2 * NF, 1, 1));
-    XV_DO(r.conv(T.d2, t1, 2 * NF, h / 2, w / 2, t2, 4 * NF, 1, 1));
-    XV_DO(r.up2(t2, 4 * NF, h / 4, w / 4, u1, 4 * NF, 4 * NF));
-    XV_DO(r.conv(T.u1, u1, 4 * NF, h / 2, w / 2, t3, 2 * NF, 1, 1));
-    XV_DO(r.up2(t3, 2 * NF, h / 2, w / 2, u2, 2 * NF, 2 * NF));
-    XV_DO(r.conv(T.u2, u2, 2 * NF, h, w, t4, NF, 1, 1));
+    VFI_DO(r.conv(T.d1, in, ics, h, w, t1, 2 * NF, 1, 1));
+    VFI_DO(r.conv(T.d2, t1, 2 * NF, h / 2, w / 2, t2, 4 * NF, 1, 1));
+    VFI_DO(r.up2(t2, 4 * NF, h / 4, w / 4, u1, 4 * NF, 4 * NF));
+    VFI_DO(r.conv(T.u1, u1, 4 * NF, h / 2, w / 2, t3, 2 * NF, 1, 1));
+    VFI_DO(r.up2(t3, 2 * NF, h / 2, w / 2, u2, 2 * NF, 2 * NF));
+    VFI_DO(r.conv(T.u2, u2, 2 * NF, h, w, t4, NF, 1, 1));
     return r.conv(T.o, t4, NF, h, w, out, 8, 1, 0, res, rcs);
 }
 
@@ -465,39 +428,38 @@ const char* lname(const char* base, int l, char (&buf)[24]) {
 // once per pair: the zero pad, the features of both frames at every level (XVFInet.forward :53-58), the flows of levels S .. 1 and level
 // 0's flow_l_tmp / flow_l (VFInet.forward :165-178): none of it depends on t
 int xvfi_prepare(vfi_xvfi* m, const float* f0, const float* f1, int C, hipStream_t st) {
-    Run r{m, st};
+    Run r{{m, st}};
     const int Hp = m->Hp, Wp = m->Wp, s = m->scale, h0 = Hp / s, w0 = Wp / s;
     char nb[24];
     float* img = r.buf("img", 2, Hp, Wp, 8);
     if (r.bad) return -1;
-    hipLaunchKernelGGL(xvfi_pad_kernel, dim3(nblk((long)Hp * Wp, 256), 2), dim3(256), 0, st, f0, f1, C, m->H, m->W, img, Hp, Wp);
-    VFI_CHECK_HIP(hipGetLastError());
+    VFI_DO(pad_frame_pair(f0, f1, C, m->H, m->W, img, Hp, Wp, 0, 0, false, st));      // F.pad(frames, (0, Wp - W, 0, Hp - H)): zeros
     // channel_converter, rec_ext_ds x log2(scale), the 3x3 layer, RResBlock2D_3D: Conv3d layers with temporal kernel 1 = a batch of two frames
     float* F[kMaxLevels];
     {
         float* x = r.buf("fe_cc", 2, Hp, Wp, NF);
         if (r.bad) return -1;
-        XV_DO(r.conv(m->cc, img, 8, Hp, Wp, x, NF, 2, 1));
+        VFI_DO(r.conv(m->cc, img, 8, Hp, Wp, x, NF, 2, 1));
         int h = Hp, w = Wp;
         for (int i = 0; i < m->nds; ++i) {
             float* y = r.buf(lname("fe_ds", i, nb), 2, h / 2, w / 2, NF);
             if (r.bad) return -1;
-            XV_DO(r.conv(m->ext_ds, x, NF, h, w, y, NF, 2, 1));
+            VFI_DO(r.conv(m->ext_ds, x, NF, h, w, y, NF, 2, 1));
             x = y, h /= 2, w /= 2;
         }
         float *x0 = r.buf("fe_x0", 2, h, w, NF), *t1 = r.buf("fe_t1", 2, h, w, NF), *y1 = r.buf("fe_y1", 2, h, w, NF), *y2 = r.buf("fe_y2", 2, h, w, NF);
         F[0] = r.buf("feat0", 2, h, w, 2 * NF);
         if (r.bad) return -1;
-        XV_DO(r.conv(m->ext_c, x, NF, h, w, x0, NF, 2, 0));
-        XV_DO(r.conv(m->rb[0], x0, NF, h, w, t1, NF, 2, 1));
-        XV_DO(r.conv(m->rb[1], t1, NF, h, w, y1, NF, 2, 0, x0, NF));
-        XV_DO(r.conv(m->rb[2], y1, NF, h, w, t1, NF, 2, 1));
-        XV_DO(r.conv(m->rb[3], t1, NF, h, w, y2, NF, 2, 0, y1, NF));
-        XV_DO(vfi_axpby(y2, NF, x0, NF, F[0], 2 * NF, 2L * h * w, NF, 1.f, 1.f, st));
+        VFI_DO(r.conv(m->ext_c, x, NF, h, w, x0, NF, 2, 0));
+        VFI_DO(r.conv(m->rb[0], x0, NF, h, w, t1, NF, 2, 1));
+        VFI_DO(r.conv(m->rb[1], t1, NF, h, w, y1, NF, 2, 0, x0, NF));
+        VFI_DO(r.conv(m->rb[2], y1, NF, h, w, t1, NF, 2, 1));
+        VFI_DO(r.conv(m->rb[3], t1, NF, h, w, y2, NF, 2, 0, y1, NF));
+        VFI_DO(vfi_axpby(y2, NF, x0, NF, F[0], 2 * NF, 2L * h * w, NF, 1.f, 1.f, st));
         for (int l = 1; l <= m->S; ++l) {
             F[l] = r.buf(lname("feat", l, nb), 2, h0 >> l, w0 >> l, 2 * NF);
             if (r.bad) return -1;
-            XV_DO(r.conv(m->ctx_ds, F[l - 1], 2 * NF, h0 >> (l - 1), w0 >> (l - 1), F[l], 2 * NF, 2, 0));
+            VFI_DO(r.conv(m->ctx_ds, F[l - 1], 2 * NF, h0 >> (l - 1), w0 >> (l - 1), F[l], 2 * NF, 2, 0));
         }
     }
     // the recursion: flow_l [h,w,4] per level in "flow<l>", level 0's flow_l_tmp (6 channels) in "tmp0"
@@ -510,23 +472,23 @@ int xvfi_prepare(vfi_xvfi* m, const float* f0, const float* f1, int C, hipStream
         if (!prev) {
             float* B = r.buf(lname("cat", l, nb), 1, h, w, 2 * NF);
             if (r.bad) return -1;
-            XV_DO(r.copy(F[l], 2 * NF, B, 2 * NF, (long)hw, NF));
-            XV_DO(r.copy(F[l] + hw * 2 * NF, 2 * NF, B + NF, 2 * NF, (long)hw, NF));
-            XV_DO(run_tower(r, m->bottom, B, 2 * NF, h, w, tmp));
-            XV_DO(r.copy(tmp, 8, fl, 4, (long)hw, 4));
+            VFI_DO(r.copy(F[l], 2 * NF, B, 2 * NF, (long)hw, NF));
+            VFI_DO(r.copy(F[l] + hw * 2 * NF, 2 * NF, B + NF, 2 * NF, (long)hw, NF));
+            VFI_DO(run_tower(r, m->bottom, B, 2 * NF, h, w, tmp));
+            VFI_DO(r.copy(tmp, 8, fl, 4, (long)hw, 4));
         } else {
             const int gcs = 2 * NF + 8;
             float *G = r.buf(lname("cf", l, nb), 1, h, w, gcs), *CF = r.buf(lname("cf1_", l, nb), 2, h, w, NF);
             if (r.bad) return -1;
             float* up = G + 2 * NF;      // up_flow_l_prev: channels 128..131 of conv_flow2's input
-            XV_DO(vfi_resize_bilinear(prev, 4, up, gcs, 1, h / 2, w / 2, h, w, 4, 2.0f, st));
+            VFI_DO(vfi_resize_bilinear(prev, 4, up, gcs, 1, h / 2, w / 2, h, w, 4, 2.0f, st));
             // warped_feat1 = bwarp(feat1, up[:, :2]) beside feat0, warped_feat0 = bwarp(feat0, up[:, 2:]) beside feat1: conv_flow1's two inputs
-            XV_DO(vfi_xvfi_bwarp(F[l], 2 * NF, (int64_t)hw * 2 * NF, 1, up, gcs, 2, F[l] + NF, 2 * NF, (int64_t)hw * 2 * NF, 2, h, w, NF, st));
-            XV_DO(r.conv(m->flow1, F[l], 2 * NF, h, w, CF, NF, 2, 0));
-            XV_DO(r.copy(CF, NF, G, gcs, (long)hw, NF));
-            XV_DO(r.copy(CF + hw * NF, NF, G + NF, gcs, (long)hw, NF));
-            XV_DO(run_tower(r, m->flow2, G, gcs, h, w, tmp));
-            XV_DO(vfi_axpby(tmp, 8, up, gcs, fl, 4, (long)hw, 4, 1.f, 1.f, st));
+            VFI_DO(vfi_xvfi_bwarp(F[l], 2 * NF, (int64_t)hw * 2 * NF, 1, up, gcs, 2, F[l] + NF, 2 * NF, (int64_t)hw * 2 * NF, 2, h, w, NF, st));
+            VFI_DO(r.conv(m->flow1, F[l], 2 * NF, h, w, CF, NF, 2, 0));
+            VFI_DO(r.copy(CF, NF, G, gcs, (long)hw, NF));
+            VFI_DO(r.copy(CF + hw * NF, NF, G + NF, gcs, (long)hw, NF));
+            VFI_DO(run_tower(r, m->flow2, G, gcs, h, w, tmp));
+            VFI_DO(vfi_axpby(tmp, 8, up, gcs, fl, 4, (long)hw, 4, 1.f, 1.f, st));
         }
         prev = fl;
     }
@@ -534,14 +496,14 @@ int xvfi_prepare(vfi_xvfi* m, const float* f0, const float* f1, int C, hipStream
     float* R = r.buf("refine_in", 1, h0, w0, 4 * NF + 8);
     if (r.bad) return -1;
     const size_t hw0 = (size_t)h0 * w0;
-    XV_DO(r.copy(F[0], 2 * NF, R, 4 * NF + 8, (long)hw0, NF));
-    XV_DO(r.copy(F[0] + hw0 * 2 * NF, 2 * NF, R + 3 * NF, 4 * NF + 8, (long)hw0, NF));
+    VFI_DO(r.copy(F[0], 2 * NF, R, 4 * NF + 8, (long)hw0, NF));
+    VFI_DO(r.copy(F[0] + hw0 * 2 * NF, 2 * NF, R + 3 * NF, 4 * NF + 8, (long)hw0, NF));
     return 0;
 }
 
 // per timestep: level 0 from the CFR on (VFInet.forward :183-226)
 int xvfi_render(vfi_xvfi* m, float t, float* out, hipStream_t st) {
-    Run r{m, st};
+    Run r{{m, st}};
     const int Hp = m->Hp, Wp = m->Wp, s = m->scale, h = Hp / s, w = Wp / s, rcs = 4 * NF + 8;
     const size_t hw = (size_t)h * w;
     const int cps = 256 / (s * s), ucs = cps + 16;
@@ -552,24 +514,24 @@ int xvfi_render(vfi_xvfi* m, float t, float* out, hipStream_t st) {
     float *T0 = r.buf("unet_t0", 1, Hp / 8, Wp / 8, 4 * NF), *T1 = r.buf("unet_t1", 1, Hp / 4, Wp / 4, 2 * NF), *T2 = r.buf("unet_t2", 1, Hp / 2, Wp / 2, NF);
     float *T3 = r.buf("unet_t3", 1, Hp, Wp, NF), *RO = r.buf("unet_out", 1, Hp, Wp, 8);
     if (r.bad) return -1;
-    XV_DO(vfi_xvfi_cfr(fl, 4, tmp + 4, 8, t, R + 4 * NF, rcs, bounds, h, w, st));
+    VFI_DO(vfi_xvfi_cfr(fl, 4, tmp + 4, 8, t, R + 4 * NF, rcs, bounds, h, w, st));
     // warped0 = bwarp(feat0, flow_t0) -> channels 64.., warped1 = bwarp(feat1, flow_t1) -> channels 128..
-    XV_DO(vfi_xvfi_bwarp(F0, 2 * NF, (int64_t)hw * 2 * NF, 0, R + 4 * NF, rcs, 2, R + NF, rcs, NF, 2, h, w, NF, st));
-    XV_DO(r.conv(m->flow3_in, R, rcs, h, w, c1, NF, 1, 1));
-    XV_DO(run_tower(r, m->flow3, c1, NF, h, w, FR, R + 4 * NF, rcs));
-    XV_DO(vfi_xvfi_bwarp(F0, 2 * NF, (int64_t)hw * 2 * NF, 0, FR, 8, 2, WF, NF, (int64_t)hw * NF, 2, h, w, NF, st));
-    XV_DO(vfi_xvfi_assemble(F0, 2 * NF, WF, NF, FR, 8, img, 8, U, ucs, h, w, s, st));
+    VFI_DO(vfi_xvfi_bwarp(F0, 2 * NF, (int64_t)hw * 2 * NF, 0, R + 4 * NF, rcs, 2, R + NF, rcs, NF, 2, h, w, NF, st));
+    VFI_DO(r.conv(m->flow3_in, R, rcs, h, w, c1, NF, 1, 1));
+    VFI_DO(run_tower(r, m->flow3, c1, NF, h, w, FR, R + 4 * NF, rcs));
+    VFI_DO(vfi_xvfi_bwarp(F0, 2 * NF, (int64_t)hw * 2 * NF, 0, FR, 8, 2, WF, NF, (int64_t)hw * NF, 2, h, w, NF, st));
+    VFI_DO(vfi_xvfi_assemble(F0, 2 * NF, WF, NF, FR, 8, img, 8, U, ucs, h, w, s, st));
     // RefineUNet (:436-453): the two concats are channel windows of D1 / D2 (decoder output first, encoder map behind)
-    XV_DO(r.conv(m->enc1, U, ucs, Hp, Wp, D2 + 2 * NF, 3 * NF, 1, 1));
-    XV_DO(r.conv(m->enc2, D2 + 2 * NF, 3 * NF, Hp / 2, Wp / 2, D1 + 4 * NF, 6 * NF, 1, 1));
-    XV_DO(r.conv(m->enc3, D1 + 4 * NF, 6 * NF, Hp / 4, Wp / 4, E3, 4 * NF, 1, 1));
-    XV_DO(r.conv(m->dec0, E3, 4 * NF, Hp / 8, Wp / 8, T0, 4 * NF, 1, 1));
-    XV_DO(r.up2(T0, 4 * NF, Hp / 8, Wp / 8, D1, 6 * NF, 4 * NF));
-    XV_DO(r.conv(m->dec1, D1, 6 * NF, Hp / 4, Wp / 4, T1, 2 * NF, 1, 1));
-    XV_DO(r.up2(T1, 2 * NF, Hp / 4, Wp / 4, D2, 3 * NF, 2 * NF));
-    XV_DO(r.conv(m->dec2, D2, 3 * NF, Hp / 2, Wp / 2, T2, NF, 1, 1));
-    XV_DO(r.up2(T2, NF, Hp / 2, Wp / 2, T3, NF, NF));
-    XV_DO(r.conv(m->dec3, T3, NF, Hp, Wp, RO, 8, 1, 0));
+    VFI_DO(r.conv(m->enc1, U, ucs, Hp, Wp, D2 + 2 * NF, 3 * NF, 1, 1));
+    VFI_DO(r.conv(m->enc2, D2 + 2 * NF, 3 * NF, Hp / 2, Wp / 2, D1 + 4 * NF, 6 * NF, 1, 1));
+    VFI_DO(r.conv(m->enc3, D1 + 4 * NF, 6 * NF, Hp / 4, Wp / 4, E3, 4 * NF, 1, 1));
+    VFI_DO(r.conv(m->dec0, E3, 4 * NF, Hp / 8, Wp / 8, T0, 4 * NF, 1, 1));
+    VFI_DO(r.up2(T0, 4 * NF, Hp / 8, Wp / 8, D1, 6 * NF, 4 * NF));
+    VFI_DO(r.conv(m->dec1, D1, 6 * NF, Hp / 4, Wp / 4, T1, 2 * NF, 1, 1));
+    VFI_DO(r.up2(T1, 2 * NF, Hp / 4, Wp / 4, D2, 3 * NF, 2 * NF));
+    VFI_DO(r.conv(m->dec2, D2, 3 * NF, Hp / 2, Wp / 2, T2, NF, 1, 1));
+    VFI_DO(r.up2(T2, NF, Hp / 2, Wp / 2, T3, NF, NF));
+    VFI_DO(r.conv(m->dec3, T3, NF, Hp, Wp, RO, 8, 1, 0));
     return vfi_xvfi_blend_out(RO, 8, U + cps + 6, ucs, t, out, Hp, Wp, m->H, m->W, st);
 }
 
@@ -579,7 +541,7 @@ int round_to(int n, int d) { return n + (d - n % d) % d; }
 
 extern "C" {
 
-int64_t vfi_xvfi_max_padded_pixels(void) { return ((1LL << 31) - 1) / (kPxFloats * 4); }
+int64_t vfi_xvfi_max_padded_pixels(void) { return max_padded_pixels(kPxFloats); }
 
 vfi_xvfi_t* vfi_xvfi_create(const float* const* tensors, const int64_t* numels, int n_tensors, int scale, int S_tst) {
     const bool known = (scale == 2 || scale == 4) && S_tst >= 0 && S_tst < kMaxLevels;
@@ -592,13 +554,7 @@ vfi_xvfi_t* vfi_xvfi_create(const float* const* tensors, const int64_t* numels, 
     vfi_xvfi* m = new vfi_xvfi();
     m->scale = scale, m->S = S_tst, m->nds = scale == 4 ? 2 : 1;
     TensorCursor cur(tensors, numels, n_tensors, "vfi_xvfi_create");
-    auto r8 = [](int c) { return (c + 7) & ~7; };
-    auto layer = [&](int cout, int cin, int k, int stride, int cin_phys = 0) -> vfi_conv_t* {
-        const float* w = cur.take((int64_t)cout * cin * k * k);
-        const float* b = cur.take(cout);
-        if (!cur.ok()) return nullptr;
-        return m->add_layer(vfi_conv_create_ex(0, w, b, cout, cin, k, stride, 0, nullptr, cin_phys ? cin_phys : r8(cin), nullptr));
-    };
+    auto layer = [&](int cout, int cin, int k, int stride) { return m->read_layer(cur, 0, cout, cin, k, stride, true, false); };
     // an aliased tensor of the state dict (one module registered twice): its numel is checked, its values are xvfi_spec's to compare
     auto alias = [&](int cout, int cin) {
         cur.take((int64_t)cout * cin * 9);
@@ -667,20 +623,15 @@ int vfi_xvfi_forward(vfi_xvfi_t* m, const float* frame0_dev, const float* frame1
     VFI_REQUIRE(t >= 0.f && t <= 1.f, "vfi_xvfi_forward: timestep %g outside [0, 1]", (double)t);
     const int divide = (1 << m->S) * m->scale * 4;
     const int Hp = round_to(H, divide), Wp = round_to(W, divide);
-    VFI_REQUIRE((int64_t)Hp * Wp <= vfi_xvfi_max_padded_pixels(),
-                "vfi_xvfi_forward: a %dx%d frame (padded %dx%d to multiples of %d) is over the size limit of %lld padded pixels: the widest buffer has %d "
-                "floats per padded pixel and the layers index an image with 32 bits", H, W, Hp, Wp, divide, (long long)vfi_xvfi_max_padded_pixels(), kPxFloats);
     hipStream_t st = (hipStream_t)stream;
-    if (m->ws.live() && (m->Hp != Hp || m->Wp != Wp || m->H != H || m->W != W)) {
-        m->have_pair = false;
-        if (m->ws.release()) return -1;
-    }
-    if (!m->ws.live()) m->have_pair = false;
-    m->H = H, m->W = W, m->Hp = Hp, m->Wp = Wp;
+    const int rc = m->enter("vfi_xvfi_forward", "XVFI", H, W, Hp, Wp, kPxFloats, m->H != H || m->W != W);
+    if (!m->ws.live()) m->have_pair = false;      // released just now, by the caller, or by a failed allocation
+    if (rc) return rc;
+    m->H = H, m->W = W;
     if (m->have_pair) {
         // the features, level flows and flow_l_tmp are kept while t varies: they are this pair's when both frames equal the padded copy bit
         // for bit (one pass over the frames and one stream synchronisation, against a third of the network)
-        Run r{m, st};
+        Run r{{m, st}};
         float *img = r.buf("img", 2, Hp, Wp, 8), *flag = r.buf("same_flag", 1, 1, 1, 4);
         if (r.bad) return -1;
         VFI_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
@@ -707,7 +658,7 @@ int vfi_xvfi_forward(vfi_xvfi_t* m, const float* frame0_dev, const float* frame1
 int vfi_xvfi_level0_flow(vfi_xvfi_t* m, float* out_dev, void* stream) {
     VFI_REQUIRE(m && out_dev, "vfi_xvfi_level0_flow: bad arguments");
     VFI_REQUIRE(m->have_pair && m->ws.live(), "vfi_xvfi_level0_flow: no forward has run since the workspace was released");
-    Run r{m, (hipStream_t)stream};
+    Run r{{m, (hipStream_t)stream}};
     const int h = m->Hp / m->scale, w = m->Wp / m->scale;
     float* tmp = r.buf("tmp0", 1, h, w, 8);
     if (r.bad) return -1;

@@ -1,4 +1,5 @@
-"""What the Python engines of the whole-network C objects share (FILM, M2M, CAIN, Sepconv, FLAVR; csrc/net_object.h is the C side).
+"""What the Python engines of the whole-network C objects share (FILM, M2M, CAIN, Sepconv, FLAVR, AMT, ATM, XVFI; csrc/net_object.h is
+the C side).
 
 A subclass names its entry points (``PREFIX``: ``vfi_cain`` -> vfi_cain_create / _destroy / _release_workspace ...), its node (``LABEL``)
 and its checkpoint layout (``shapes``), and writes its own forward.  Engines whose object reports its workspace size add
@@ -67,14 +68,23 @@ class WorkspaceBytes:
         return int(self._fn("workspace_bytes")(self.handle)) if getattr(self, "handle", None) else 0
 
 
-def frame_ptrs(frames):
-    """frames: a non-empty sequence of [H,W,C>=3] fp32 contiguous device tensors of one shape -> (host array of their device pointers,
-    (H, W, C))."""
-    assert len(frames) > 0
+def check_frames(*frames):
+    """The frames of one forward (a pair, a batch, a window): [H,W,C>=3] fp32 contiguous device tensors of one shape -> (H, W, C)."""
     H, W, Cc = frames[0].shape
     for f in frames:
         assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
-    return (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames]), (H, W, Cc)
+    return H, W, Cc
+
+
+def padded_to(n, d):
+    """InputPadder(dims, d) of the reference's models: n rounded up to a multiple of d"""
+    return n + (((n // d) + 1) * d - n) % d
+
+
+def frame_ptrs(frames):
+    """frames: a non-empty sequence of frames check_frames accepts -> (host array of their device pointers, (H, W, C))."""
+    assert len(frames) > 0
+    return (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames]), check_frames(*frames)
 
 
 class PairBatchEngine(WorkspaceBytes, NetEngine):

@@ -1,9 +1,11 @@
-"""The frame loop of the pair-at-a-time nodes (FILM, M2M, IFRNet, GMFSS, IFUNet, CAIN, Sepconv).
+"""The frame loop of the pair-at-a-time nodes (FILM, M2M, IFRNet, GMFSS, IFUNet, CAIN, Sepconv, AMT, ATM, XVFI).  Of the eight
+whole-network objects (netengine.py: FILM, M2M, CAIN, Sepconv, FLAVR, AMT, ATM, XVFI) all but FLAVR, whose forward takes a four-frame
+window (flavr.py), run their clips here.
 
 The reference walks the clip pair by pair (vfi_utils.generic_frame_loop, vfi_utils.py:149-389; film/__init__.py:63-113); the pairs are
 independent, so the tasks are block-partitioned over ranks and the new frames all-gathered.  What differs between the
-nodes is how one pair's new frames are computed — the ``pair_frames`` function each node passes in (film.film_pair, cain.eval_pair;
-m2m.run_plan binds m2m.timestep_pair); everything around it is here, once:
+nodes is how one pair's new frames are computed — the ``pair_frames`` function each node passes in (film.film_pair, cain.eval_pair,
+amt.pair_frames, atm.atm_pair, xvfi.xvfi_pair; m2m.run_plan binds m2m.timestep_pair); everything around it is here, once:
 
   * host side (hostpipe.py): every needed frame is uploaded once through pinned staging ahead of the compute streams; new frames and
     pass-through frames land in their final rows of the output tensor in the background;

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
-from .netengine import NetEngine, WorkspaceBytes
+from .netengine import NetEngine, WorkspaceBytes, check_frames
 from .nodeloop import run_plan
 from .schedule import InterpolationStateList, generic_output_plan
 from .xvfi_spec import CKPT_CONFIGS, check_state_dict, config_of, load_file, padded_size, xvfi_shapes
@@ -55,9 +55,7 @@ class XvfiEngine(WorkspaceBytes, NetEngine):
 
     def forward(self, frame0, frame1, t, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
-        H, W, Cc = frame0.shape
-        for f in (frame0, frame1):
-            assert f.shape == (H, W, Cc) and f.is_cuda and f.dtype == torch.float32 and f.is_contiguous(), "frames: [H,W,C] fp32 contiguous"
+        H, W, Cc = check_frames(frame0, frame1)
         check_frame_size(H, W, self.config)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)

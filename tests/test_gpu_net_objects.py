@@ -1,5 +1,5 @@
-"""-m gpu: what the five whole-network objects (FILM, M2M, CAIN, Sepconv, FLAVR) get from their shared base (csrc/net_object.h,
-netengine.py), on seeded weights.
+"""-m gpu: what the eight whole-network objects (FILM, M2M, CAIN, Sepconv, FLAVR, AMT, ATM, XVFI) get from their shared base
+(csrc/net_object.h, netengine.py), on seeded weights.
 
 Malformed checkpoints are refused by host-side argument validation, not read: a wrong tensor count, a wrong element count in the LAST
 tensor (every earlier layer exists by then and the failed create must tear it down), a null tensor pointer in the middle.
@@ -7,7 +7,9 @@ tensor (every earlier layer exists by then and the failed create must tear it do
 Workspace lifecycle: forward at shape A, at B, at A again, release, A once more — the three A frames are bit-equal.  The re-allocation at A
 after B is where a lost zero fill would show (FILM and M2M read zero channel padding, FLAVR zero borders).  The shapes are the smallest
 that reach every branch: FILM's 7-level minimum of 64; M2M padded to 128x128 / 64x128; CAIN two padded sizes with reflection on both
-axes; Sepconv odd rows (the cropped residual add) / even ones; FLAVR padded 48x64 / 64x80."""
+axes; Sepconv odd rows (the cropped residual add) / even ones; FLAVR padded 48x64 / 64x80; AMT-S 120x136 (padded 128x144, top and left
+4: its 128-pixel minimum side binds) / 128x160; ATM-lite 40x100 (padded 64x128) / 64x64; XVFI (2, 1) 40x56 (padded bottom / right to
+48x64) / 64x80, whose second and third run at A go through the kept-pair path."""
 import ctypes as C
 from collections import namedtuple
 
@@ -16,8 +18,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-Net = namedtuple("Net", "engine state_dict keys create_args frames run shape_a shape_b")
-NAMES = ["film", "m2m", "cain", "sepconv", "flavr"]
+# create: the raw create entry point where it is not PREFIX_create; engine_args: what the engine takes after the state dict
+Net = namedtuple("Net", "engine state_dict keys create_args frames run shape_a shape_b create engine_args", defaults=(None, ()))
+NAMES = ["film", "m2m", "cain", "sepconv", "flavr", "amt", "atm", "xvfi"]
 
 
 def _net(name):
@@ -44,6 +47,23 @@ def _net(name):
         from cfi_amd.sepconv_spec import seeded_state_dict, sepconv_shapes
 
         return Net(SepconvEngine, seeded_state_dict(1), list(sepconv_shapes()), (), 2, pair, (67, 99), (64, 96))
+    if name == "amt":
+        from cfi_amd.amt import AmtEngine
+        from cfi_amd.amt_spec import amt_shapes, seeded_state_dict
+
+        return Net(AmtEngine, seeded_state_dict("S", 1), list(amt_shapes("S")), (0,), 2, lambda e, f: e.forward(f[0], f[1], [0.5])[0], (120, 136), (128, 160))
+    if name == "atm":
+        from cfi_amd.atm import AtmEngine
+        from cfi_amd.atm_spec import seeded_state_dict, weight_shapes
+
+        return Net(AtmEngine, seeded_state_dict(1), list(weight_shapes("lite")), (0,), 2, lambda e, f: e.forward(f[0], f[1]), (40, 100), (64, 64),
+                   create="vfi_atm_create_variant")
+    if name == "xvfi":
+        from cfi_amd.xvfi import XvfiEngine
+        from cfi_amd.xvfi_spec import seeded_state_dict, xvfi_shapes
+
+        return Net(XvfiEngine, seeded_state_dict((2, 1), 1), list(xvfi_shapes(2)), (2, 1), 2, lambda e, f: e.forward(f[0], f[1], 0.5), (40, 56), (64, 80),
+                   engine_args=((2, 1),))
     from cfi_amd.flavr import FlavrEngine
     from cfi_amd.flavr_spec import flavr_shapes, seeded_state_dict
 
@@ -71,7 +91,7 @@ def test_malformed_checkpoint_is_refused(hip_lib, nets, name):
 
     net = nets(name)
     prefix = net.engine.PREFIX
-    create, destroy = getattr(hip_lib, prefix + "_create"), getattr(hip_lib, prefix + "_destroy")
+    create, destroy = getattr(hip_lib, net.create or prefix + "_create"), getattr(hip_lib, prefix + "_destroy")
     tensors = [net.state_dict[k].detach().to("cpu", torch.float32).contiguous() for k in net.keys]
     n = len(tensors)
 
@@ -100,7 +120,7 @@ def test_workspace_lifecycle(nets, name):
     net = nets(name)
     fa = synth.texture_frames(net.frames, *net.shape_a, seed=3).cuda()
     fb = synth.texture_frames(net.frames, *net.shape_b, seed=4).cuda()
-    eng = net.engine(net.state_dict)
+    eng = net.engine(net.state_dict, *net.engine_args)
     try:
         reports = hasattr(eng, "workspace_bytes")
         assert reports == (name != "film"), "FILM's object reports no workspace size (ckpt.end_call then always releases it)"

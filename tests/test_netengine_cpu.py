@@ -119,16 +119,38 @@ def test_failed_status_raises_with_the_entry_point_name(fake):
 
 
 def test_which_engines_report_their_workspace():
+    from cfi_amd.amt import AmtEngine
+    from cfi_amd.atm import AtmEngine
     from cfi_amd.cain import CainEngine
     from cfi_amd.film import FilmEngine
     from cfi_amd.flavr import FlavrEngine
     from cfi_amd.m2m import M2MEngine
     from cfi_amd.sepconv import SepconvEngine
+    from cfi_amd.xvfi import XvfiEngine
 
     assert not hasattr(FilmEngine, "workspace_bytes")      # ckpt.end_call: hasattr -> FILM's 15 GB are released after every call
-    for cls in (M2MEngine, CainEngine, SepconvEngine, FlavrEngine):
+    for cls in (M2MEngine, CainEngine, SepconvEngine, FlavrEngine, AmtEngine, AtmEngine, XvfiEngine):
         assert hasattr(cls, "workspace_bytes") and issubclass(cls, netengine.NetEngine)
     assert FilmEngine.__del__ is netengine.NetEngine.__del__
+
+
+def test_frame_pair_check(monkeypatch):
+    """check_frames, behind frame_ptrs and the AMT / ATM / XVFI forwards: a mismatched shape, a non-fp32 and a non-contiguous frame raise;
+    so does a host tensor (the is_cuda leg, the only one a machine without a GPU reaches with real tensors); with that leg answered, a
+    good pair gives (H, W, C) and each of the other legs still fires."""
+    good = torch.zeros(4, 6, 3)
+    text = r"frames: \[H,W,C\] fp32 contiguous"
+    with pytest.raises(AssertionError, match=text):
+        netengine.check_frames(good, good)                  # host tensors: is_cuda
+    with pytest.raises(AssertionError, match=text):
+        netengine.frame_ptrs([good])
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+    assert netengine.check_frames(good, good.clone()) == (4, 6, 3)
+    assert netengine.frame_ptrs([good, good])[1] == (4, 6, 3)
+    for bad in (torch.zeros(4, 5, 3), good.double(), torch.zeros(4, 6, 6)[..., ::2]):
+        assert bad.shape != good.shape or bad.dtype != torch.float32 or not bad.is_contiguous()
+        with pytest.raises(AssertionError, match=text):
+            netengine.check_frames(good, bad)
 
 
 def test_m2m_release_workspace_forgets_the_prepared_pair(fake):
