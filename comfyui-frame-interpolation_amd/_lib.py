@@ -271,6 +271,9 @@ PROTOTYPES = {
     "vfi_xvfi_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "vfi_xvfi_level0_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vfi_xvfi_max_padded_pixels": (C.c_int64, []),
+    "vfi_xvfi_large_max_padded_pixels": (C.c_int64, []),
+    "vfi_xvfi_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
+    "vfi_xvfi_set_large_frames": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_xvfi_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_xvfi_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_m2m_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),

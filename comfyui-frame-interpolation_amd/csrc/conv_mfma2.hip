@@ -69,13 +69,19 @@ struct Conv2Geom {
 // floats [h] and [2 + h] of the pixel's chunk and of the weight row, i.e. the channel pairs (0|1), (2|3) — the live terms of the
 // plain form's (0|4), (1|5), (2|6), (3|7) in the same order, without its four fma(x, 0, acc).  DMA, LDS image and epilogue are the
 // plain form's.
-template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false>
+// LARGE (plain NHWC layers, zero padding): the input image holds 2 GiB or more (below 4 GiB), so a byte offset from the image's start no
+// longer fits the 31 bits the descriptor's range check leaves.  The descriptor is rebased per tile instead: its base is the first input
+// row the tile's halo touches (a 64-bit, wave-uniform address), its size the rows the halo spans, and the per-lane offsets count from
+// that row — a few rows of bytes, whatever the image.  Same pieces, same LDS image, same arithmetic: same bits as the plain form wherever
+// both are legal.  The output side needs nothing: the epilogue forms 64-bit addresses already.
+template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false, bool LARGE = false>
 __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource / LDS-DMA builtins do not exist in the host pass
     using G = Conv2Geom<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED>;
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(!GROUPED || (WN == 4 && NT == 1 && TAPS == 4), "grouped: one 2x2 tap group per wave column");
     static_assert(!TAIL4 || (STRIDE == 2 && TAPS == 9 && CK == 8 && !GROUPED && !MASKED), "live-K tail: stride-2 3x3, 8-channel chunks");
+    static_assert(!LARGE || (!GROUPED && !EXT && !MASKED && !TAIL4), "large images: the plain feature set only");
     constexpr int KW = G::KW, SUBX = G::SUBX, TWO = G::TWO, THO = G::THO, TWI = G::TWI;
     constexpr int Q = G::Q, C8 = G::C8, BN = G::BN;
 
@@ -111,6 +117,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
     // activation DMA: voffset per 16-byte piece inside the image; out-of-image halo -> out of range -> zero fill
     auto make_avoff = [&](int Y0, int X0, int(&avoff)[G::NAW]) {
         const int iy0 = STRIDE * Y0 - G::PADLO, ix0 = STRIDE * X0 - G::PADLO;
+        const int r0 = LARGE ? (iy0 > 0 ? iy0 : 0) : 0;      // the row the tile's descriptor starts at (make_rsrc)
 #pragma unroll
         for (int i = 0; i < G::NAW; ++i) {
             const int j = wave + 4 * i;
@@ -123,12 +130,18 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
                 avoff[i] = pix < G::NPIX ? ((cy * a.Win + cx) * pstr + q * qstr) * 4 : (int)0x80000000;
             } else {
                 const bool ok = pix < G::NPIX && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
-                avoff[i] = ok ? ((iy * a.Win + ix) * pstr + q * qstr) * 4 : (int)0x80000000;
+                avoff[i] = ok ? (((iy - r0) * a.Win + ix) * pstr + q * qstr) * 4 : (int)0x80000000;
             }
         }
     };
-    auto make_rsrc = [&](int n) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, img_floats * 4, 0x00020000);
+    auto make_rsrc = [&](int n, int Y0) {
+        if constexpr (LARGE) {
+            const int iy0 = STRIDE * Y0 - G::PADLO, r0 = iy0 > 0 ? iy0 : 0;
+            const int rows = a.Hin - r0 < G::THI ? a.Hin - r0 : G::THI;
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats + (size_t)r0 * a.Win * a.in_cs), 0, rows * a.Win * a.in_cs * 4, 0x00020000);
+        } else {
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, img_floats * 4, 0x00020000);
+        }
     };
     // weight DMA: per-lane source pointers of this wave's pieces (tile- and chunk-invariant part)
     const unsigned tmask = MASKED ? a.tapmask[blockIdx.y] : 0xffffu;
@@ -201,7 +214,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
     int n, Y0, X0, avoff[G::NAW];
     decode(tile, n, Y0, X0);
     make_avoff(Y0, X0, avoff);
-    __amdgpu_buffer_rsrc_t rsrc = make_rsrc(n);
+    __amdgpu_buffer_rsrc_t rsrc = make_rsrc(n, Y0);
     issue(rsrc, avoff, k0, 0);
     __syncthreads();  // LDS-DMA counts on vmcnt: the barrier's release drains it
     int buf = 0;
@@ -227,7 +240,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
             } else if (has_next) {
                 decode(ntile, nn, nY0, nX0);
                 make_avoff(nY0, nX0, navoff);
-                nrsrc = make_rsrc(nn);
+                nrsrc = make_rsrc(nn, nY0);
                 issue(nrsrc, navoff, k0, buf ^ 1);
             }
             const float* sb = smem + buf * G::BUF_FLOATS;
@@ -561,7 +574,7 @@ static int split_reduce(const ConvArgs& a, const float* ws, int ks, size_t slice
     return 0;
 }
 
-template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false>
+template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false, bool LARGE = false>
 static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     using G = Conv2Geom<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED>;
     a.ksplit = 0, a.split_stride = 0;      // launcher-owned fields (callers do not set them)
@@ -569,7 +582,12 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     a.tiles_y = cdiv(a.Hout, G::THO);
     VFI_REQUIRE(a.Cin_p % CK == 0, "conv2 %s: Cin_p=%d not a multiple of the K chunk %d", name, a.Cin_p, CK);
     VFI_REQUIRE(a.Cout_p % G::BN == 0, "conv2 %s: Cout_p=%d not a multiple of the N tile %d", name, a.Cout_p, G::BN);
-    VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
+    if (LARGE) {      // the per-tile descriptor: the whole image below 4 GiB, the rows of one tile's halo below 2 GiB
+        VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 <= 0xffffffffL && !a.in_plane && !a.pad_mode && (long)G::THI * a.Win * a.in_cs * 4 < 0x7fffffffL,
+                    "conv2 %s: image larger than 2 GiB", name);
+    } else {
+        VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
+    }
     VFI_REQUIRE(!a.in_plane || a.in_plane >= a.Hin * a.Win * 4, "conv2 %s: bad plane stride", name);
     VFI_REQUIRE(!TAIL4 || a.cin_live == a.Cin_p - 4, "conv2 %s: the live-K tail needs 4 live channels in the last chunk (Cin %d of %d)", name, a.cin_live, a.Cin_p);
     // resident workgroups per CU of this instantiation and the CU count, PER DEVICE: one process may drive several
@@ -582,11 +600,11 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     int occ = occ_of[dev].load(std::memory_order_acquire);
     if (!occ) {
         VFI_CHECK_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>),
+            reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, LARGE>),
             hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
         int o = 0;
         VFI_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &o, reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), 256,
+            &o, reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, LARGE>), 256,
             G::LDS_BYTES));
         hipDeviceProp_t p;
         VFI_CHECK_HIP(hipGetDeviceProperties(&p, dev));
@@ -632,11 +650,11 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         p.out = ws, p.out_cs = a.Cout_p, p.bias = zeros, p.beta = nullptr, p.res = nullptr, p.res_cs = 0;
         p.act = 0, p.post_scale = 0.f, p.post_shift = 0.f, p.Cout = a.Cout_p;
         p.ksplit = ks, p.split_stride = (long)slice;
-        conv_record_launch(kConvFamilyGen2, 0, MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, ks, T, T);
+        conv_record_launch(kConvFamilyGen2, 0, LARGE ? 3 : MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, ks, T, T);
         {
             TraceScope ts(name, s);
             // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_mode implies EXT)
-            hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), dim3(T, ny, ks), dim3(256), G::LDS_BYTES, s, p);
+            hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, LARGE>), dim3(T, ny, ks), dim3(256), G::LDS_BYTES, s, p);
             VFI_CHECK_HIP(hipGetLastError());
         }
         return split_reduce(a, ws, ks, slice, s);
@@ -649,9 +667,9 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     if (gx > T || (long)T * ny < 4L * cus * occ) gx = T;
     if (MASKED) gx = T;      // N blocks carry 1, 2, 2 or 4 taps: one workgroup per tile, the dispatcher balances them
     dim3 grid(gx, ny);
-    conv_record_launch(kConvFamilyGen2, 0, MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, 1, gx, T);
+    conv_record_launch(kConvFamilyGen2, 0, LARGE ? 3 : MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, 1, gx, T);
     TraceScope ts(name, s);
-    hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4>), grid, dim3(256), G::LDS_BYTES, s, a);
+    hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, LARGE>), grid, dim3(256), G::LDS_BYTES, s, a);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -675,6 +693,16 @@ static int launch2_t(const ConvArgs& a, hipStream_t s, const char* name) {
     const bool ext = a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
     return ext ? launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, true>(a, s, name)
                : launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, false>(a, s, name);
+}
+
+// The tiles conv_pick_variant gives the plain layer forms (3x3 stride 1 / 2, 2x2 and 1x1 stride 1) also exist in the LARGE form.  It is
+// taken only from the size on (conv_input_large: 2 GiB, or what the test option large_image_bytes says); every smaller launch takes
+// launch2_t as before.  Layers with the extended feature set and every other tile keep the plain form and its 2 GiB guard.
+template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK>
+static int launch2_tl(const ConvArgs& a, hipStream_t s, const char* name) {
+    const bool ext = a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
+    if (!ext && !a.in_plane && conv_input_large(a)) return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, false, false, false, true>(a, s, name);
+    return launch2_t<STRIDE, TAPS, MT, NT, WM, WN, CK, false>(a, s, name);
 }
 
 // second-generation variants, numbered from kConv2Base in the common variant space
@@ -723,36 +751,36 @@ const ConvVariant& conv2_variant(int i) { return i < kNumVariants2 ? kVariants2[
 
 int conv2_launch(const ConvArgs& a, int idx, hipStream_t s, const char* nm) {
     switch (idx) {
-        case 0: return launch2_t<1, 9, 2, 2, 4, 1, 8, false>(a, s, nm);
+        case 0: return launch2_tl<1, 9, 2, 2, 4, 1, 8>(a, s, nm);
         case 1: return launch2_t<1, 9, 2, 3, 4, 1, 8, false>(a, s, nm);
-        case 2: return launch2_t<1, 9, 1, 2, 4, 1, 8, false>(a, s, nm);
-        case 3: return launch2_t<1, 9, 1, 3, 4, 1, 8, false>(a, s, nm);
+        case 2: return launch2_tl<1, 9, 1, 2, 4, 1, 8>(a, s, nm);
+        case 3: return launch2_tl<1, 9, 1, 3, 4, 1, 8>(a, s, nm);
         case 4: return launch2_t<1, 9, 2, 2, 2, 2, 8, false>(a, s, nm);
         case 5: return launch2_t<1, 9, 4, 2, 2, 2, 8, false>(a, s, nm);
         case 6: return launch2_t<1, 9, 2, 2, 4, 1, 16, false>(a, s, nm);
-        case 7: return launch2_t<2, 9, 1, 2, 4, 1, 8, false>(a, s, nm);
+        case 7: return launch2_tl<2, 9, 1, 2, 4, 1, 8>(a, s, nm);
         case 8: return launch2_t<2, 9, 2, 2, 4, 1, 8, false>(a, s, nm);
-        case 9: return launch2_t<2, 9, 1, 3, 4, 1, 8, false>(a, s, nm);
+        case 9: return launch2_tl<2, 9, 1, 3, 4, 1, 8>(a, s, nm);
         case 10: return launch2_t<2, 9, 2, 1, 4, 1, 8, false>(a, s, nm);
         case 11: return launch2_t<1, 4, 4, 1, 1, 4, 8, true>(a, s, nm);
         case 12: return launch2_t<1, 4, 8, 1, 1, 4, 8, true>(a, s, nm);
-        case 13: return launch2_t<1, 9, 2, 1, 4, 1, 8, false>(a, s, nm);
-        case 14: return launch2_t<1, 4, 2, 2, 4, 1, 8, false>(a, s, nm);
-        case 15: return launch2_t<1, 4, 1, 2, 4, 1, 8, false>(a, s, nm);
-        case 16: return launch2_t<1, 1, 2, 2, 4, 1, 8, false>(a, s, nm);
-        case 17: return launch2_t<1, 1, 1, 2, 4, 1, 8, false>(a, s, nm);
-        case 18: return launch2_t<1, 1, 2, 1, 4, 1, 8, false>(a, s, nm);
-        case 19: return launch2_t<1, 4, 2, 1, 4, 1, 8, false>(a, s, nm);
+        case 13: return launch2_tl<1, 9, 2, 1, 4, 1, 8>(a, s, nm);
+        case 14: return launch2_tl<1, 4, 2, 2, 4, 1, 8>(a, s, nm);
+        case 15: return launch2_tl<1, 4, 1, 2, 4, 1, 8>(a, s, nm);
+        case 16: return launch2_tl<1, 1, 2, 2, 4, 1, 8>(a, s, nm);
+        case 17: return launch2_tl<1, 1, 1, 2, 4, 1, 8>(a, s, nm);
+        case 18: return launch2_tl<1, 1, 2, 1, 4, 1, 8>(a, s, nm);
+        case 19: return launch2_tl<1, 4, 2, 1, 4, 1, 8>(a, s, nm);
         case 20: return launch2_t<2, 4, 2, 1, 4, 1, 8, false>(a, s, nm);
         case 21: return launch2_t<2, 4, 1, 2, 4, 1, 8, false>(a, s, nm);
         case 22: return launch2_t<1, 9, 4, 2, 4, 1, 8, false>(a, s, nm);
-        case 23: return launch2_t<1, 1, 1, 2, 4, 1, 32, false>(a, s, nm);
-        case 24: return launch2_t<1, 1, 2, 2, 2, 2, 32, false>(a, s, nm);
+        case 23: return launch2_tl<1, 1, 1, 2, 4, 1, 32>(a, s, nm);
+        case 24: return launch2_tl<1, 1, 2, 2, 2, 2, 32>(a, s, nm);
         case 25: return launch2_masked<1, 4, 2, 2, 4, 1, 8>(a, s, nm);
         case 26: return launch2_masked<1, 4, 1, 2, 4, 1, 8>(a, s, nm);
         case 27: return launch2_masked<1, 4, 2, 2, 4, 1, 16>(a, s, nm);
         case 28: return launch2_masked<1, 4, 1, 2, 4, 1, 16>(a, s, nm);
-        case 29: return launch2_t<1, 9, 1, 1, 4, 1, 8, false>(a, s, nm);
+        case 29: return launch2_tl<1, 9, 1, 1, 4, 1, 8>(a, s, nm);
         case 30: return launch2_tail<1, 2>(a, s, nm);
     }
     set_error("conv2: bad variant %d", idx);

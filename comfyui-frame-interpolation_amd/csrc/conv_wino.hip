@@ -158,7 +158,9 @@ __device__ __forceinline__ f32x2 wino_pk_mul(f32x2 x, f32x2 y) {
 //     of conv_mfma2's out_mode 1 epilogue;
 //   2 (out_mode 2, the layer objects of M2M / IFRNet / IFUNet / GMFSS): NHWC [n][2H][2W][out_cs], pixel (2 oy + (g >> 1), 2 ox + (g & 1)),
 //     channel cg.  No residual in either form.
-template <int RTX, int MODE, bool FULL = false, int SHUF = 0>
+// LARGE (SHUF 0): an output / residual image of 2 GiB or more — the descriptors start at the region's first row and span the region's rows
+// (64-bit, wave-uniform base), so the row part of every offset counts from there and stays small; the same stores in the same order.
+template <int RTX, int MODE, bool FULL = false, int SHUF = 0, bool LARGE = false>
 __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const ConvArgs& a, int n, int oy0, int ox0, int co, int coc, int half, float bs,
                                               float bt, float pre, int LO = 0, float inv_LO = 0.f, int gray = 0) {
     const int H = a.Hin, W = a.Win;
@@ -166,13 +168,17 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
     const float ps = a.post_scale != 0.f ? a.post_scale : 1.0f, sh = a.post_scale != 0.f ? a.post_shift : 0.0f;
     const int planes = a.out_planes ? a.out_planes : 2;
     const int Ws4 = 4 * W;                       // SHUF: T row length in pixels
+    static_assert(!LARGE || SHUF == 0, "large images: NHWC stores only");
+    const int lrows = H - oy0 < 2 * (32 / RTX) ? H - oy0 : 2 * (32 / RTX);      // LARGE: the rows of the region that exist
     const __amdgpu_buffer_rsrc_t orsrc =
+        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + ((size_t)n * H + oy0) * W * a.out_cs), 0, lrows * W * a.out_cs * 4, 0x00020000) :
         SHUF == 1 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * planes * 16 * H * W * 4), 0, planes * 16 * H * W * 16, 0x00020000)
         : SHUF == 2 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * 4 * H * W * a.out_cs), 0, 4 * H * W * a.out_cs * 4, 0x00020000)
                     : __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * H * W * a.out_cs), 0, H * W * a.out_cs * 4, 0x00020000);
     const bool has_res = MODE >= 10 && a.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(has_res ? a.res + (size_t)n * H * W * a.res_cs : a.out), 0, has_res ? H * W * a.res_cs * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc =
+        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? a.res + ((size_t)n * H + oy0) * W * a.res_cs : a.out), 0, has_res ? lrows * W * a.res_cs * 4 : 0, 0x00020000)
+              : __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? a.res + (size_t)n * H * W * a.res_cs : a.out), 0, has_res ? H * W * a.res_cs * 4 : 0, 0x00020000);
     const int xlane = ox0 + 8 * half;          // this lane's first output column; + xq per store
     const bool cok = co < a.Cout;
     const bool interior = FULL || ox0 + 2 * RTX <= W;  // every column of the region is inside the image (wave-uniform)
@@ -222,7 +228,8 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
         for (int ey = 0; ey < 2; ++ey) {
             const int oy = oy0 + 2 * tyy + ey;          // wave-uniform
             if (FULL || oy < H) {
-                const int rowo = SHUF == 1 ? oy * 4 * Ws4 * 16 : (SHUF == 2 ? oy * 4 * W * a.out_cs * 4 : oy * W * a.out_cs * 4), rowr = oy * W * a.res_cs * 4;
+                const int oyr = LARGE ? oy - oy0 : oy;      // the row the descriptors count from
+                const int rowo = SHUF == 1 ? oy * 4 * Ws4 * 16 : (SHUF == 2 ? oy * 4 * W * a.out_cs * 4 : oyr * W * a.out_cs * 4), rowr = oyr * W * a.res_cs * 4;
 #pragma unroll
                 for (int ex = 0; ex < 2; ++ex) {
                     f32x2 v2 = wino_pk_mul_hi(wino_pk_add_lo(y[ey * 2 + ex], bsbt), bsbt);
@@ -256,7 +263,10 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
     }
 }
 
-template <int RTX, int MODE, int SHUF = 0, int PROBE = 0>
+// LARGE: an input, output or residual image of 2 GiB or more (below 4 GiB).  The activation descriptor is rebased per work item on the
+// first input row the region's patch touches and spans the patch's rows, the cursor's offsets count from that row; the epilogue likewise
+// (wino_epilogue).  Pieces, LDS images, K order and arithmetic are the plain kernel's: the same bits wherever both are legal.
+template <int RTX, int MODE, int SHUF = 0, int PROBE = 0, bool LARGE = false>
 __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool EXT = MODE >= 10;     // a general epilogue (wino_epilogue's MODE 10 + act): one kernel per activation, no switch in the item loop
@@ -338,6 +348,7 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
     int* const avtab = (int*)(smem + G::NBUF * G::BUF_FLOATS) + wave * (NA * 64);
     auto make_avoff = [&](const Cur& c) {
         const int ol = opaque_lane();
+        const int r0 = LARGE ? (c.Ry0 > 0 ? c.Ry0 - 1 : 0) : 0;      // the row the item's descriptor starts at (make_arsrc)
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int sp = i * 64 + ol;                      // swizzled slot = where the DMA puts this lane's 16 bytes
@@ -347,7 +358,7 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
             const int iy = c.Ry0 - 1 + py, ix = c.Rx0 - 1 + ((sl >> 1) - py * PW);
             const int cy = pad_index(iy, H, a.pad_mode), cx = pad_index(ix, W, a.pad_mode);   // replicate: edge clamp, reflect: mirror
             const bool ok = code >= 0 && c.valid && (a.pad_mode || (cy == iy && cx == ix));
-            avtab[i * 64 + ol] = ok ? ((cy * W + cx) * a.in_cs + (code & 1) * 4) * 4 : (int)0x80000000;
+            avtab[i * 64 + ol] = ok ? (((cy - r0) * W + cx) * a.in_cs + (code & 1) * 4) * 4 : (int)0x80000000;
         }
     };
     // One DMA piece per call: the K loop spreads a chunk's pieces over its MFMA groups (ten in a row back up the texture
@@ -414,10 +425,16 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
     auto make_wrsrc = [&](bool live) {
         return __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, live ? 16 * a.Cin_p * a.Cout_p * 4 : 0, 0x00020000);
     };
-    auto make_arsrc = [&](int n, bool live) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, live ? img_floats * 4 : 0, 0x00020000);
+    auto make_arsrc = [&](int n, int Ry0, bool live) {
+        if constexpr (LARGE) {
+            const int r0 = Ry0 > 0 ? Ry0 - 1 : 0;
+            const int rows = H - r0 < G::PH ? H - r0 : G::PH;
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats + (size_t)r0 * W * a.in_cs), 0, live ? rows * W * a.in_cs * 4 : 0, 0x00020000);
+        } else {
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, live ? img_floats * 4 : 0, 0x00020000);
+        }
     };
-    __amdgpu_buffer_rsrc_t drsrc = make_arsrc(dcur.n, true), dwrsrc = make_wrsrc(true);
+    __amdgpu_buffer_rsrc_t drsrc = make_arsrc(dcur.n, dcur.Ry0, true), dwrsrc = make_wrsrc(true);
     auto dma_issue_all = [&](int buf) {       // prologue: a whole chunk at once
         int av[NA];
         load_avoff(av);
@@ -433,7 +450,7 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
             d_k = 0;
             d_ok = item(++d_it, dcur);
             if (d_ok) make_avoff(dcur);
-            drsrc = make_arsrc(d_ok ? dcur.n : 0, d_ok);
+            drsrc = make_arsrc(d_ok ? dcur.n : 0, d_ok ? dcur.Ry0 : 0, d_ok);
             dwrsrc = make_wrsrc(d_ok);
             if (!d_ok) dcur.nb = 0;
         }
@@ -661,9 +678,9 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
                 const int co = ccur.nb * 32 + (ole & 31);
                 const int coc = co < a.Cout ? co : a.Cout - 1;
                 if (ccur.Ry0 + RH <= H && ccur.Rx0 + RW <= W)
-                    wino_epilogue<RTX, MODE, true, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
+                    wino_epilogue<RTX, MODE, true, SHUF, LARGE>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
                 else
-                    wino_epilogue<RTX, MODE, false, SHUF>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
+                    wino_epilogue<RTX, MODE, false, SHUF, LARGE>(acc, a, ccur.n, ccur.Ry0, ccur.Rx0, co, coc, half, cst[co], cst[G::MAXCO + co], cst[2 * G::MAXCO + co], p.LO, p.inv_LO, p.gray);
             }
             if (PROBE == 3) {
                 WINO_STAMP(true, sd);
@@ -852,6 +869,18 @@ static int wino_cus(int dev) {
     return c;
 }
 
+// Large images: an operand (input, output, residual) of one image at or over the mark (conv_bytes_large).  The LARGE instantiations exist
+// for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual, and operands below 4 GiB.
+static long wino_operand_bytes(const ConvArgs& a) {
+    const long px = (long)a.Hin * a.Win;
+    const long m = (a.in_cs > a.out_cs ? a.in_cs : a.out_cs);
+    return px * 4 * (a.res && a.res_cs > m ? a.res_cs : m);
+}
+static bool wino_large(const ConvArgs& a) { return a.out_mode == 0 && conv_bytes_large(wino_operand_bytes(a)); }
+static bool wino_large_ok(const ConvArgs& a) {
+    return wino_operand_bytes(a) <= 0xffffffffL && !a.pad_mode && !a.in_plane && a.act >= 0 && a.act <= 2 && a.post_scale == 0.f;
+}
+
 // Is the Winograd kernel the better choice for this layer on this launch?  (3x3 stride 1 only; enough work items to fill the
 // chip — coarse pyramid levels with long K stay on the direct kernel's split-K path.)
 bool conv_wino_eligible(const ConvArgs& a) {
@@ -859,8 +888,14 @@ bool conv_wino_eligible(const ConvArgs& a) {
     if (mode == 1) return false;
     if (a.ntaps != 9 || a.Hout != a.Hin || a.Wout != a.Win || a.in_plane || a.out_mode != 0) return false;
     if (a.Cin_p % 8 || a.Cout_p % 32 || a.Cout_p > 1024) return false;
-    if ((long)a.Hin * a.Win * a.in_cs * 4 >= 0x7fffffffL || (long)a.Hin * a.Win * a.out_cs * 4 >= 0x7fffffffL) return false;
-    if (a.res && (long)a.Hin * a.Win * a.res_cs * 4 >= 0x7fffffffL) return false;
+    // a launch the direct kernel serves today keeps it: only an input at or over the mark (which both kernels used to refuse) opens the
+    // LARGE form; a small input with an output of 2 GiB or more stays where it was, on the direct kernel's 64-bit stores
+    if (!conv_input_large(a)) {
+        if ((long)a.Hin * a.Win * a.in_cs * 4 >= 0x7fffffffL || (long)a.Hin * a.Win * a.out_cs * 4 >= 0x7fffffffL) return false;
+        if (a.res && (long)a.Hin * a.Win * a.res_cs * 4 >= 0x7fffffffL) return false;
+    } else if (!wino_large_ok(a)) {
+        return false;
+    }
     if (mode == 2) return true;
     // decided from the IMAGE, never from the launch's batch (the two kernels sum in different orders: a frame's bits must not depend
     // on its launch mates): work items of a nominal two-image launch — what FILM / M2M / IFRNet / GMFSS issue per pair
@@ -882,7 +917,7 @@ bool conv_wino_eligible(const ConvArgs& a) {
     return true;
 }
 
-template <int RTX, int MODE, int SHUF = 0, int PROBE = 0>
+template <int RTX, int MODE, int SHUF = 0, int PROBE = 0, bool LARGE = false>
 static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     using G = WinoGeom<RTX>;
     ConvArgs& a = p.a;
@@ -900,7 +935,7 @@ static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     VFI_REQUIRE(dev >= 0 && dev < kMaxDevices, "conv_wino %s: device index %d out of range", name, dev);
     static std::atomic<int> attr_set[kMaxDevices];
     if (!attr_set[dev].load(std::memory_order_acquire)) {
-        VFI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<RTX, MODE, SHUF, PROBE>),
+        VFI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<RTX, MODE, SHUF, PROBE, LARGE>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
         attr_set[dev].store(1, std::memory_order_release);
     }
@@ -910,9 +945,9 @@ static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     grid = round_up(grid, 8);
     p.xcd_map = option(kOptWinoXcd) ? 1 : 0;
     p.clk_tag = clock_probe_tag(name);
-    conv_record_launch(kConvFamilyWino, RTX, MODE, SHUF, 1, grid, items);
+    conv_record_launch(kConvFamilyWino, RTX, MODE, LARGE ? 3 : SHUF, 1, grid, items);
     TraceScope ts(name, s);
-    hipLaunchKernelGGL((conv_wino_kernel<RTX, MODE, SHUF, PROBE>), dim3(grid), dim3(256), G::LDS_BYTES, s, p);
+    hipLaunchKernelGGL((conv_wino_kernel<RTX, MODE, SHUF, PROBE, LARGE>), dim3(grid), dim3(256), G::LDS_BYTES, s, p);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -924,7 +959,8 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
     VFI_REQUIRE(a.Cin_p % 8 == 0 && a.Cout_p % 32 == 0 && a.Cout_p <= 1024 && a.in_cs >= a.Cin_p && a.in_cs % 4 == 0, "conv_wino %s: bad channel padding Cin_p=%d Cout_p=%d in_cs=%d",
                 name, a.Cin_p, a.Cout_p, a.in_cs);
     VFI_REQUIRE(((uintptr_t)a.in & 15) == 0 && ((uintptr_t)a.w & 15) == 0, "conv_wino %s: unaligned pointers", name);
-    VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv_wino %s: image larger than 2 GiB", name);
+    const bool large = wino_large(a) && wino_large_ok(a);      // a layer without a LARGE instantiation keeps the plain form and its guards
+    VFI_REQUIRE(large || (long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv_wino %s: image larger than 2 GiB", name);
     VFI_REQUIRE(a.act != 3 || a.prelu, "conv_wino %s: act 3 needs per-channel slopes", name);
     WinoArgs p;
     p.a = a;
@@ -940,13 +976,23 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
         variant = e16 > e8 * 1.15 ? 16 : 8;
     }
     VFI_REQUIRE(variant == 8 || variant == 16, "conv_wino %s: bad variant %d", name, variant);
-    VFI_REQUIRE((a.out_mode == 1 || (long)a.Hin * a.Win * a.out_cs * 4 * (a.out_mode == 2 ? 4 : 1) < 0x7fffffffL) && (!a.res || (long)a.Hin * a.Win * a.res_cs * 4 < 0x7fffffffL),
+    VFI_REQUIRE(large || ((a.out_mode == 1 || (long)a.Hin * a.Win * a.out_cs * 4 * (a.out_mode == 2 ? 4 : 1) < 0x7fffffffL) && (!a.res || (long)a.Hin * a.Win * a.res_cs * 4 < 0x7fffffffL)),
                 "conv_wino %s: output / residual image larger than 2 GiB", name);
     // the hot epilogue: no residual, no post affine, none / LeakyReLU with a slope in [0,1]
     // ... or per-channel PReLU (MODE 1)
     const bool ext = a.res != nullptr || a.post_scale != 0.f || !(a.act == 0 || (a.act == 1 && a.slope >= 0.f && a.slope <= 1.f) || a.act == 3);
     VFI_REQUIRE(a.act >= 0 && a.act <= 5, "conv_wino %s: activation code %d", name, a.act);
     const int mode = ext ? 10 + a.act : (a.act == 3 ? 1 : 0);      // wino_epilogue's MODE: one kernel per general activation
+    if (large) {      // 16x8 regions whatever the fill (the region shape changes no bit); the row span of a patch stays far below 2 GiB
+        VFI_REQUIRE((long)10 * a.Win * (a.in_cs > a.out_cs ? a.in_cs : a.out_cs) * 4 < 0x7fffffffL && (!a.res || (long)10 * a.Win * a.res_cs * 4 < 0x7fffffffL),
+                    "conv_wino %s: image larger than 2 GiB", name);
+        switch (mode) {
+            case 0: return wino_launch_t<8, 0, 0, 0, true>(p, s, name);
+            case 10: return wino_launch_t<8, 10, 0, 0, true>(p, s, name);
+            case 11: return wino_launch_t<8, 11, 0, 0, true>(p, s, name);
+            default: return wino_launch_t<8, 12, 0, 0, true>(p, s, name);
+        }
+    }
     if (a.out_mode == 1) {      // transposed convolution + PixelShuffle as a 3x3 layer (pack_deconv_as_conv3x3): hot epilogue, 16x8 regions
         VFI_REQUIRE(!ext && a.Cout % 4 == 0 && a.act == 0 && !a.beta, "conv_wino %s: the pixel-shuffle output takes the plain epilogue (bias only)", name);
         VFI_REQUIRE((long)(a.out_planes ? a.out_planes : 2) * 16 * a.Hin * a.Win * 16 < 0x7fffffffL, "conv_wino %s: block output larger than 2 GiB", name);

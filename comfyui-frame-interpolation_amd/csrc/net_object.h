@@ -201,6 +201,8 @@ struct VFI_INTERNAL NetObject {
 
 // The layers index one image with 32 bits of bytes: the padded pixels a net may take whose widest buffer has px_floats floats per pixel.
 inline int64_t max_padded_pixels(int px_floats) { return 0x7fffffffLL / (px_floats * 4); }
+// ... and of a net whose layers all have a large-image form (conv_mfma2.hip / conv_wino.hip: LARGE), where one image stays below 4 GiB
+inline int64_t max_padded_pixels_large(int px_floats) { return 0xffffffffLL / (px_floats * 4); }
 
 // Base of such a net: the padded size is the key of its workspace.
 struct VFI_INTERNAL PaddedNet : NetObject {
@@ -208,9 +210,12 @@ struct VFI_INTERNAL PaddedNet : NetObject {
 
     // The entry guard of a forward: an H x W frame padded to Hp x Wp is refused before any launch or allocation when it is over the size
     // limit; the workspace is released when the padded size (or the caller's own part of the key, `rekey`) changed; the key is stored.
-    // who: the entry point, net: the model's name in the refusal.
-    int enter(const char* who, const char* net, int H, int W, int Hp_, int Wp_, int px_floats, bool rekey = false) {
-        VFI_REQUIRE((int64_t)Hp_ * Wp_ <= max_padded_pixels(px_floats),
+    // who: the entry point, net: the model's name in the refusal.  large: the object serves images up to 4 GiB (max_padded_pixels_large).
+    int enter(const char* who, const char* net, int H, int W, int Hp_, int Wp_, int px_floats, bool rekey = false, bool large = false) {
+        VFI_REQUIRE(!large || (int64_t)Hp_ * Wp_ <= max_padded_pixels_large(px_floats),
+                    "%s: a %dx%d frame (padded %dx%d) is over the size limit of %s with large frames on, %lld padded pixels: Hp * Wp * %d bytes must stay "
+                    "below 4 GiB for the layers' index arithmetic", who, H, W, Hp_, Wp_, net, (long long)max_padded_pixels_large(px_floats), px_floats * 4);
+        VFI_REQUIRE(large || (int64_t)Hp_ * Wp_ <= max_padded_pixels(px_floats),
                     "%s: a %dx%d frame (padded %dx%d) is over the size limit of %s, %lld padded pixels: Hp * Wp * %d bytes must stay below 2 GiB "
                     "for the layers' index arithmetic", who, H, W, Hp_, Wp_, net, (long long)max_padded_pixels(px_floats), px_floats * 4);
         if (ws.live() && (Hp != Hp_ || Wp != Wp_ || rekey) && ws.release()) return -1;

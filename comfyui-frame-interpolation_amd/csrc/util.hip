@@ -32,6 +32,7 @@ static const struct { const char* name; long dflt; } kOptTable[kOptCount] = {
     {"stage_quad", 14}, {"fuse_encode", 1}, {"fuse0a", 1}, {"m2n2_px", -1}, {"grouped_variant", -1}, {"splitk", 1},
     {"splat_atomic", 0}, {"splat_spill_cap", -1}, {"wino_xcd", 1}, {"deconv_wino", 1}, {"encode_batched", 1}, {"wino_quant", 1}, {"xcd_bands", 0}, {"m2m_fused", 1}, {"m2m_side", 0}, {"film_side", 1}, {"wino_probe", 0},
     {"sepconv_split_heads", 0}, {"sepconv_planar", 1}, {"stage0", 1}, {"att_ksplit", 0}, {"wino_dead", 1},
+    {"large_image_bytes", 0x7fffffffL},
 };
 static std::atomic<long> g_opt[kOptCount];
 static std::atomic<bool> g_opt_init{false};

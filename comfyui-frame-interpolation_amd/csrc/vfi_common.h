@@ -80,6 +80,7 @@ enum Option {
     kOptStage0,             // 1: RIFE block 0's input assembled from the per-frame staging images the frame pack kernels write (default), 0: gathered from the packs per pair
     kOptAttKsplit,          // 1..8: the number of key ranges attention_launch_t asks for (attention.hip; reduced so that no range is empty), default 0: chosen from the device's CU count
     kOptWinoDead,           // 1: the Winograd kernel skips the transform planes a transposed-convolution layer's weights leave zero (ConvArgs::wino_dead; default), 0: all 16 planes: same bits
+    kOptLargeBytes,         // bytes of one image from which a layer object's operand counts as large and the launch takes the per-tile / per-region descriptors (conv_mfma2.hip, conv_wino.hip: LARGE); default 2^31 - 1, lower values put small images on that path: same bits
     kOptCount
 };
 long option(Option o);
@@ -90,8 +91,8 @@ int option_set(const char* name, long value);      // 0, or -2 for an unknown na
 int variant_override(const char* trace_name);      // tile variant forced for a trace name (vfi_test_variant_override), -1 = none
 // What the calling thread's last convolution launch was (vfi_test_last_conv_launch): written by the host-side launchers launch_t,
 // launch2_e and wino_launch_t.  Stores under VFI_TEST_TAPS only; in the product library both are empty functions.
-//   family 1 / 2 = first / second generation direct kernel, 3 = Winograd;  form: direct 0 plain, 1 EXT, 2 MASKED; Winograd MODE;
-//   store: out_mode (direct) / SHUF (Winograd);  ks: split-K slices (1 = unsplit);  work: tiles (direct) / work items (Winograd)
+//   family 1 / 2 = first / second generation direct kernel, 3 = Winograd;  form: direct 0 plain, 1 EXT, 2 MASKED, 3 LARGE; Winograd MODE;
+//   store: out_mode (direct) / SHUF (Winograd; 3 = the LARGE form, whose store is SHUF 0's);  ks: split-K slices (1 = unsplit);  work: tiles (direct) / work items (Winograd)
 enum { kConvFamilyGen1 = 1, kConvFamilyGen2 = 2, kConvFamilyWino = 3 };
 void conv_record_variant(int variant);      // conv_launch: the direct variant id in the common numbering, kept for the launcher's record
 void conv_record_launch(int family, int wino_region, int form, int store, int ks, long grid_x, long work);   // wino_region: 8 / 16, direct: 0
@@ -217,6 +218,10 @@ struct WinoDeconvPack {
 };
 void pack_deconv_wino(const float* w_iohw, const float* bias, const float* prelu, int Cin, int LO, const int* chan_map, int Cin_p, WinoDeconvPack& out);
 bool conv_wino_eligible(const ConvArgs& a);
+// Large images (2 GiB <= one image's bytes < 4 GiB): the direct kernel addresses its output and residual with 64 bits in every form, so
+// only its input decides; the Winograd kernel goes through descriptors on all three.
+inline bool conv_bytes_large(long bytes) { return bytes >= option(kOptLargeBytes); }
+inline bool conv_input_large(const ConvArgs& a) { return conv_bytes_large((long)a.Hin * a.Win * a.in_cs * 4); }
 int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal
 int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* trace_name);
 void deconv4x4_taps(ConvArgs& a);

@@ -379,7 +379,7 @@ namespace {
 constexpr int NF = 64;
 constexpr int kMaxLevels = 8;
 // the widest per-image buffer, floats per padded pixel: the RefineUNet's input at scale 2 (64 shuffled channels + 16); the layers index
-// an image with 32 bits
+// an image with 32 bits of bytes, signed (the limit of every object as created) or unsigned (after vfi_xvfi_set_large_frames)
 constexpr int kPxFloats = 80;
 
 struct Tower {      // Conv2d(4, 2, 1), Conv2d(4, 2, 1), up 2 + 3x3, up 2 + 3x3, 3x3: conv_flow_bottom / conv_flow2 / conv_flow3 after its 1x1
@@ -395,6 +395,7 @@ struct vfi_xvfi : PaddedNet {
     vfi_conv_t *flow1 = nullptr, *flow3_in = nullptr;
     vfi_conv_t *enc1 = nullptr, *enc2 = nullptr, *enc3 = nullptr, *dec0 = nullptr, *dec1 = nullptr, *dec2 = nullptr, *dec3 = nullptr;
     int H = 0, W = 0;            // the frame size is part of the workspace key too: the kept pair is compared against the padded copy
+    bool large = false;          // vfi_xvfi_set_large_frames: padded frames up to max_padded_pixels_large(kPxFloats) are served
     bool have_pair = false;      // the workspace holds the features, the level flows and flow_l_tmp of the pair whose padded copy is "img"
     int* flag_host = nullptr;    // pinned: xvfi_same_kernel's verdict
 };
@@ -542,6 +543,14 @@ int round_to(int n, int d) { return n + (d - n % d) % d; }
 extern "C" {
 
 int64_t vfi_xvfi_max_padded_pixels(void) { return max_padded_pixels(kPxFloats); }
+int64_t vfi_xvfi_large_max_padded_pixels(void) { return max_padded_pixels_large(kPxFloats); }
+int64_t vfi_xvfi_object_max_padded_pixels(const vfi_xvfi_t* m) { return !m ? 0 : (m->large ? max_padded_pixels_large(kPxFloats) : max_padded_pixels(kPxFloats)); }
+
+int vfi_xvfi_set_large_frames(vfi_xvfi_t* m, int on) {
+    VFI_REQUIRE(m, "vfi_xvfi_set_large_frames: null object");
+    m->large = on != 0;
+    return 0;
+}
 
 vfi_xvfi_t* vfi_xvfi_create(const float* const* tensors, const int64_t* numels, int n_tensors, int scale, int S_tst) {
     const bool known = (scale == 2 || scale == 4) && S_tst >= 0 && S_tst < kMaxLevels;
@@ -624,7 +633,7 @@ int vfi_xvfi_forward(vfi_xvfi_t* m, const float* frame0_dev, const float* frame1
     const int divide = (1 << m->S) * m->scale * 4;
     const int Hp = round_to(H, divide), Wp = round_to(W, divide);
     hipStream_t st = (hipStream_t)stream;
-    const int rc = m->enter("vfi_xvfi_forward", "XVFI", H, W, Hp, Wp, kPxFloats, m->H != H || m->W != W);
+    const int rc = m->enter("vfi_xvfi_forward", "XVFI", H, W, Hp, Wp, kPxFloats, m->H != H || m->W != W, m->large);
     if (!m->ws.live()) m->have_pair = false;      // released just now, by the caller, or by a failed allocation
     if (rc) return rc;
     m->H = H, m->W = W;

@@ -26,12 +26,28 @@ from .xvfi_spec import CKPT_CONFIGS, check_state_dict, config_of, load_file, pad
 MODEL_TYPE = "xvfi"
 FLOATS_PER_PADDED_PIXEL = 80      # the widest per-image buffer: the RefineUNet's input at scale 2, 64 shuffled channels + 16 (csrc/xvfi_net.hip)
 MAX_PADDED_PIXELS = ((1 << 31) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)      # = vfi_xvfi_max_padded_pixels(): 6 710 886
+# with config.yaml's xvfi_large_frames on: one image below 4 GiB, served by the layer kernels' large-image forms
+# (= vfi_xvfi_large_max_padded_pixels(): 13 421 772; 2160x3840 fits both configurations, padded 2160x3840 / 2560x4096)
+LARGE_MAX_PADDED_PIXELS = ((1 << 32) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)
+
+
+def large_frames_enabled():
+    """config.yaml's ``xvfi_large_frames`` key (absent = off), read at call time"""
+    from . import ckpt
+
+    return bool(ckpt.load_config().get("xvfi_large_frames", False))
+
+
+def max_padded_pixels():
+    """The limit in force: MAX_PADDED_PIXELS, or LARGE_MAX_PADDED_PIXELS with ``xvfi_large_frames`` on"""
+    return LARGE_MAX_PADDED_PIXELS if large_frames_enabled() else MAX_PADDED_PIXELS
 
 
 def check_frame_size(H, W, config):
     Hp, Wp = padded_size(H, W, config)
-    if Hp * Wp > MAX_PADDED_PIXELS:
-        raise ValueError(f"XVFI VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({MAX_PADDED_PIXELS} padded pixels)")
+    limit = max_padded_pixels()
+    if Hp * Wp > limit:
+        raise ValueError(f"XVFI VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({limit} padded pixels)")
 
 
 class XvfiEngine(WorkspaceBytes, NetEngine):
@@ -50,13 +66,19 @@ class XvfiEngine(WorkspaceBytes, NetEngine):
     def check_state_dict(self, state_dict):
         check_state_dict(state_dict, self.config[0])
 
+    def _sync_large_frames(self):
+        """The object's limit follows config.yaml's ``xvfi_large_frames`` key as it is now"""
+        self._call("set_large_frames", int(large_frames_enabled()))
+
     def max_padded_pixels(self):
-        return int(self.lib.vfi_xvfi_max_padded_pixels())
+        self._sync_large_frames()
+        return int(self.lib.vfi_xvfi_object_max_padded_pixels(self.handle))
 
     def forward(self, frame0, frame1, t, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
         H, W, Cc = check_frames(frame0, frame1)
         check_frame_size(H, W, self.config)
+        self._sync_large_frames()
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         self._call("forward", frame0.data_ptr(), frame1.data_ptr(), Cc, H, W, float(t), out.data_ptr(), _lib.stream_ptr())

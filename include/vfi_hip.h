@@ -888,11 +888,20 @@ void vfi_xvfi_destroy(vfi_xvfi_t* net);
  * result, not clamped.  The features of both frames at every level, the level flows and level 0's flow_l_tmp do not depend on t: they are
  * computed when the pair differs from the one the object holds (compared bit for bit on the device; one stream synchronisation) and kept while t
  * varies.  A frame whose padded size exceeds vfi_xvfi_max_padded_pixels() = (2^31 - 1) / 320 = 6 710 886 pixels is refused before any launch:
- * the widest per-image buffer (the RefineUNet's input at scale 2) has 80 floats per padded pixel and the layers index an image with 32 bits. */
+ * the widest per-image buffer (the RefineUNet's input at scale 2) has 80 floats per padded pixel and the layers index an image with 32 bits.
+ * After vfi_xvfi_set_large_frames(net, 1) the limit of that object is vfi_xvfi_large_max_padded_pixels() = (2^32 - 1) / 320 = 13 421 772 pixels
+ * (2160 x 3840 fits both configurations: 2160 x 3840 padded pixels for Vimeo, 2560 x 4096 for X4K; 3072 x 4608 does not): the layers whose
+ * image holds 2 GiB or more take the large-image form of their kernel, which addresses an image below 4 GiB. */
 int vfi_xvfi_forward(vfi_xvfi_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, float t, float* out_dev, void* stream);
 /* out_dev [Hp / scale, Wp / scale, 6] = level 0's flow_l_tmp (:177) of the pair the object holds */
 int vfi_xvfi_level0_flow(vfi_xvfi_t* net, float* out_dev, void* stream);
 int64_t vfi_xvfi_max_padded_pixels(void);
+/* the limit with large frames on, and the limit vfi_xvfi_forward applies to this object (one of the two) */
+int64_t vfi_xvfi_large_max_padded_pixels(void);
+int64_t vfi_xvfi_object_max_padded_pixels(const vfi_xvfi_t* net);
+/* on != 0: the object serves padded frames up to vfi_xvfi_large_max_padded_pixels(); 0 (every object as created): up to
+ * vfi_xvfi_max_padded_pixels().  Changes no result at a size both serve. */
+int vfi_xvfi_set_large_frames(vfi_xvfi_t* net, int on);
 int vfi_xvfi_release_workspace(vfi_xvfi_t* net);
 int64_t vfi_xvfi_workspace_bytes(const vfi_xvfi_t* net);
 

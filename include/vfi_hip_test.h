@@ -39,7 +39,9 @@ int64_t vfi_test_pack_deconv3x3(const float* weight_host, const float* bias_host
 /* A/B options of tools/ and tests/: each selects between two CORRECT forms of a kernel or launch (csrc/vfi_common.h, enum Option):
  *   stage_quad (bit mask, default 14), fuse_encode (1), fuse0a (1; 2 = the fused kernel in its earlier form, which multiplies all 24 padded input channels: same bits), stage0 (1; 0 = block 0's input gathered from the frame packs per pair instead of assembled from the per-frame staging images), m2n2_px (-1), grouped_variant (-1), splitk (1), splat_atomic (0; 1 = LDS-atomic tile kernel, 3 = staged list gather with compaction for C == 4),
  *   splat_spill_cap (-1), wino_xcd (1), deconv_wino (1), encode_batched (1), wino_quant (1), m2m_fused (1: M2M render as one kernel), m2m_side (0; 1: M2M prepare forks its image-pyramid convolutions onto a side stream — measured neutral / slower under pair lanes), film_side (1: FILM forward on two streams — image 1's feature extraction and the backward flow pyramid beside image 0's / the forward one), xcd_bands (0), wino_dead (1; 0 = the Winograd kernel multiplies all 16 transform planes of a transposed-convolution layer instead of skipping the zero ones: same bits), att_ksplit (0 = the key split of the attention kernel chosen from the CU count; 1..8 = that many key ranges, fewer where one would be empty), wino_probe (0; 1..4 = the cycle-ledger forms of the hot
- *   Winograd instantiation: same results, s_memtime stamps summed per wave of workgroup 0).
+ *   Winograd instantiation: same results, s_memtime stamps summed per wave of workgroup 0), large_image_bytes (2^31 - 1; the bytes of one
+ *   image from which a layer object's launch takes the large-image form of its kernel, csrc/conv_mfma2.hip / conv_wino.hip LARGE: a lower
+ *   value puts small images on that path, same bits).
  * The product library reads NO experiment switch from the environment and does not contain this call: the defaults are all it can run.
  * Returns 0, or -2 for an unknown name. */
 int vfi_test_set_option(const char* name, int64_t value);
@@ -53,8 +55,8 @@ int vfi_test_variant_override(const char* spec);
  * launcher: layer objects, vfi_conv3x3, the networks): up to 8 int32 to `out` —
  *   [0] kernel family: 1 first-generation direct (csrc/conv_mfma.hip), 2 second-generation direct (conv_mfma2.hip), 3 Winograd; 0 = none yet
  *   [1] direct: tile variant id in the common numbering (0.. / 32..); Winograd: region shape 8 (16x8 pixels) / 16 (32x4)
- *   [2] direct: 0 plain, 1 EXT, 2 MASKED instantiation; Winograd: the epilogue MODE (0, 1, 10 .. 15)
- *   [3] the store form: out_mode (direct) / SHUF (Winograd)
+ *   [2] direct: 0 plain, 1 EXT, 2 MASKED, 3 LARGE instantiation; Winograd: the epilogue MODE (0, 1, 10 .. 15)
+ *   [3] the store form: out_mode (direct) / SHUF (Winograd; 3 = the LARGE instantiation, an NHWC store as SHUF 0)
  *   [4] split-K slices (1 = unsplit; > 1: the epilogue ran in the reduce kernel)
  *   [5] grid.x   [6] tiles (direct) / work items (Winograd): grid.x < [6] is a persistent launch
  *   [7] launches this thread has made so far.

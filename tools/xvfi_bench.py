@@ -1,6 +1,6 @@
 """Device-resident XVFI at 1080p, seeded weights, both configurations (Vimeo: scale 2, S_tst 1; X4K: scale 4, S_tst 5).
 
-    python tools/xvfi_bench.py [--iters 5] [--height 1080] [--width 1920] [--trace]
+    python tools/xvfi_bench.py [--iters 5] [--height 1080] [--width 1920] [--trace] [--large-frames]
 
 Prints one JSON line: per configuration the ms per interpolated frame at x2 (one timestep per pair: features + level flows + one render)
 and at x8 (seven timesteps per pair: the pair-level work once), medians of `iters` pairs timed with device events around the calls with the
@@ -39,13 +39,17 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--trace", action="store_true", help="per-kernel event trace of one extra x2 pair")
+    ap.add_argument("--large-frames", action="store_true", help="run as with config.yaml's xvfi_large_frames on (sizes over 6 710 886 padded pixels)")
     args = ap.parse_args()
     from pkgload import load_package
 
     load_package()
     import cain_restated
-    from cfi_amd import _lib, xvfi, xvfi_spec
+    from cfi_amd import _lib, ckpt, xvfi, xvfi_spec
 
+    if args.large_frames:
+        real_config = ckpt.load_config
+        ckpt.load_config = lambda: dict(real_config(), xvfi_large_frames=True)
     H, W = args.height, args.width
     frames = cain_restated.seeded_frames(3, H, W, 3, 5).cuda()
     result = {"tool": "xvfi_bench", "height": H, "width": W, "iters": args.iters}
