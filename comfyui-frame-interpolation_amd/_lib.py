@@ -181,6 +181,8 @@ PROTOTYPES = {
     "vfi_film_destroy": (None, [C.c_void_p]),
     "vfi_film_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vfi_film_release_workspace": (C.c_int, [C.c_void_p]),
+    "vfi_film_max_pixels": (C.c_int64, []),
+    "vfi_film_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_film_two_streams": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_film_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.POINTER(C.c_int64)]),
@@ -200,6 +202,8 @@ PROTOTYPES = {
     "vfi_cain_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_cain_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_conv_accept_odd": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfi_conv_allow_huge": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfi_conv_huge_max_floats": (C.c_int64, []),
     "vfi_sepconv_pair_out": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_sepconvnet_create": (C.c_void_p, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int]),
@@ -319,6 +323,10 @@ WINO_TEST_PROTOTYPES = {
 ATM_TEST_PROTOTYPES = {
     "vfi_atm_ensemble_record": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
 }
+# ... and include/vfi_hip_test_large.h (the log of LARGE-form launches): test builds only
+LARGE_TEST_PROTOTYPES = {
+    "vfi_test_large_launches": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+}
 
 
 # The runtime variables this package honours — all of them select resources or diagnostics, none changes a frame's values
@@ -371,6 +379,7 @@ def load():
         protos.update(TEST_PROTOTYPES)
         protos.update(WINO_TEST_PROTOTYPES)
         protos.update(ATM_TEST_PROTOTYPES)
+        protos.update(LARGE_TEST_PROTOTYPES)
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

@@ -69,7 +69,8 @@ struct Conv2Geom {
 // floats [h] and [2 + h] of the pixel's chunk and of the weight row, i.e. the channel pairs (0|1), (2|3) — the live terms of the
 // plain form's (0|4), (1|5), (2|6), (3|7) in the same order, without its four fma(x, 0, acc).  DMA, LDS image and epilogue are the
 // plain form's.
-// LARGE (plain NHWC layers, zero padding): the input image holds 2 GiB or more (below 4 GiB), so a byte offset from the image's start no
+// LARGE (plain NHWC layers, zero padding): the input image holds 2 GiB or more (below 4 GiB; up to 2^31 - 1 floats for a layer object with
+// vfi_conv_allow_huge: nothing below counts bytes from the image's start, conv_large.h has the arithmetic), so a byte offset from there no
 // longer fits the 31 bits the descriptor's range check leaves.  The descriptor is rebased per tile instead: its base is the first input
 // row the tile's halo touches (a 64-bit, wave-uniform address), its size the rows the halo spans, and the per-lane offsets count from
 // that row — a few rows of bytes, whatever the image.  Same pieces, same LDS image, same arithmetic: same bits as the plain form wherever
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
     // activation DMA: voffset per 16-byte piece inside the image; out-of-image halo -> out of range -> zero fill
     auto make_avoff = [&](int Y0, int X0, int(&avoff)[G::NAW]) {
         const int iy0 = STRIDE * Y0 - G::PADLO, ix0 = STRIDE * X0 - G::PADLO;
-        const int r0 = LARGE ? (iy0 > 0 ? iy0 : 0) : 0;      // the row the tile's descriptor starts at (make_rsrc)
+        [[maybe_unused]] const int r0 = LARGE ? large_row0(iy0) : 0;      // the row the tile's descriptor starts at (make_rsrc)
 #pragma unroll
         for (int i = 0; i < G::NAW; ++i) {
             const int j = wave + 4 * i;
@@ -130,15 +131,15 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
                 avoff[i] = pix < G::NPIX ? ((cy * a.Win + cx) * pstr + q * qstr) * 4 : (int)0x80000000;
             } else {
                 const bool ok = pix < G::NPIX && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
-                avoff[i] = ok ? (((iy - r0) * a.Win + ix) * pstr + q * qstr) * 4 : (int)0x80000000;
+                if constexpr (LARGE) avoff[i] = ok ? large_lane_bytes(iy, r0, a.Win, ix, pstr, q * qstr) : (int)0x80000000;
+                else avoff[i] = ok ? ((iy * a.Win + ix) * pstr + q * qstr) * 4 : (int)0x80000000;
             }
         }
     };
     auto make_rsrc = [&](int n, int Y0) {
         if constexpr (LARGE) {
-            const int iy0 = STRIDE * Y0 - G::PADLO, r0 = iy0 > 0 ? iy0 : 0;
-            const int rows = a.Hin - r0 < G::THI ? a.Hin - r0 : G::THI;
-            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats + (size_t)r0 * a.Win * a.in_cs), 0, rows * a.Win * a.in_cs * 4, 0x00020000);
+            const int r0 = large_row0(STRIDE * Y0 - G::PADLO), rows = large_rows(a.Hin, r0, G::THI);
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + large_base_floats(n, img_floats, r0, a.Win, a.in_cs)), 0, large_span_bytes(rows, a.Win, a.in_cs), 0x00020000);
         } else {
             return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, img_floats * 4, 0x00020000);
         }
@@ -582,8 +583,9 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     a.tiles_y = cdiv(a.Hout, G::THO);
     VFI_REQUIRE(a.Cin_p % CK == 0, "conv2 %s: Cin_p=%d not a multiple of the K chunk %d", name, a.Cin_p, CK);
     VFI_REQUIRE(a.Cout_p % G::BN == 0, "conv2 %s: Cout_p=%d not a multiple of the N tile %d", name, a.Cout_p, G::BN);
-    if (LARGE) {      // the per-tile descriptor: the whole image below 4 GiB, the rows of one tile's halo below 2 GiB
-        VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 <= 0xffffffffL && !a.in_plane && !a.pad_mode && (long)G::THI * a.Win * a.in_cs * 4 < 0x7fffffffL,
+    if (LARGE) {      // the per-tile descriptor: the whole image below 4 GiB (with the layer's permission: its floats in an int, the kernel's
+                      // img_floats), the rows of one tile's halo below 2 GiB (conv_large.h)
+        VFI_REQUIRE(large_image_ok(a.Hin, a.Win, a.in_cs, a.huge_ok != 0) && !a.in_plane && !a.pad_mode && large_span_ok(G::THI, a.Win, a.in_cs),
                     "conv2 %s: image larger than 2 GiB", name);
     } else {
         VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
@@ -651,6 +653,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         p.act = 0, p.post_scale = 0.f, p.post_shift = 0.f, p.Cout = a.Cout_p;
         p.ksplit = ks, p.split_stride = (long)slice;
         conv_record_launch(kConvFamilyGen2, 0, LARGE ? 3 : MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, ks, T, T);
+        if (LARGE) conv_record_large(kConvFamilyGen2, a);
         {
             TraceScope ts(name, s);
             // (the same instantiation as the unsplit launch: its dynamic-LDS attribute is the one set above; pad_mode implies EXT)
@@ -668,6 +671,7 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     if (MASKED) gx = T;      // N blocks carry 1, 2, 2 or 4 taps: one workgroup per tile, the dispatcher balances them
     dim3 grid(gx, ny);
     conv_record_launch(kConvFamilyGen2, 0, LARGE ? 3 : MASKED ? 2 : (EXT ? 1 : 0), a.out_mode, 1, gx, T);
+    if (LARGE) conv_record_large(kConvFamilyGen2, a);
     TraceScope ts(name, s);
     hipLaunchKernelGGL((conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, LARGE>), grid, dim3(256), G::LDS_BYTES, s, a);
     VFI_CHECK_HIP(hipGetLastError());

@@ -169,15 +169,15 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
     const int planes = a.out_planes ? a.out_planes : 2;
     const int Ws4 = 4 * W;                       // SHUF: T row length in pixels
     static_assert(!LARGE || SHUF == 0, "large images: NHWC stores only");
-    const int lrows = H - oy0 < 2 * (32 / RTX) ? H - oy0 : 2 * (32 / RTX);      // LARGE: the rows of the region that exist
+    const int lrows = LARGE ? large_rows(H, oy0, 2 * (32 / RTX)) : 0;      // LARGE: the rows of the region that exist
     const __amdgpu_buffer_rsrc_t orsrc =
-        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + ((size_t)n * H + oy0) * W * a.out_cs), 0, lrows * W * a.out_cs * 4, 0x00020000) :
+        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + large_row_base_floats(n, H, oy0, W, a.out_cs)), 0, large_span_bytes(lrows, W, a.out_cs), 0x00020000) :
         SHUF == 1 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * planes * 16 * H * W * 4), 0, planes * 16 * H * W * 16, 0x00020000)
         : SHUF == 2 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * 4 * H * W * a.out_cs), 0, 4 * H * W * a.out_cs * 4, 0x00020000)
                     : __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * H * W * a.out_cs), 0, H * W * a.out_cs * 4, 0x00020000);
     const bool has_res = MODE >= 10 && a.res != nullptr;
     const __amdgpu_buffer_rsrc_t rrsrc =
-        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? a.res + ((size_t)n * H + oy0) * W * a.res_cs : a.out), 0, has_res ? lrows * W * a.res_cs * 4 : 0, 0x00020000)
+        LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? a.res + large_row_base_floats(n, H, oy0, W, a.res_cs) : a.out), 0, has_res ? large_span_bytes(lrows, W, a.res_cs) : 0, 0x00020000)
               : __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? a.res + (size_t)n * H * W * a.res_cs : a.out), 0, has_res ? H * W * a.res_cs * 4 : 0, 0x00020000);
     const int xlane = ox0 + 8 * half;          // this lane's first output column; + xq per store
     const bool cok = co < a.Cout;
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
     int* const avtab = (int*)(smem + G::NBUF * G::BUF_FLOATS) + wave * (NA * 64);
     auto make_avoff = [&](const Cur& c) {
         const int ol = opaque_lane();
-        const int r0 = LARGE ? (c.Ry0 > 0 ? c.Ry0 - 1 : 0) : 0;      // the row the item's descriptor starts at (make_arsrc)
+        [[maybe_unused]] const int r0 = LARGE ? large_row0(c.Ry0 - 1) : 0;      // the row the item's descriptor starts at (make_arsrc)
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int sp = i * 64 + ol;                      // swizzled slot = where the DMA puts this lane's 16 bytes
@@ -358,7 +358,8 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
             const int iy = c.Ry0 - 1 + py, ix = c.Rx0 - 1 + ((sl >> 1) - py * PW);
             const int cy = pad_index(iy, H, a.pad_mode), cx = pad_index(ix, W, a.pad_mode);   // replicate: edge clamp, reflect: mirror
             const bool ok = code >= 0 && c.valid && (a.pad_mode || (cy == iy && cx == ix));
-            avtab[i * 64 + ol] = ok ? (((cy - r0) * W + cx) * a.in_cs + (code & 1) * 4) * 4 : (int)0x80000000;
+            if constexpr (LARGE) avtab[i * 64 + ol] = ok ? large_lane_bytes(cy, r0, W, cx, a.in_cs, (code & 1) * 4) : (int)0x80000000;
+            else avtab[i * 64 + ol] = ok ? ((cy * W + cx) * a.in_cs + (code & 1) * 4) * 4 : (int)0x80000000;
         }
     };
     // One DMA piece per call: the K loop spreads a chunk's pieces over its MFMA groups (ten in a row back up the texture
@@ -427,9 +428,8 @@ __global__ __launch_bounds__(256) void conv_wino_kernel(const WinoArgs p) {
     };
     auto make_arsrc = [&](int n, int Ry0, bool live) {
         if constexpr (LARGE) {
-            const int r0 = Ry0 > 0 ? Ry0 - 1 : 0;
-            const int rows = H - r0 < G::PH ? H - r0 : G::PH;
-            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats + (size_t)r0 * W * a.in_cs), 0, live ? rows * W * a.in_cs * 4 : 0, 0x00020000);
+            const int r0 = large_row0(Ry0 - 1), rows = large_rows(H, r0, G::PH);
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + large_base_floats(n, img_floats, r0, W, a.in_cs)), 0, live ? large_span_bytes(rows, W, a.in_cs) : 0, 0x00020000);
         } else {
             return __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + (size_t)n * img_floats), 0, live ? img_floats * 4 : 0, 0x00020000);
         }
@@ -870,7 +870,9 @@ static int wino_cus(int dev) {
 }
 
 // Large images: an operand (input, output, residual) of one image at or over the mark (conv_bytes_large).  The LARGE instantiations exist
-// for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual, and operands below 4 GiB.
+// for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual, and operands below 4 GiB — with the
+// layer object's permission (ConvArgs::huge_ok) up to kConvHugeMaxFloats floats each (conv_large.h: the kernel keeps an image's floats in an
+// int and forms every address from a per-region 64-bit base).
 static long wino_operand_bytes(const ConvArgs& a) {
     const long px = (long)a.Hin * a.Win;
     const long m = (a.in_cs > a.out_cs ? a.in_cs : a.out_cs);
@@ -878,7 +880,8 @@ static long wino_operand_bytes(const ConvArgs& a) {
 }
 static bool wino_large(const ConvArgs& a) { return a.out_mode == 0 && conv_bytes_large(wino_operand_bytes(a)); }
 static bool wino_large_ok(const ConvArgs& a) {
-    return wino_operand_bytes(a) <= 0xffffffffL && !a.pad_mode && !a.in_plane && a.act >= 0 && a.act <= 2 && a.post_scale == 0.f;
+    const long bytes = wino_operand_bytes(a);
+    return (a.huge_ok ? bytes / 4 <= kConvHugeMaxFloats : bytes <= kConvLargeMaxBytes) && !a.pad_mode && !a.in_plane && a.act >= 0 && a.act <= 2 && a.post_scale == 0.f;
 }
 
 // Is the Winograd kernel the better choice for this layer on this launch?  (3x3 stride 1 only; enough work items to fill the
@@ -946,6 +949,7 @@ static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     p.xcd_map = option(kOptWinoXcd) ? 1 : 0;
     p.clk_tag = clock_probe_tag(name);
     conv_record_launch(kConvFamilyWino, RTX, MODE, LARGE ? 3 : SHUF, 1, grid, items);
+    if (LARGE) conv_record_large(kConvFamilyWino, a);
     TraceScope ts(name, s);
     hipLaunchKernelGGL((conv_wino_kernel<RTX, MODE, SHUF, PROBE, LARGE>), dim3(grid), dim3(256), G::LDS_BYTES, s, p);
     VFI_CHECK_HIP(hipGetLastError());

@@ -34,6 +34,13 @@ struct Layer {
     int cout = 0, cin_phys = 0;
 };
 
+// channels of the aligned-pyramid tensor of level l without the fusion's slot: [imgA 3, 0, featA F | imgB 3, 0, featB F | flows 4], padded to x8
+int aligned_channels(int level) { return r8(2 * (4 + feat_channels(level)) + 4); }
+// The widest tensor per full-resolution pixel is al[0]: the aligned level 0 plus the FILTERS channels the fusion's up-sampling layer
+// writes behind it (208 floats; the next are tw[k][0] with 4 + 2 * 64 = 132 and al[1] with 528 on a quarter of the pixels).  Its floats
+// must fit the layers' bound for one operand image (conv_large.h: kConvHugeMaxFloats, the layers are created with vfi_conv_allow_huge).
+int64_t film_max_pixels() { return kConvHugeMaxFloats / (aligned_channels(0) + FILTERS); }
+
 // reference channel order of one aligned-pyramid level [imgA 3, featA F, imgB 3, featB F, bflow 2, fflow 2]
 // -> physical order [imgA 3, 0, featA F | imgB 3, 0, featB F | bflow 2, fflow 2 | zero pad to x8]
 std::vector<int> aligned_map(int F) {
@@ -182,6 +189,8 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
         L.cout = cout;
         L.cin_phys = cin_phys > 0 ? cin_phys : r8(cin);
         L.h = net->add_layer(vfi_conv_create(w, b, cout, cin, kk, kk, cmap ? cmap->data() : nullptr, L.cin_phys));
+        // operands of 4 GiB and more (al[0], tw[k][0], al[1] at 2160x3840): frames up to today's limit run the launches they always ran
+        if (L.h && vfi_conv_allow_huge(L.h, 1)) net->failed = true;
         if (!up2) return;
         up2->cout = cout, up2->cin_phys = L.cin_phys;
         up2->h = net->add_layer(vfi_conv_create_up2x2(w, b, cout, cin, cmap ? cmap->data() : nullptr, L.cin_phys));
@@ -206,7 +215,7 @@ vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, 
         make(net->pred[lvl][3], nf / 2, nf, 1, nullptr, 0);
         make(net->pred[lvl][4], 2, nf / 2, 1, nullptr, 0);
     }
-    for (int l = 0; l < FUS; ++l) net->cal[l] = r8(2 * (4 + feat_channels(l)) + 4);
+    for (int l = 0; l < FUS; ++l) net->cal[l] = aligned_channels(l);
     make(net->out_conv, 3, FILTERS, 1, nullptr, 0);
     for (int f = 0; f < 4; ++f) {
         const int lvl = 3 - f, nf = FILTERS << std::min(lvl, 3);
@@ -253,9 +262,17 @@ int vfi_film_release_workspace(vfi_film_t* net) {
     return net->ws.release();
 }
 
+int64_t vfi_film_max_pixels(void) { return film_max_pixels(); }
+
+int64_t vfi_film_workspace_bytes(vfi_film_t* net) { return net ? net->ws.bytes() : 0; }
+
 int vfi_film_forward(vfi_film_t* net, const float* x0_dev, const float* x1_dev, int C, int H, int W, float* out_dev, int clamp,
                      void* stream) {
     VFI_REQUIRE(net && x0_dev && x1_dev && out_dev && C >= 3, "vfi_film_forward: bad arguments");
+    // before any allocation or launch (the workspace of an accepted frame is released only when the size changes, in ensure_workspace)
+    VFI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= film_max_pixels(),
+                "vfi_film_forward: a %dx%d frame is over the size limit of FILM, %lld pixels: the aligned pyramid's level 0 (%d floats per pixel) must "
+                "stay within the layers' %lld floats per image", H, W, (long long)film_max_pixels(), aligned_channels(0) + FILTERS, (long long)kConvHugeMaxFloats);
     if (int rc = ensure_workspace(net, H, W)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float* xs[2] = {x0_dev, x1_dev};

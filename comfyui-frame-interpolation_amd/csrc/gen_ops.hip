@@ -236,6 +236,7 @@ struct vfi_conv {
     int stride = 1, pad_mode = 0, kind = 0;  // kind 0: Conv2d, 1: ConvTranspose2d(4, 2, 1), 2: nearest x2 up-sampling + Conv2d(2, 'same') (vfi_conv_create_up2x2)
     unsigned char* tapmask = nullptr;         // kind 2: taps of every 64-channel N block's parity
     bool odd_ok = false;                      // 3x3 stride-2 layer that takes odd input sizes (vfi_conv_accept_odd)
+    bool huge_ok = false;                     // operand images of 4 GiB and more are served where a LARGE kernel form exists (vfi_conv_allow_huge)
     int cin_src = 0;                          // 4x4 stride-2 layer (kh == 4): channels of the caller's input window; Cin_p = 4 * cin_src is the
                                               //   space-to-depth image's (s2d_pad1_kernel), over which the layer is a 2x2 stride-1 one (taps == 4)
 };
@@ -487,6 +488,14 @@ int vfi_conv_accept_odd(vfi_conv_t* c, int on) {
     return 0;
 }
 
+int vfi_conv_allow_huge(vfi_conv_t* c, int on) {
+    VFI_REQUIRE(c, "vfi_conv_allow_huge: null handle");
+    c->huge_ok = on != 0;
+    return 0;
+}
+
+int64_t vfi_conv_huge_max_floats(void) { return kConvHugeMaxFloats; }
+
 int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs, int N,
                         int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs, void* stream) {
     VFI_REQUIRE(c && in_dev && out_dev && N > 0 && Hin > 0 && Win > 0, "vfi_conv_forward_ex: bad arguments");
@@ -520,6 +529,7 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
     a.act = act;
     a.slope = slope;
     a.split_ok = 1;
+    a.huge_ok = c->huge_ok ? 1 : 0;
     a.post_scale = post_scale;
     a.post_shift = post_shift;
     a.pad_mode = c->pad_mode;
@@ -614,6 +624,7 @@ int vfi_conv_forward(const vfi_conv_t* c, const float* in_dev, int in_cs, float*
     a.act = act;
     a.slope = slope;
     a.split_ok = 1;
+    a.huge_ok = c->huge_ok ? 1 : 0;
     char name[64];
     static const bool by_shape = getenv("VFI_TRACE_SHAPES") != nullptr;      // per-shape trace rows (tools/film_bench.py --shapes)
     if (c->kind == 2) {      // H x W is the LOW-resolution input; the output is [2H, 2W, out_cs] (vfi_conv_create_up2x2)

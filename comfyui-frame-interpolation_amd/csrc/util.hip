@@ -14,6 +14,7 @@
 
 #include "../../include/vfi_hip.h"
 #include "../../include/vfi_hip_test.h"
+#include "../../include/vfi_hip_test_large.h"
 
 namespace vfi {
 
@@ -86,9 +87,25 @@ int conv_record_read(int32_t* out, int cap) {
     for (int i = 0; i < n; ++i) out[i] = g_conv_rec[i];
     return n;
 }
+// the LARGE-form launches of this thread since the log was last read (vfi_test_large_launches): a whole network's worth, where the record
+// above keeps the last launch only
+static thread_local std::vector<int32_t> g_conv_large_log;
+void conv_record_large(int family, const ConvArgs& a) {
+    if (g_conv_large_log.size() >= 6 * 256) return;
+    const int32_t e[6] = {family, a.Hin, a.Win, a.in_cs, a.Cin_p, a.Cout};
+    g_conv_large_log.insert(g_conv_large_log.end(), e, e + 6);
+}
+int conv_large_log_read(int32_t* out, int cap_entries) {
+    const int n = (int)(g_conv_large_log.size() / 6);
+    for (int i = 0; i < n && i < cap_entries; ++i)
+        for (int j = 0; j < 6; ++j) out[6 * i + j] = g_conv_large_log[6 * i + j];
+    g_conv_large_log.clear();
+    return n;
+}
 #else
 void conv_record_variant(int) {}
 void conv_record_launch(int, int, int, int, int, long, long) {}
+void conv_record_large(int, const ConvArgs&) {}
 #endif
 #ifdef VFI_TEST_TAPS
 static void variant_override_set(const char* spec) {      // "conv0a_b3=42,resconv_c128=36"; empty / null clears
@@ -330,6 +347,10 @@ int vfi_test_variant_override(const char* spec) {
 int vfi_test_last_conv_launch(int32_t* out, int cap) {
     VFI_REQUIRE(out && cap > 0, "vfi_test_last_conv_launch: no buffer");
     return conv_record_read(out, cap);
+}
+int vfi_test_large_launches(int32_t* out, int cap_entries) {
+    VFI_REQUIRE(cap_entries == 0 || out, "vfi_test_large_launches: no buffer");
+    return conv_large_log_read(out, cap_entries);
 }
 #endif
 

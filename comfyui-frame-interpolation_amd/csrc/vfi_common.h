@@ -5,6 +5,8 @@
 #include <string>
 #include <vector>
 
+#include "conv_large.h"
+
 namespace vfi {
 
 void set_error(const char* fmt, ...);
@@ -97,6 +99,9 @@ enum { kConvFamilyGen1 = 1, kConvFamilyGen2 = 2, kConvFamilyWino = 3 };
 void conv_record_variant(int variant);      // conv_launch: the direct variant id in the common numbering, kept for the launcher's record
 void conv_record_launch(int family, int wino_region, int form, int store, int ks, long grid_x, long work);   // wino_region: 8 / 16, direct: 0
 int conv_record_read(int32_t* out, int cap);
+struct ConvArgs;
+void conv_record_large(int family, const ConvArgs& a);      // a LARGE-form launch, kept in a per-thread log (vfi_test_large_launches); empty in the product library
+int conv_large_log_read(int32_t* out, int cap_entries);    // entries of 6 ints (family, Hin, Win, in_cs, Cin_p, Cout); reading empties the log
 
 // Compute units the persistent kernels may size their grids for: the device's count minus what vfi_set_reserved_cus holds back for a
 // collective kernel running beside them (a resident RCCL kernel takes whole CUs from one-workgroup-per-CU kernels, whose displaced
@@ -148,6 +153,9 @@ struct ConvArgs {
     float post_scale, post_shift;  // y = act(...) * post_scale + post_shift  (post_scale == 0 means "not set" = 1, 0)
     int split_ok;          // caller: the launcher may cut K over several workgroups (split-K; generic layer objects only — the
                            //   RIFE network keeps one kernel per layer whatever the batch, so results do not depend on batching)
+    int huge_ok;           // host side only: the layer object's permission (vfi_conv_allow_huge) — the LARGE forms may serve operand images of 4 GiB
+                           //   and more, up to kConvHugeMaxFloats floats (conv_large.h); 0 = refused from 4 GiB on.  It sits in the four bytes of
+                           //   padding in front of the pointer below, so that no kernel argument moved when it was added (static_assert below)
     const unsigned char* tapmask;  // 2x2 layers in the "up-sample x2 first" form (conv_mfma2.hip, MASKED): per 64-channel N block the taps (bit a * 2 + b) of
     int par_cout;                  //   its parity; par_cout = channels per parity group (4 groups: Cout_p == 4 * par_cout), output [2 Hout, 2 Wout] interleaved
     int ksplit;            // set by the launcher: > 1 = split-K launch, blockIdx.z owns a K range and the slice
@@ -158,6 +166,8 @@ struct ConvArgs {
                            //   block, 4 bits per block (kWinoDead*, block nb = bits 4 (nb % 8) of word nb / 8), from WinoDeconvPack; 0 = none known
     int wino_gray;         //   1: the four parity groups of such a layer are packed in the order p00 p01 p11 p10 (wino_gray_order)
 };
+
+static_assert(sizeof(ConvArgs) == 208 && offsetof(ConvArgs, tapmask) == 160 && offsetof(ConvArgs, huge_ok) == 156, "ConvArgs: the kernels' argument offsets are part of their code");
 
 struct ConvVariant {
     const char* name;
@@ -218,8 +228,9 @@ struct WinoDeconvPack {
 };
 void pack_deconv_wino(const float* w_iohw, const float* bias, const float* prelu, int Cin, int LO, const int* chan_map, int Cin_p, WinoDeconvPack& out);
 bool conv_wino_eligible(const ConvArgs& a);
-// Large images (2 GiB <= one image's bytes < 4 GiB): the direct kernel addresses its output and residual with 64 bits in every form, so
-// only its input decides; the Winograd kernel goes through descriptors on all three.
+// Large images (2 GiB <= one image's bytes < 4 GiB; with ConvArgs::huge_ok up to kConvHugeMaxFloats floats, conv_large.h): the direct kernel
+// addresses its output and residual with 64 bits in every form, so only its input decides; the Winograd kernel goes through descriptors on
+// all three.
 inline bool conv_bytes_large(long bytes) { return bytes >= option(kOptLargeBytes); }
 inline bool conv_input_large(const ConvArgs& a) { return conv_bytes_large((long)a.Hin * a.Win * a.in_cs * 4); }
 int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal

@@ -25,12 +25,48 @@ import torch
 from . import _lib
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film_spec import check_state_dict, film_shapes
-from .lanes import lane_set
+from .lanes import LaneSet, lane_set, lanes_for
 from .netengine import NetEngine
 from .nodeloop import run_plan
 from .schedule import InterpolationStateList, film_output_plan
 
 MODEL_TYPE = "film"
+# Frames of up to this many pixels run the launches they ran before the layers' large forms existed: (2^32 - 1) // (208 * 4), the
+# widest tensor at one image below 4 GiB.  Above it the node opens ONE pair lane whatever lanes.DEFAULT_LANES says: a 4K workspace is
+# 69 GB, and two of them beside the staging rings have not been measured.
+LANE_PIXELS = 5162220
+
+
+def max_pixels():
+    """The largest frame the C object takes, H * W (vfi_film_max_pixels: read from the library, not repeated here)"""
+    return int(_lib.load().vfi_film_max_pixels())
+
+
+def check_frame_size(H, W):
+    """Before a clip is uploaded or an engine built: the wording of vfi_film_forward's own guard"""
+    limit = max_pixels()
+    if H * W > limit:
+        raise ValueError(f"FILM VFI: a {H}x{W} frame is over the size limit of FILM, {limit} pixels: the aligned pyramid's level 0 "
+                         f"(208 floats per pixel) must stay within the layers' 2147483647 floats per image")
+
+
+def lanes_for_frame(H, W):
+    """Pair lanes of a call on H x W frames"""
+    return lanes_for(MODEL_TYPE) if H * W <= LANE_PIXELS else 1
+
+
+def film_lane_set(build):
+    """The node's LaneSet, built with the lanes of the model type as before"""
+    ls = lane_set(MODEL_TYPE, build)
+    ls.k_built = ls.k
+    return ls
+
+
+def limit_lanes(engine, H, W):
+    """The lanes one call on H x W frames may open: never more than the set was built with (its streams), one above LANE_PIXELS.  Lanes beyond
+    the first are built at first use, so a 4K call never pays for a second engine."""
+    if isinstance(engine, LaneSet):
+        engine.k = min(getattr(engine, "k_built", engine.k), lanes_for_frame(H, W))
 
 
 class FilmEngine(NetEngine):
@@ -57,6 +93,11 @@ class FilmEngine(NetEngine):
         if n != buf.numel():
             raise RuntimeError("vfi_film_debug_read_flow: " + _lib.last_error())
         return buf.view(h, w, 2)
+
+    def workspace_now(self):
+        """Device bytes of the workspace as it stands (tools, documentation).  Deliberately not called workspace_bytes: ckpt.end_call would
+        take that name as leave to keep 15-69 GB resident between calls."""
+        return int(self.lib.vfi_film_workspace_bytes(self.handle)) if getattr(self, "handle", None) else 0
 
     def forward(self, x0, x1, clamp=False):
         """x0, x1: [H,W,C>=3] fp32 device tensors -> [H,W,3] device tensor (Interpolator.forward, time = 0.5)."""
@@ -124,11 +165,14 @@ class FILM_VFI:
 
     def vfi(self, ckpt_name: typing.AnyStr, frames: torch.Tensor, clear_cache_after_n_frames=10,
             multiplier: typing.SupportsInt = 2, optional_interpolation_states: InterpolationStateList = None, **kwargs):
+        H, W = (int(v) for v in frames.shape[1:3])
+        check_frame_size(H, W)      # before the checkpoint is read, an engine built or a frame uploaded
         model_path = load_file_from_github_release(MODEL_TYPE, ckpt_name)
         # (the reference re-loads the TorchScript file on every call, film/__init__.py:74; see ckpt.cached_engine)
         def build():
             sd = _load_state_dict(model_path)
-            return lane_set("film", lambda: FilmEngine(sd))
-        with engine_call(cached_engine(MODEL_TYPE, model_path, build), tuple(frames.shape[1:3])) as engine:
+            return film_lane_set(lambda: FilmEngine(sd))
+        with engine_call(cached_engine(MODEL_TYPE, model_path, build), (H, W)) as engine:
+            limit_lanes(engine, H, W)      # (the cached set may come from a call on frames of another size)
             plan, tasks = film_output_plan(len(frames), multiplier, optional_interpolation_states)
             return (run_plan(engine, frames, plan, tasks, film_pair, "FILM VFI"),)

@@ -138,12 +138,21 @@ typedef struct vfi_film vfi_film_t;
 vfi_film_t* vfi_film_create(const float* const* tensors, const int64_t* numels, int n_tensors);
 void vfi_film_destroy(vfi_film_t* net);
 /* out_dev [H,W,3] = Interpolator(x0, x1) for x0_dev, x1_dev [H,W,C] fp32 (C >= 3, alpha ignored); clamp != 0 applies the
- * node's prediction.clamp(0, 1) (film/__init__.py:39).  H, W >= 64.  The workspace (15 GB at 1080p) is sized on first use.
+ * node's prediction.clamp(0, 1) (film/__init__.py:39).  H, W >= 64, H * W <= vfi_film_max_pixels().  The workspace (15 GB at 1080p) is sized on first use.
  * All work is ordered on `stream` as seen by the caller; inside, half of the network up to the fusion runs on a side stream of the
  * object's own (forked from and joined to `stream` by events within the call: round 6, docs/design/film.md). */
 int vfi_film_forward(vfi_film_t* net, const float* x0_dev, const float* x1_dev, int C, int H, int W, float* out_dev, int clamp,
                      void* stream);
 int vfi_film_release_workspace(vfi_film_t* net);
+/* The largest frame vfi_film_forward takes, in pixels H * W: vfi_conv_huge_max_floats() / 208 = 10 324 440, where 208 = 144 + 64 floats per
+ * pixel is the object's widest tensor, the aligned pyramid's level 0 with the fusion's slot (2160x3840 and 2160x4096 fit; 2176x4800 does
+ * not).  A larger frame is refused before any allocation or launch.  The object's layers carry vfi_conv_allow_huge: at 2160x3840 three of
+ * them read an operand of more than 4 GiB (docs/design/film.md).  Frames of up to 5 162 220 pixels, the limit before the large layer forms
+ * existed, run the launches they always ran. */
+int64_t vfi_film_max_pixels(void);
+/* Device bytes of the object's workspace as it stands (0 before the first forward and after a release; it grows during the first forward of
+ * a frame size, whose scratch tensors are allocated at first use).  For tools and documentation: 69 GB at 2160x3840. */
+int64_t vfi_film_workspace_bytes(vfi_film_t* net);
 /* on != 0 (the default): vfi_film_forward forks half of the network onto the object's side stream; 0: everything on the caller's stream —
  * what a host that already keeps several pairs in flight on streams of its own (the nodes' pair lanes) wants: four busy streams on the
  * runtime's four hardware queues left the lanes 2 % slower than two.  Frames are bit-identical either way.  Returns the previous setting. */
@@ -223,6 +232,15 @@ vfi_conv_t* vfi_conv_create_ex(int kind, const float* w_host, const float* bias_
  * missing row / column read as padding.  Off by default (such a layer rejects odd sizes); even sizes compute the same bits either way.
  * Fails for any other layer. */
 int vfi_conv_accept_odd(vfi_conv_t* conv, int on);
+/* Operand images (input, output, residual of ONE image) and the kernels' index arithmetic.  Every layer object serves images below 2 GiB.
+ * The plain forms — kind 0, zero padding, act 0 / 1 / 2, no post affine; 3x3 stride 1 / 2, 2x2, 1x1 and the 4x4 stride-2 polyphase form —
+ * also serve 2 GiB up to 4 GiB - 1 through kernel forms that rebase their buffer descriptors per tile / per region.  From 4 GiB on a call
+ * is refused ("image larger than 2 GiB") unless the object was given this permission: then the same forms serve operand images of up to
+ * vfi_conv_huge_max_floats() = 2^31 - 1 floats (8 GiB - 4 bytes) each, the bound of the audited arithmetic (an image's float count is kept
+ * in an int; every address is a 64-bit per-tile base plus an offset of a few rows).  Off by default, a property of the object; no launch
+ * that was legal without it changes its kernel, its geometry or a bit of its output.  The extended forms keep their 2 GiB refusal. */
+int vfi_conv_allow_huge(vfi_conv_t* conv, int on);
+int64_t vfi_conv_huge_max_floats(void);
 int vfi_conv_forward_ex(const vfi_conv_t* conv, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs,
                         int N, int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs,
                         void* stream);

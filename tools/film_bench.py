@@ -1,4 +1,10 @@
-"""FILM 2x at 1080p on one MI355X (BASELINE.json configs[2]): parity vs the oracle at full size + timing + kernel split."""
+"""FILM 2x on one MI355X (BASELINE.json configs[2] at the default 1080x1920): timing, workspace bytes, kernel split; with --parity (or
+--check) one pair against oracle/film_oracle.py on the host at full size.
+
+    python tools/film_bench.py [H W] [--parity]          e.g.  VFI_TRACE_SHAPES=1 python tools/film_bench.py 2160 3840 --parity
+
+The parity mode prints max |d| and the number of values over the project's per-pixel gate of 1e-3; at 2160x3840 the host oracle takes
+minutes on 16 threads, which is why it lives here and not in the test suite."""
 import os
 import sys
 import time
@@ -16,14 +22,15 @@ from cfi_amd.film import FilmEngine  # noqa: E402
 
 if __name__ == "__main__":
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1080, 1920)
-    check = "--check" in sys.argv
+    check = "--check" in sys.argv or "--parity" in sys.argv
     sd = synth.film_synth_state_dict(1234)
     eng = FilmEngine(sd)
     fr = synth.smooth_frames(2, H, W, seed=2, shift=4.0)
     x0, x1 = fr[0].cuda().contiguous(), fr[1].cuda().contiguous()
     out = eng.forward(x0, x1)
     torch.cuda.synchronize()
-    print(f"FILM {H}x{W}: device memory after first forward {torch.cuda.memory_allocated() / 2**30:.1f} GiB (torch buffers)", flush=True)
+    print(f"FILM {H}x{W}: device memory after first forward {torch.cuda.memory_allocated() / 2**30:.1f} GiB (torch buffers), "
+          f"workspace {eng.workspace_now()} bytes = {eng.workspace_now() / 1e9:.2f} GB (vfi_film_workspace_bytes)", flush=True)
     for rep in range(2):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -50,5 +57,6 @@ if __name__ == "__main__":
         with torch.inference_mode():
             want = film_oracle.film_forward(sd, fr[0:1].permute(0, 3, 1, 2).contiguous(), fr[1:2].permute(0, 3, 1, 2).contiguous())
         d = (out.cpu() - want[0].permute(1, 2, 0)).abs()
-        print(f"FILM {H}x{W} vs oracle: max|d| = {d.max().item():.3e} mean {d.mean().item():.3e} (oracle CPU {time.time() - t0:.1f}s), "
+        print(f"FILM {H}x{W} vs oracle: max|d| = {d.max().item():.3e} mean {d.mean().item():.3e}, {int((d > 1e-3).sum())} of {d.numel()} values over 1e-3 "
+              f"(oracle CPU {time.time() - t0:.1f}s), "
               f"output range [{want.min().item():.2f},{want.max().item():.2f}]", flush=True)
