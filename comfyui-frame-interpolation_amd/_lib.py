@@ -261,6 +261,8 @@ PROTOTYPES = {
     "vfi_atm_forward_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_atm_max_padded_pixels": (C.c_int64, []),
     "vfi_atm_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
+    "vfi_atm_large_max_padded_pixels": (C.c_int64, [C.c_int]),
+    "vfi_atm_set_large_frames": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_atm_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_atm_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_xvfi_bicubic_down": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

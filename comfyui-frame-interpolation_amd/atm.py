@@ -10,13 +10,16 @@ every model call the midpoint of two known frames, clamped to [0, 1] and re-used
 last frame is appended: schedule.film_output_plan + nodeloop.run_plan with film.film_schedule.  Each model call is ONE vfi_atm_forward
 (csrc/atm_net.hip), or ONE vfi_atm_forward_ensemble in the ensemble mode (the global branch at scales 1, 1/2 and 1/4, scored and chosen on
 the device): centred replicate pad to multiples of 64, the network, un-pad, clamp.  No pair lanes, no HIP graph.
+
+Frame size: 6 710 886 (lite) / 4 194 303 (base) padded pixels; with config.yaml's ``atm_large_frames`` key on 13 421 772 / 8 388 607, which
+lets both models take 2160x3840 in every ``global_motion`` mode (vfi_atm_set_large_frames; the layers' large-image kernel forms).
 """
 import typing
 
 import torch
 
 from . import _lib
-from .atm_spec import CKPT_NAMES, VARIANTS, atm_ensemble_enabled, check_ckpt_name, check_state_dict, load_file, weight_shapes
+from .atm_spec import CKPT_NAMES, VARIANTS, atm_ensemble_enabled, atm_large_frames_enabled, check_ckpt_name, check_state_dict, load_file, weight_shapes
 from .ckpt import cached_engine, engine_call, load_file_from_github_release
 from .film import film_schedule
 from .netengine import NetEngine, WorkspaceBytes, check_frames, padded_to
@@ -32,6 +35,10 @@ MAX_PADDED_PIXELS = ((1 << 31) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)      # = vf
 # 2176x3840 does not; tests/test_gpu_atm_base.py asserts that this limit is vfi_atm_object_max_padded_pixels' of a base object
 BASE_FLOATS_PER_PADDED_PIXEL = 128
 MAX_PADDED_PIXELS_BASE = ((1 << 31) - 1) // (BASE_FLOATS_PER_PADDED_PIXEL * 4)      # 4 194 303
+# with config.yaml's atm_large_frames on: one image below 4 GiB, served by the layer kernels' large-image forms
+# (= vfi_atm_large_max_padded_pixels(0 / 1): 13 421 772 / 8 388 607; 2160x3840, padded 2176x3840 = 8 355 840, fits both)
+LARGE_MAX_PADDED_PIXELS = ((1 << 32) - 1) // (FLOATS_PER_PADDED_PIXEL * 4)
+LARGE_MAX_PADDED_PIXELS_BASE = ((1 << 32) - 1) // (BASE_FLOATS_PER_PADDED_PIXEL * 4)
 
 
 def padded_size(H, W):
@@ -39,9 +46,17 @@ def padded_size(H, W):
     return padded_to(H, 64), padded_to(W, 64)
 
 
-def check_frame_size(H, W, variant="lite"):
+def max_padded_pixels(variant="lite", large=None):
+    """The limit in force for a variant: today's, or the large one with config.yaml's ``atm_large_frames`` on (``large``: the key's state
+    where the caller has read it already; None: read now)"""
+    if atm_large_frames_enabled() if large is None else large:
+        return LARGE_MAX_PADDED_PIXELS_BASE if variant == "base" else LARGE_MAX_PADDED_PIXELS
+    return MAX_PADDED_PIXELS_BASE if variant == "base" else MAX_PADDED_PIXELS
+
+
+def check_frame_size(H, W, variant="lite", large=None):
     Hp, Wp = padded_size(H, W)
-    limit = MAX_PADDED_PIXELS_BASE if variant == "base" else MAX_PADDED_PIXELS
+    limit = max_padded_pixels(variant, large)
     if Hp * Wp > limit:
         raise ValueError(f"ATM VFI: {H}x{W} frames (padded {Hp}x{Wp}) are beyond the kernels' index arithmetic ({limit} padded pixels"
                          f"{' for ATM-base' if variant == 'base' else ''})")
@@ -81,13 +96,24 @@ class AtmEngine(WorkspaceBytes, NetEngine):
     def check_state_dict(self, state_dict):
         check_state_dict(state_dict, self.variant)
 
+    def _sync_large_frames(self):
+        """The object's limit follows config.yaml's ``atm_large_frames`` key as it is now"""
+        self._call("set_large_frames", int(atm_large_frames_enabled()))
+
     def max_padded_pixels(self):
+        self._sync_large_frames()
         return int(self._fn("object_max_padded_pixels")(self.handle))
 
     def forward(self, frame0, frame1, global_motion=True, out=None):
         """frame0 / frame1: [H,W,C>=3] fp32 contiguous device tensors (not written) -> [H,W,3]."""
         H, W, Cc = check_frames(frame0, frame1)
-        check_frame_size(H, W, self.variant)
+        Hp, Wp = padded_size(H, W)
+        if Hp * Wp > (MAX_PADDED_PIXELS_BASE if self.variant == "base" else MAX_PADDED_PIXELS):
+            # only a frame beyond the 2 GiB limit needs the key: read it now (one config.yaml parse, 0.7 ms, on a frame of 65 ms and more);
+            # every smaller frame runs what it always ran, whatever the key and the object's switch say
+            large = atm_large_frames_enabled()
+            check_frame_size(H, W, self.variant, large)
+            self._call("set_large_frames", int(large))
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
         if global_motion == ENSEMBLE:

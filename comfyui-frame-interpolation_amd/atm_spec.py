@@ -13,7 +13,10 @@ served only when config.yaml's ``atm_base`` key is on (``atm_base_enabled()``); 
 refused as before.
 
 The multi-scale global-motion ensemble ("On with Ensemble (slowest)", for both models) is served only when config.yaml's ``atm_ensemble`` key
-is on (``atm_ensemble_enabled()``); absent or off, the choice is refused by name as before."""
+is on (``atm_ensemble_enabled()``); absent or off, the choice is refused by name as before.
+
+Frames beyond the 2 GiB-per-image limits (2160x3840 for both models) are served only when config.yaml's ``atm_large_frames`` key is on
+(``atm_large_frames_enabled()``); absent or off, the limits and the refusal are what they were."""
 from collections import OrderedDict
 
 CKPT_NAMES = ("atm-vfi-base.pt", "atm-vfi-lite.pt", "atm-vfi-base-pct.pt")      # the reference's widget order
@@ -165,6 +168,13 @@ def atm_ensemble_enabled():
     from . import ckpt
 
     return bool(ckpt.load_config().get("atm_ensemble", False))
+
+
+def atm_large_frames_enabled():
+    """config.yaml's ``atm_large_frames`` key (absent = off), read at call time"""
+    from . import ckpt
+
+    return bool(ckpt.load_config().get("atm_large_frames", False))
 
 
 def check_ckpt_name(ckpt_name):

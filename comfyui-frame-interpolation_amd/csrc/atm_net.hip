@@ -527,7 +527,8 @@ constexpr int kMotion = 5, kTensors = 232;
 // the 1/16 map.  px_floats: the widest per-image buffer in floats per padded pixel (the layers index one image with 32 bits of bytes).  lite:
 // the refinement net's input, local_c / 4 + 5 + 15 = 76 channels padded to 80 (its 2 ref_hid = 64-channel concat buffer is narrower).  base:
 // the refinement net's full-resolution concat buffer (up3 | proj), 2 ref_hid = 128 channels; its input is 116 padded to 120, the last
-// up-sampling level's taps r8(4 * 101) / 4 = 102, the 4 C MLP buffers 1536 / 64.
+// up-sampling level's taps r8(4 * 101) / 4 = 102, the 4 C MLP buffers 1536 / 64.  The limit is signed (every object as created) or unsigned
+// (after vfi_atm_set_large_frames: every layer that meets an image of 2 GiB or more has a large-image form, docs/design/atm.md "4K").
 struct Cfg {
     int hid[4], local_c, global_c, last, mlp_ratio, local_head, global_head, ref_hid, px_floats;
     const char* name;
@@ -565,6 +566,7 @@ struct vfi_atm : PaddedNet {
     vfi_conv_t *proj = nullptr, *down1 = nullptr, *down2[2] = {}, *down3[3] = {}, *up1d = nullptr, *up1c = nullptr, *up2d = nullptr, *up2c = nullptr,
                *up3d = nullptr, *rh[2] = {};
     int variant = 0;
+    bool large = false;      // vfi_atm_set_large_frames: padded frames up to max_padded_pixels_large(px_floats) are served
     // the ensemble's device record: [0..2] the three losses and [3] the chosen level as vfi_atm_select_flow wrote them, [4..6] the losses as the
     // scoring kernels wrote them; ens_ran: an ensemble forward has been enqueued on ens_stream
     float* ens_rec = nullptr;
@@ -843,7 +845,17 @@ extern "C" {
 
 int64_t vfi_atm_max_padded_pixels(void) { return max_padded_pixels(kCfg[0].px_floats); }
 
-int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* m) { return m ? max_padded_pixels(kCfg[m->variant].px_floats) : 0; }
+int64_t vfi_atm_large_max_padded_pixels(int variant) { return variant == 0 || variant == 1 ? max_padded_pixels_large(kCfg[variant].px_floats) : 0; }
+
+int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* m) {
+    return !m ? 0 : (m->large ? max_padded_pixels_large(kCfg[m->variant].px_floats) : max_padded_pixels(kCfg[m->variant].px_floats));
+}
+
+int vfi_atm_set_large_frames(vfi_atm_t* m, int on) {
+    VFI_REQUIRE(m, "vfi_atm_set_large_frames: null object");
+    m->large = on != 0;
+    return 0;
+}
 
 vfi_atm_t* vfi_atm_create(const float* const* tensors, const int64_t* numels, int n_tensors) { return vfi_atm_create_variant(tensors, numels, n_tensors, 0); }
 
@@ -992,7 +1004,7 @@ namespace {
 // the size guard and the workspace key of the two entry points; `who` names the caller in the refusal
 int atm_enter(vfi_atm_t* m, const char* who, int H, int W) {
     const Cfg& g = kCfg[m->variant];
-    return m->enter(who, g.name, H, W, atm_pad64(H), atm_pad64(W), g.px_floats);
+    return m->enter(who, g.name, H, W, atm_pad64(H), atm_pad64(W), g.px_floats, false, m->large);
 }
 
 }  // namespace

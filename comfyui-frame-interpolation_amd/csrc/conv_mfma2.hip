@@ -75,6 +75,8 @@ struct Conv2Geom {
 // row the tile's halo touches (a 64-bit, wave-uniform address), its size the rows the halo spans, and the per-lane offsets count from
 // that row — a few rows of bytes, whatever the image.  Same pieces, same LDS image, same arithmetic: same bits as the plain form wherever
 // both are legal.  The output side needs nothing: the epilogue forms 64-bit addresses already.
+// LARGE with EXT: the one extended feature is the per-channel PReLU (act 3, no residual) — ATM's full-resolution layers.  Padding modes,
+// sigmoid, GELU, the post affine and the interleaved store (EXTF below) are compiled out of it and stay refused above 2 GiB (launch2_tl).
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false, bool LARGE = false>
 __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource / LDS-DMA builtins do not exist in the host pass
@@ -82,7 +84,9 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(!GROUPED || (WN == 4 && NT == 1 && TAPS == 4), "grouped: one 2x2 tap group per wave column");
     static_assert(!TAIL4 || (STRIDE == 2 && TAPS == 9 && CK == 8 && !GROUPED && !MASKED), "live-K tail: stride-2 3x3, 8-channel chunks");
-    static_assert(!LARGE || (!GROUPED && !EXT && !MASKED && !TAIL4), "large images: the plain feature set only");
+    static_assert(!LARGE || (!GROUPED && !MASKED && !TAIL4), "large images: the plain feature set, or per-channel PReLU alone (EXT)");
+    static_assert(!LARGE || !EXT || TAPS != 4, "large images with per-channel PReLU: 3x3 and 1x1 tiles");
+    constexpr bool EXTF = EXT && !LARGE;      // the full extended feature set
     constexpr int KW = G::KW, SUBX = G::SUBX, TWO = G::TWO, THO = G::THO, TWI = G::TWI;
     constexpr int Q = G::Q, C8 = G::C8, BN = G::BN;
 
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
             const int pix = idx / Q, q = idx - pix * Q;
             const int py = pix / TWI, px = pix - py * TWI;
             const int iy = iy0 + py, ix = ix0 + px;
-            if (EXT && a.pad_mode) {  // edge clamp (replicate) or mirror (reflect) instead of the descriptor's zero fill
+            if (EXTF && a.pad_mode) {  // edge clamp (replicate) or mirror (reflect) instead of the descriptor's zero fill
                 const int cy = pad_index(iy, a.Hin, a.pad_mode), cx = pad_index(ix, a.Win, a.pad_mode);
                 avoff[i] = pix < G::NPIX ? ((cy * a.Win + cx) * pstr + q * qstr) * 4 : (int)0x80000000;
             } else {
@@ -381,9 +385,9 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
             }
         } else {
         const bool nhwc = a.out_mode == 0 && !GROUPED;
-        const bool inter = EXT && GROUPED && a.out_mode == 2;       // transposed conv, parity groups interleaved into NHWC
-        const bool fast = a.res == nullptr && (nhwc || inter) && (a.act == 0 || a.act == 1 || (EXT && (a.act == 3 || a.act == 5))) &&
-                          !(EXT && a.post_scale != 0.f);
+        const bool inter = EXTF && GROUPED && a.out_mode == 2;      // transposed conv, parity groups interleaved into NHWC
+        const bool fast = a.res == nullptr && (nhwc || inter) && (a.act == 0 || a.act == 1 || (EXT && (a.act == 3 || (EXTF && a.act == 5)))) &&
+                          !(EXTF && a.post_scale != 0.f);
         if (fast) {
             // element (r) of a sub-tile -> output pixel: NHWC (oy, ox); interleaved (2*oy + gy, 2*ox + gx) of a [2H, 2W] image
             const int m = inter ? 2 : 1;
@@ -409,7 +413,7 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
                                 ob[(r >> 2) * ystr + (r & 3) * xstr] = fmaxf(v, v * uslope);
                             }
                         } else {                    // image border and / or per-channel (or out-of-range) slopes
-                            const bool gelu = EXT && a.act == 5;
+                            const bool gelu = EXTF && a.act == 5;
                             const float sl = a.act == 0 || gelu ? 1.0f : (a.act == 1 ? a.slope : a.prelu[co]);
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
@@ -478,15 +482,15 @@ __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
                         if (a.act == 1) v = v > 0.f ? v : v * a.slope;
                         else if (a.act == 2) v = fminf(fmaxf(v, 0.f), 1.f);
                         else if (EXT && a.act == 3) v = v > 0.f ? v : v * a.prelu[coc];
-                        else if (EXT && a.act == 4) v = 1.0f / (1.0f + expf(-v));
-                        else if (EXT && a.act == 5) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-                        if (EXT && a.post_scale != 0.f) v = v * a.post_scale + a.post_shift;
+                        else if (EXTF && a.act == 4) v = 1.0f / (1.0f + expf(-v));
+                        else if (EXTF && a.act == 5) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+                        if (EXTF && a.post_scale != 0.f) v = v * a.post_scale + a.post_shift;
                         if (cok && oy < a.Hout && ox < a.Wout) {
                             if (GROUPED && a.out_mode == 1) {
                                 const int Ws = 4 * a.Wout, Hs = 4 * a.Hout, c = co >> 2;
                                 const int Yt = 4 * oy + 2 * (g >> 1) + ((co >> 1) & 1), Xt = 4 * ox + 2 * (g & 1) + (co & 1);
                                 outp[((size_t)(n * (a.out_planes ? a.out_planes : 2) + (c >> 2)) * Hs * Ws + (size_t)Yt * Ws + Xt) * 4 + (c & 3)] = v;
-                            } else if (EXT && GROUPED && a.out_mode == 2) {
+                            } else if (EXTF && GROUPED && a.out_mode == 2) {
                                 const size_t q2 = (size_t)(n * 2 * a.Hout + 2 * oy + (g >> 1)) * (2 * a.Wout) + 2 * ox + (g & 1);
                                 outp[q2 * a.out_cs + co] = v;
                             } else {
@@ -587,6 +591,8 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
                       // img_floats), the rows of one tile's halo below 2 GiB (conv_large.h)
         VFI_REQUIRE(large_image_ok(a.Hin, a.Win, a.in_cs, a.huge_ok != 0) && !a.in_plane && !a.pad_mode && large_span_ok(G::THI, a.Win, a.in_cs),
                     "conv2 %s: image larger than 2 GiB", name);
+        // ... and of the extended feature set the per-channel PReLU alone (the kernel has none of the others in this form)
+        VFI_REQUIRE(!EXT || (a.act == 3 && !a.res && a.post_scale == 0.f && a.out_mode == 0), "conv2 %s: image larger than 2 GiB", name);
     } else {
         VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
     }
@@ -615,6 +621,21 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         occ_of[dev].store(occ, std::memory_order_release);   // (two threads racing here compute the same values)
     }
     const int cus = cus_of[dev].load(std::memory_order_relaxed);
+    // A LARGE form decides its K split with the occupancy of its plain twin: the two differ in registers (d1_m1n1 with per-channel PReLU: 4
+    // resident workgroups against 3), the split sets the summation order, and both forms must give the same bits wherever both are legal.
+    int occ_k = occ;
+    if constexpr (LARGE) {
+        static std::atomic<int> occ_plain_of[kMaxDevices];
+        occ_k = occ_plain_of[dev].load(std::memory_order_acquire);
+        if (!occ_k) {
+            const void* twin = reinterpret_cast<const void*>(&conv_mfma2_kernel<STRIDE, TAPS, MT, NT, WM, WN, CK, GROUPED, EXT, MASKED, TAIL4, false>);
+            VFI_CHECK_HIP(hipFuncSetAttribute(twin, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
+            int o = 0;
+            VFI_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, twin, 256, G::LDS_BYTES));
+            occ_k = o < 1 ? 1 : o;
+            occ_plain_of[dev].store(occ_k, std::memory_order_release);
+        }
+    }
     const int T = a.N * a.tiles_x * a.tiles_y;
     const int ny = a.Cout_p / G::BN;
     // ---- split-K: a coarse pyramid level with many input channels (FILM's 1920 -> 256 at 16 x 30: 32 workgroups, each walking
@@ -624,12 +645,12 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
     int ks = 1;
     if (!GROUPED && !MASKED && a.out_mode == 0 && a.split_ok && split_enabled()) {
         const int nchunks = a.Cin_p / CK;
-        const long wgs = (long)T * ny, want = 3L * cus * occ;
+        const long wgs = (long)T * ny, want = 3L * cus * occ_k;
         // ... and a K loop long enough that a fraction of it outweighs the reduce launch (~20 us): 32 chunks of a 3x3 layer
         // (IFUNet's 128-channel layers at 16 chunks lost 0.7 ms per frame to their reduces)
         // — or so few workgroups that the layer leaves 7/8 of the chip idle (FILM's 128-channel layers at 16 x 30 and 33 x 60)
-        const bool long_k = TAPS * nchunks >= 288, tiny = wgs * 8 <= (long)cus * occ && nchunks >= 16;
-        if (wgs < (long)cus * occ && (long_k || tiny)) {      // less than one resident wave of workgroups
+        const bool long_k = TAPS * nchunks >= 288, tiny = wgs * 8 <= (long)cus * occ_k && nchunks >= 16;
+        if (wgs < (long)cus * occ_k && (long_k || tiny)) {      // less than one resident wave of workgroups
             ks = (int)((want + wgs - 1) / wgs);
             ks = ks > nchunks / 8 ? nchunks / 8 : ks;
             ks = ks > 16 ? 16 : ks;
@@ -701,11 +722,16 @@ static int launch2_t(const ConvArgs& a, hipStream_t s, const char* name) {
 
 // The tiles conv_pick_variant gives the plain layer forms (3x3 stride 1 / 2, 2x2 and 1x1 stride 1) also exist in the LARGE form.  It is
 // taken only from the size on (conv_input_large: 2 GiB, or what the test option large_image_bytes says); every smaller launch takes
-// launch2_t as before.  Layers with the extended feature set and every other tile keep the plain form and its 2 GiB guard.
+// launch2_t as before.  Of the extended feature set the 3x3 and 1x1 tiles serve one layer form large: per-channel PReLU (act 3) with zero
+// padding, no residual and no post affine.  Every other extended layer and every other tile keep the plain form and its 2 GiB guard.
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK>
 static int launch2_tl(const ConvArgs& a, hipStream_t s, const char* name) {
     const bool ext = a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
     if (!ext && !a.in_plane && conv_input_large(a)) return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, false, false, false, true>(a, s, name);
+    if constexpr (TAPS != 4) {
+        const bool prelu_only = a.act == 3 && !a.pad_mode && a.post_scale == 0.f && a.out_mode == 0 && !a.res;
+        if (prelu_only && !a.in_plane && conv_input_large(a)) return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, true, false, false, true>(a, s, name);
+    }
     return launch2_t<STRIDE, TAPS, MT, NT, WM, WN, CK, false>(a, s, name);
 }
 

@@ -870,7 +870,8 @@ static int wino_cus(int dev) {
 }
 
 // Large images: an operand (input, output, residual) of one image at or over the mark (conv_bytes_large).  The LARGE instantiations exist
-// for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual, and operands below 4 GiB — with the
+// for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual and per-channel PReLU without one (the hot
+// MODE 1; residual + PReLU, MODE 13, has no LARGE form and stays refused), and operands below 4 GiB — with the
 // layer object's permission (ConvArgs::huge_ok) up to kConvHugeMaxFloats floats each (conv_large.h: the kernel keeps an image's floats in an
 // int and forms every address from a per-region 64-bit base).
 static long wino_operand_bytes(const ConvArgs& a) {
@@ -881,7 +882,8 @@ static long wino_operand_bytes(const ConvArgs& a) {
 static bool wino_large(const ConvArgs& a) { return a.out_mode == 0 && conv_bytes_large(wino_operand_bytes(a)); }
 static bool wino_large_ok(const ConvArgs& a) {
     const long bytes = wino_operand_bytes(a);
-    return (a.huge_ok ? bytes / 4 <= kConvHugeMaxFloats : bytes <= kConvLargeMaxBytes) && !a.pad_mode && !a.in_plane && a.act >= 0 && a.act <= 2 && a.post_scale == 0.f;
+    return (a.huge_ok ? bytes / 4 <= kConvHugeMaxFloats : bytes <= kConvLargeMaxBytes) && !a.pad_mode && !a.in_plane && a.act >= 0 &&
+           (a.act <= 2 || (a.act == 3 && !a.res)) && a.post_scale == 0.f;
 }
 
 // Is the Winograd kernel the better choice for this layer on this launch?  (3x3 stride 1 only; enough work items to fill the
@@ -992,6 +994,7 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
                     "conv_wino %s: image larger than 2 GiB", name);
         switch (mode) {
             case 0: return wino_launch_t<8, 0, 0, 0, true>(p, s, name);
+            case 1: return wino_launch_t<8, 1, 0, 0, true>(p, s, name);
             case 10: return wino_launch_t<8, 10, 0, 0, true>(p, s, name);
             case 11: return wino_launch_t<8, 11, 0, 0, true>(p, s, name);
             default: return wino_launch_t<8, 12, 0, 0, true>(p, s, name);

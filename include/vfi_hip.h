@@ -238,7 +238,11 @@ int vfi_conv_accept_odd(vfi_conv_t* conv, int on);
  * is refused ("image larger than 2 GiB") unless the object was given this permission: then the same forms serve operand images of up to
  * vfi_conv_huge_max_floats() = 2^31 - 1 floats (8 GiB - 4 bytes) each, the bound of the audited arithmetic (an image's float count is kept
  * in an int; every address is a 64-bit per-tile base plus an offset of a few rows).  Off by default, a property of the object; no launch
- * that was legal without it changes its kernel, its geometry or a bit of its output.  The extended forms keep their 2 GiB refusal. */
+ * that was legal without it changes its kernel, its geometry or a bit of its output.  Of the extended feature set one layer form is served
+ * in the same way and to the same bounds: per-channel PReLU (act 3) with zero padding, no residual and no post affine, by the Winograd kernel
+ * (3x3 stride 1) and the direct kernel (3x3 stride 1 / 2, 1x1) — ATM's full-resolution layers, operands of 2.67 to 4.28 GB at 2160 x 3840.
+ * The other extended forms (replicate / reflect padding, sigmoid, GELU, post affine, transposed convolutions, residual + PReLU) keep their
+ * 2 GiB refusal. */
 int vfi_conv_allow_huge(vfi_conv_t* conv, int on);
 int64_t vfi_conv_huge_max_floats(void);
 int vfi_conv_forward_ex(const vfi_conv_t* conv, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs,
@@ -845,7 +849,12 @@ void vfi_atm_destroy(vfi_atm_t* net);
  * is ATM-lite's limit; the limit that vfi_atm_forward applies is the object's own, vfi_atm_object_max_padded_pixels(net): for ATM-base
  * (2^31 - 1) / 512 = 4 194 303 pixels, its widest per-image buffer being the refinement net's full-resolution concat buffer of 2 * 64 = 128
  * channels (its input is 116 channels padded to 120, the last transposed convolution's taps r8(4 * 101) / 4 = 102 floats per full-resolution
- * pixel, the 4 C MLP buffers 1536 / 64): 1472 x 2560 fits, 2176 x 3840 does not. */
+ * pixel, the 4 C MLP buffers 1536 / 64): 1472 x 2560 fits, 2176 x 3840 does not.
+ * After vfi_atm_set_large_frames(net, 1) the limit of that object is vfi_atm_large_max_padded_pixels(variant): (2^32 - 1) / 320 = 13 421 772
+ * pixels for ATM-lite, (2^32 - 1) / 512 = 8 388 607 for ATM-base (2160 x 3840, padded 2176 x 3840 = 8 355 840, fits both).  The layers whose
+ * operand image holds 2 GiB or more take the large-image form of their kernel, which addresses an image below 4 GiB; ATM's full-resolution
+ * layers are Conv2d + per-channel PReLU, which the Winograd kernel (3x3 stride 1) and the direct kernel (3x3 stride 1 / 2, 1x1) have in
+ * that form (docs/design/atm.md "4K" lists every buffer and kernel concerned). */
 int vfi_atm_forward(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, int global_motion, float* out_dev, void* stream);
 /* Network.forward_global_ensemble (network_lite.py:599-704; network_base.py has the same code)["I_t"] for ONE pair: "On with Ensemble
  * (slowest)".  Frames and out_dev as vfi_atm_forward's.  The global branch (feature extractor, last_feat_extract, global fusion, two ATM blocks,
@@ -861,6 +870,11 @@ int vfi_atm_forward(vfi_atm_t* net, const float* frame0_dev, const float* frame1
 int vfi_atm_forward_ensemble(vfi_atm_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, float* out_dev, void* stream);
 int64_t vfi_atm_max_padded_pixels(void);
 int64_t vfi_atm_object_max_padded_pixels(const vfi_atm_t* net);
+/* the limit of a variant (0 = ATM-lite, 1 = ATM-base; 0 for any other) with large frames on; vfi_atm_object_max_padded_pixels follows the switch */
+int64_t vfi_atm_large_max_padded_pixels(int variant);
+/* on != 0: the object serves padded frames up to vfi_atm_large_max_padded_pixels(its variant), in all three global-motion modes; 0 (every
+ * object as created): up to its limit above.  Changes no result at a size both serve. */
+int vfi_atm_set_large_frames(vfi_atm_t* net, int on);
 int vfi_atm_release_workspace(vfi_atm_t* net);
 int64_t vfi_atm_workspace_bytes(const vfi_atm_t* net);
 
