@@ -225,6 +225,10 @@ PROTOTYPES = {
     "vfi_flavr_forward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_flavr_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_flavr_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "vfi_flavr_max_padded_pixels": (C.c_int64, []),
+    "vfi_flavr_large_max_padded_pixels": (C.c_int64, []),
+    "vfi_flavr_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
+    "vfi_flavr_set_large_frames": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_amt_pool_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_amt_corr_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_int, C.c_void_p]),

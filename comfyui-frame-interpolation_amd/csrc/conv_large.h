@@ -38,6 +38,17 @@ __host__ __device__ inline int large_span_bytes(int rows, int W, int cs) { retur
 // byte offset of float `f` of pixel (iy, ix) from the descriptor's base: pixels are pstr floats apart
 __host__ __device__ inline int large_lane_bytes(int iy, int r0, int W, int ix, int pstr, int f) { return (((iy - r0) * W + ix) * pstr + f) * 4; }
 
+// ---- the transposed convolution's interleaved store (conv_wino.hip: SHUF 2 in its LARGE form) ----
+// A region of RH input rows from oy0 writes the output rows [2 oy0, 2 oy0 + 2 RH) of the [2H, 2W] image of cs-float pixels; its descriptor
+// starts at output row 2 oy0 of image n and spans those rows, cut at the image's end.
+__host__ __device__ inline int large_deconv_rows(int H, int oy0, int RH) { return large_rows(2 * H, 2 * oy0, 2 * RH); }
+__host__ __device__ inline size_t large_deconv_base_floats(int n, int H, int oy0, int W, int cs) { return large_row_base_floats(n, 2 * H, 2 * oy0, 2 * W, cs); }
+__host__ __device__ inline int large_deconv_span_bytes(int rows, int W, int cs) { return large_span_bytes(rows, 2 * W, cs); }
+// byte offsets from that base.  Lane part: parity g = 2 py + px of the lane's channel group, channel cg of out_cs, the lane's first input column
+__host__ __device__ inline int large_deconv_lane_bytes(int g, int xlane, int W, int cs, int cg) { return (((g >> 1) * 2 * W + (g & 1) + 2 * xlane) * cs + cg) * 4; }
+// ... per-store part: input row oyr of the region (two output rows each), input column xq from the lane's first
+__host__ __device__ inline int large_deconv_store_bytes(int oyr, int xq, int W, int cs) { return oyr * 4 * W * cs * 4 + 2 * xq * cs * 4; }
+
 // Host side: may one operand image of H x W pixels of cs floats be served?  huge = the layer object's permission.
 inline bool large_image_ok(int H, int W, int cs, bool huge) {
     const long floats = (long)H * W * cs;

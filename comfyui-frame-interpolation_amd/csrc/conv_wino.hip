@@ -160,6 +160,8 @@ __device__ __forceinline__ f32x2 wino_pk_mul(f32x2 x, f32x2 y) {
 //     channel cg.  No residual in either form.
 // LARGE (SHUF 0): an output / residual image of 2 GiB or more — the descriptors start at the region's first row and span the region's rows
 // (64-bit, wave-uniform base), so the row part of every offset counts from there and stays small; the same stores in the same order.
+// LARGE with SHUF 2 (MODE 0 only): the same for the interleaved [2H, 2W] output — the descriptor starts at output row 2 oy0 and spans the
+// region's 2 RH output rows; the lane part (parity row and column, channel) is the plain form's.
 template <int RTX, int MODE, bool FULL = false, int SHUF = 0, bool LARGE = false>
 __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const ConvArgs& a, int n, int oy0, int ox0, int co, int coc, int half, float bs,
                                               float bt, float pre, int LO = 0, float inv_LO = 0.f, int gray = 0) {
@@ -168,9 +170,10 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
     const float ps = a.post_scale != 0.f ? a.post_scale : 1.0f, sh = a.post_scale != 0.f ? a.post_shift : 0.0f;
     const int planes = a.out_planes ? a.out_planes : 2;
     const int Ws4 = 4 * W;                       // SHUF: T row length in pixels
-    static_assert(!LARGE || SHUF == 0, "large images: NHWC stores only");
-    const int lrows = LARGE ? large_rows(H, oy0, 2 * (32 / RTX)) : 0;      // LARGE: the rows of the region that exist
+    static_assert(!LARGE || SHUF == 0 || (SHUF == 2 && MODE == 0), "large images: NHWC stores only");
+    const int lrows = !LARGE ? 0 : SHUF == 2 ? large_deconv_rows(H, oy0, 2 * (32 / RTX)) : large_rows(H, oy0, 2 * (32 / RTX));      // LARGE: the (output) rows of the region that exist
     const __amdgpu_buffer_rsrc_t orsrc =
+        LARGE && SHUF == 2 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + large_deconv_base_floats(n, H, oy0, W, a.out_cs)), 0, large_deconv_span_bytes(lrows, W, a.out_cs), 0x00020000) :
         LARGE ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + large_row_base_floats(n, H, oy0, W, a.out_cs)), 0, large_span_bytes(lrows, W, a.out_cs), 0x00020000) :
         SHUF == 1 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * planes * 16 * H * W * 4), 0, planes * 16 * H * W * 16, 0x00020000)
         : SHUF == 2 ? __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * 4 * H * W * a.out_cs), 0, 4 * H * W * a.out_cs * 4, 0x00020000)
@@ -192,6 +195,7 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
         g ^= (g >> 1) & gray;      // gray = 1: the groups sit in the order p00 p01 p11 p10 (wino_gray_order); N position -> parity 2 py + px
         const int c = cg >> 2;
         if (SHUF == 1) lane_o = ((((c >> 2) * 4 * H + 2 * (g >> 1) + ((cg >> 1) & 1)) * Ws4 + 2 * (g & 1) + (cg & 1) + 4 * xlane) * 4 + (c & 3)) * 4;
+        else if (LARGE) lane_o = large_deconv_lane_bytes(g, xlane, W, a.out_cs, cg);      // (conv_large.h: the plain form's expression, below)
         else lane_o = (((g >> 1) * 2 * W + (g & 1) + 2 * xlane) * a.out_cs + cg) * 4;
     }
     // Two tiles (accumulator registers r, r + 1 = neighbours in x) per step, in packed fp32: the epilogue's VALU work is not hidden by
@@ -229,7 +233,7 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
             const int oy = oy0 + 2 * tyy + ey;          // wave-uniform
             if (FULL || oy < H) {
                 const int oyr = LARGE ? oy - oy0 : oy;      // the row the descriptors count from
-                const int rowo = SHUF == 1 ? oy * 4 * Ws4 * 16 : (SHUF == 2 ? oy * 4 * W * a.out_cs * 4 : oyr * W * a.out_cs * 4), rowr = oyr * W * a.res_cs * 4;
+                const int rowo = SHUF == 1 ? oy * 4 * Ws4 * 16 : (SHUF == 2 ? (LARGE ? large_deconv_store_bytes(oyr, 0, W, a.out_cs) : oy * 4 * W * a.out_cs * 4) : oyr * W * a.out_cs * 4), rowr = oyr * W * a.res_cs * 4;
 #pragma unroll
                 for (int ex = 0; ex < 2; ++ex) {
                     f32x2 v2 = wino_pk_mul_hi(wino_pk_add_lo(y[ey * 2 + ex], bsbt), bsbt);
@@ -254,7 +258,7 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Con
                             else if (MODE == 15) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
                             v = v * ps + sh;
                         }
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), orsrc, ok ? lane_o : (int)0x80000000, rowo + (SHUF == 1 ? xq * 64 : (SHUF == 2 ? 2 * xq * a.out_cs * 4 : xq * a.out_cs * 4)), 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), orsrc, ok ? lane_o : (int)0x80000000, rowo + (SHUF == 1 ? xq * 64 : (SHUF == 2 ? (LARGE ? large_deconv_store_bytes(0, xq, W, a.out_cs) : 2 * xq * a.out_cs * 4) : xq * a.out_cs * 4)), 0);
                     }
                 }
             }
@@ -874,14 +878,18 @@ static int wino_cus(int dev) {
 // MODE 1; residual + PReLU, MODE 13, has no LARGE form and stays refused), and operands below 4 GiB — with the
 // layer object's permission (ConvArgs::huge_ok) up to kConvHugeMaxFloats floats each (conv_large.h: the kernel keeps an image's floats in an
 // int and forms every address from a per-region 64-bit base).
+// The transposed convolution of a layer object (out_mode 2) has one LARGE form: the hot epilogue (MODE 0: none / LeakyReLU with a slope in
+// [0,1]), zero padding, no residual, no post affine.  Its operands are the input image and the interleaved [2 Hin, 2 Win] output image.
 static long wino_operand_bytes(const ConvArgs& a) {
     const long px = (long)a.Hin * a.Win;
+    if (a.out_mode == 2) return px * 4 * (a.in_cs > 4 * a.out_cs ? a.in_cs : 4 * a.out_cs);
     const long m = (a.in_cs > a.out_cs ? a.in_cs : a.out_cs);
     return px * 4 * (a.res && a.res_cs > m ? a.res_cs : m);
 }
-static bool wino_large(const ConvArgs& a) { return a.out_mode == 0 && conv_bytes_large(wino_operand_bytes(a)); }
+static bool wino_large(const ConvArgs& a) { return (a.out_mode == 0 || a.out_mode == 2) && conv_bytes_large(wino_operand_bytes(a)); }
 static bool wino_large_ok(const ConvArgs& a) {
     const long bytes = wino_operand_bytes(a);
+    if (a.out_mode == 2 && (a.res || !(a.act == 0 || (a.act == 1 && a.slope >= 0.f && a.slope <= 1.f)))) return false;
     return (a.huge_ok ? bytes / 4 <= kConvHugeMaxFloats : bytes <= kConvLargeMaxBytes) && !a.pad_mode && !a.in_plane && a.act >= 0 &&
            (a.act <= 2 || (a.act == 3 && !a.res)) && a.post_scale == 0.f;
 }
@@ -950,7 +958,7 @@ static int wino_launch_t(WinoArgs& p, hipStream_t s, const char* name) {
     grid = round_up(grid, 8);
     p.xcd_map = option(kOptWinoXcd) ? 1 : 0;
     p.clk_tag = clock_probe_tag(name);
-    conv_record_launch(kConvFamilyWino, RTX, MODE, LARGE ? 3 : SHUF, 1, grid, items);
+    conv_record_launch(kConvFamilyWino, RTX, MODE, LARGE ? (SHUF == 2 ? kWinoStoreLargeDeconv : 3) : SHUF, 1, grid, items);
     if (LARGE) conv_record_large(kConvFamilyWino, a);
     TraceScope ts(name, s);
     hipLaunchKernelGGL((conv_wino_kernel<RTX, MODE, SHUF, PROBE, LARGE>), dim3(grid), dim3(256), G::LDS_BYTES, s, p);
@@ -966,6 +974,11 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
                 name, a.Cin_p, a.Cout_p, a.in_cs);
     VFI_REQUIRE(((uintptr_t)a.in & 15) == 0 && ((uintptr_t)a.w & 15) == 0, "conv_wino %s: unaligned pointers", name);
     const bool large = wino_large(a) && wino_large_ok(a);      // a layer without a LARGE instantiation keeps the plain form and its guards
+    // the transposed form over its bounds says which bound: 4 GiB per operand on its own, kConvHugeMaxFloats floats with the permission
+    VFI_REQUIRE(large || a.out_mode != 2 || a.act == 3 || wino_operand_bytes(a) < 0x7fffffffL,
+                "conv_wino %s: image larger than 2 GiB: the transposed convolution serves operand images below 4 GiB, and up to 2^31 - 1 floats with "
+                "vfi_conv_allow_huge (input %ld floats, output %ld floats, permission %s)",
+                name, (long)a.Hin * a.Win * a.in_cs, 4L * a.Hin * a.Win * a.out_cs, a.huge_ok ? "on" : "off");
     VFI_REQUIRE(large || (long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv_wino %s: image larger than 2 GiB", name);
     VFI_REQUIRE(a.act != 3 || a.prelu, "conv_wino %s: act 3 needs per-channel slopes", name);
     WinoArgs p;
@@ -989,6 +1002,11 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
     const bool ext = a.res != nullptr || a.post_scale != 0.f || !(a.act == 0 || (a.act == 1 && a.slope >= 0.f && a.slope <= 1.f) || a.act == 3);
     VFI_REQUIRE(a.act >= 0 && a.act <= 5, "conv_wino %s: activation code %d", name, a.act);
     const int mode = ext ? 10 + a.act : (a.act == 3 ? 1 : 0);      // wino_epilogue's MODE: one kernel per general activation
+    if (large && a.out_mode == 2) {      // the transposed convolution: a region's patch spans 10 input rows, its stores 16 output rows of 2 Win pixels
+        VFI_REQUIRE(a.Cout % 4 == 0 && mode == 0, "conv_wino %s: the large transposed-convolution form takes none / LeakyReLU only", name);
+        VFI_REQUIRE(large_span_ok(10, a.Win, a.in_cs) && large_span_ok(16, 2 * a.Win, a.out_cs), "conv_wino %s: image larger than 2 GiB", name);
+        return wino_launch_t<8, 0, 2, 0, true>(p, s, name);
+    }
     if (large) {      // 16x8 regions whatever the fill (the region shape changes no bit); the row span of a patch stays far below 2 GiB
         VFI_REQUIRE((long)10 * a.Win * (a.in_cs > a.out_cs ? a.in_cs : a.out_cs) * 4 < 0x7fffffffL && (!a.res || (long)10 * a.Win * a.res_cs * 4 < 0x7fffffffL),
                     "conv_wino %s: image larger than 2 GiB", name);

@@ -371,6 +371,7 @@ struct vfi_flavr : NetObject {
     float* cat[4] = {};                                // (dx_0 | x_0) [P/4, 6, 128], (dx_1 | x_1) [P/4, 6, 128], (dx_2 | x_2) [P/16, 6, 256], (dx_3 | x_3) [P/64, 6, 512]
     float *sub = nullptr, *dsout = nullptr;            // sub-sampled input / output of a downsample convolution, [pixels, 4, C]
     float *fin = nullptr, *fused = nullptr;            // last up-convolution [P, 4 * 64], feature_fuse [P, 64]
+    bool large = false;                                // vfi_flavr_set_large_frames: padded frames up to kLargeMaxPixels are served
 };
 
 namespace {
@@ -472,6 +473,13 @@ int forward_window(vfi_flavr* m, const float* const* frames, int C, int H, int W
 // the largest padded frame: the last up-convolution's [Hp, Wp, 4 * 64] output must stay below the convolution kernels' 2^31-byte image limit
 // (every other tensor is smaller: the widest bordered one, [Hp/2, Wp/2, 6 * 128], is 3/4 of it)
 bool size_ok(int Hp, int Wp) { return (long)Hp * Wp * T * 64 * 4 < 0x7fffffffL; }
+constexpr long kMaxPixels = (0x7fffffffL / 4 - 1) / (T * 64);      // 2 097 151: what size_ok admits
+// ... with vfi_flavr_set_large_frames: the same tensor, the widest operand image of any layer, must fit the layer kernels' bound for one
+// operand with the permission (conv_large.h: kConvHugeMaxFloats floats); the layers that meet an image of 2 GiB or more all have a
+// large form (docs/design/flavr.md "4K")
+constexpr long kLargeMaxPixels = kConvHugeMaxFloats / (T * 64);      // 8 388 607
+static_assert(kMaxPixels == 2097151 && kLargeMaxPixels == 8388607, "FLAVR's frame limits");
+bool size_ok_large(int Hp, int Wp) { return (long)Hp * Wp <= kLargeMaxPixels; }
 
 }  // namespace
 
@@ -630,14 +638,34 @@ int vfi_flavr_release_workspace(vfi_flavr_t* m) {
 
 int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* m) { return m ? m->ws.bytes() : 0; }
 
+int64_t vfi_flavr_max_padded_pixels(void) { return kMaxPixels; }
+
+int64_t vfi_flavr_large_max_padded_pixels(void) { return kLargeMaxPixels; }
+
+int64_t vfi_flavr_object_max_padded_pixels(const vfi_flavr_t* m) { return !m ? 0 : (m->large ? kLargeMaxPixels : kMaxPixels); }
+
+// The permission for operand images of 4 GiB and more goes to every layer object with the switch (and leaves with it): below the old limit
+// no layer meets an image of 2 GiB, so the permission changes no launch there.
+int vfi_flavr_set_large_frames(vfi_flavr_t* m, int on) {
+    VFI_REQUIRE(m, "vfi_flavr_set_large_frames: null object");
+    for (vfi_conv_t* L : m->layers)
+        if (vfi_conv_allow_huge(L, on != 0)) return -1;
+    m->large = on != 0;
+    return 0;
+}
+
 int vfi_flavr_forward(vfi_flavr_t* m, const float* const* frames_dev, int N, int C, int H, int W, float* out_dev, void* stream) {
     VFI_REQUIRE(m && frames_dev && out_dev && N > 0 && C >= 3 && H > 0 && W > 0, "vfi_flavr_forward: bad arguments");
     for (int i = 0; i < T * N; ++i) VFI_REQUIRE(frames_dev[i], "vfi_flavr_forward: null frame pointer %d", i);
     const int Hp = pad16(H), Wp = pad16(W);
-    VFI_REQUIRE(size_ok(Hp, Wp),
+    VFI_REQUIRE(m->large || size_ok(Hp, Wp),
                 "vfi_flavr_forward: a %dx%d frame (padded %dx%d) is over the size limit: the last up-convolution's [Hp, Wp, 256] fp32 tensor must stay "
                 "below 2 GiB (Hp * Wp <= 2097151; 1088x1920 fits)",
                 H, W, Hp, Wp);
+    VFI_REQUIRE(!m->large || size_ok_large(Hp, Wp),
+                "vfi_flavr_forward: a %dx%d frame (padded %dx%d) is over the size limit with large frames on: the last up-convolution's [Hp, Wp, 256] fp32 "
+                "tensor must stay within the layer kernels' 2^31 - 1 floats per image (Hp * Wp <= %ld; 2160x3840 fits)",
+                H, W, Hp, Wp, kLargeMaxPixels);
     hipStream_t st = (hipStream_t)stream;
     if (ensure_workspace(m, Hp, Wp, st)) return -1;
     for (int n = 0; n < N; ++n)

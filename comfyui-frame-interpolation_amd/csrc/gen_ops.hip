@@ -594,7 +594,14 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
         // ... and from 128 x 128 input pixels up: below that (the 34x60 / 68x120 pyramid levels at 1080p, K = 256 ... 768) the direct kernel's
         // split-K wins by 10-75 % whatever the item count (profiles/r05_deconv_ab.txt: 512->256 @34x60 153 vs 267 us, 256->128 @68x120 114 vs 143 us;
         // from 136x240 up the Winograd form wins: 64->16 @544x960 339 vs 696 us)
-        if (regions / 4 * (b.Cout_p / 32) >= 192 && (long)Hin * Win >= 16384 && (long)4 * Hin * Win * out_cs * 4 < 0x7fffffffL && (long)Hin * Win * in_cs * 4 < 0x7fffffffL)
+        // An input or a 4x output image at or over the mark (conv_bytes_large) takes the form's LARGE instantiation, which exists for the hot
+        // epilogue (none / LeakyReLU) only: conv_wino_launch serves it below 4 GiB per operand, with the object's permission up to
+        // kConvHugeMaxFloats floats, and refuses it beyond.  Per-channel PReLU has no large form: above 2 GiB it stays with the grouped
+        // direct tiles (tile 43 refuses an input over 2 GiB; the first-generation tile 13 indexes floats and has no such guard).  Under the default mark `below` and `large_form` exclude each other, so no launch below it changes.
+        const long in_bytes = (long)Hin * Win * in_cs * 4, out_bytes = (long)4 * Hin * Win * out_cs * 4;
+        const bool below = out_bytes < 0x7fffffffL && in_bytes < 0x7fffffffL;
+        const bool large_form = act != 3 && conv_bytes_large(in_bytes > out_bytes ? in_bytes : out_bytes);
+        if (regions / 4 * (b.Cout_p / 32) >= 192 && (long)Hin * Win >= 16384 && (below || large_form))
             return conv_wino_launch(b, 8, (hipStream_t)stream, it->second);
     }
     return conv_launch(a, c->kind == 1 ? 1 : c->stride, c->kind == 1, -1, (hipStream_t)stream, it->second);

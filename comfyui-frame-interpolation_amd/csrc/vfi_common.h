@@ -94,8 +94,9 @@ int variant_override(const char* trace_name);      // tile variant forced for a 
 // What the calling thread's last convolution launch was (vfi_test_last_conv_launch): written by the host-side launchers launch_t,
 // launch2_e and wino_launch_t.  Stores under VFI_TEST_TAPS only; in the product library both are empty functions.
 //   family 1 / 2 = first / second generation direct kernel, 3 = Winograd;  form: direct 0 plain, 1 EXT, 2 MASKED, 3 LARGE; Winograd MODE;
-//   store: out_mode (direct) / SHUF (Winograd; 3 = the LARGE form, whose store is SHUF 0's);  ks: split-K slices (1 = unsplit);  work: tiles (direct) / work items (Winograd)
+//   store: out_mode (direct) / SHUF (Winograd; 3 = the LARGE form, whose store is SHUF 0's; 5 = 3 + 2, the LARGE form of SHUF 2, the transposed convolution);  ks: split-K slices (1 = unsplit);  work: tiles (direct) / work items (Winograd)
 enum { kConvFamilyGen1 = 1, kConvFamilyGen2 = 2, kConvFamilyWino = 3 };
+enum { kWinoStoreLargeDeconv = 5 };
 void conv_record_variant(int variant);      // conv_launch: the direct variant id in the common numbering, kept for the launcher's record
 void conv_record_launch(int family, int wino_region, int form, int store, int ks, long grid_x, long work);   // wino_region: 8 / 16, direct: 0
 int conv_record_read(int32_t* out, int cap);

@@ -703,10 +703,22 @@ void vfi_flavr_destroy(vfi_flavr_t* net);
 /* unpad(model([pad(f) for f in window])[0]) for N windows in one call (vfi_models/flavr/__init__.py:67-84): frames_dev = host array of 4 N
  * device pointers to [H,W,C] fp32 frames (window n = pointers 4 n .. 4 n + 3; C >= 3; not written), out_dev [N,H,W,3].  The windows run
  * one after another through the same launches as a call with one window, so a window's result does not depend on its batch mates; the
- * workspace is sized for one window.  Frames whose padded size exceeds 2^21 - 1 pixels (1088 x 1920 fits) are refused before any launch. */
+ * workspace is sized for one window.  Frames whose padded size exceeds 2^21 - 1 pixels (1088 x 1920 fits) are refused before any launch
+ * (vfi_flavr_set_large_frames below raises that limit to 8 388 607). */
 int vfi_flavr_forward(vfi_flavr_t* net, const float* const* frames_dev, int N, int C, int H, int W, float* out_dev, void* stream);
 int vfi_flavr_release_workspace(vfi_flavr_t* net);
 int64_t vfi_flavr_workspace_bytes(const vfi_flavr_t* net);
+/* The largest padded frame (Hp * Wp, sides rounded up to multiples of 16) an object serves as created: 2 097 151, the last up-convolution's
+ * [Hp, Wp, 256] fp32 tensor below 2 GiB.  After vfi_flavr_set_large_frames(net, 1) the limit of that object is
+ * vfi_flavr_large_max_padded_pixels() = (2^31 - 1) / 256 = 8 388 607 (2160 x 3840 fits, 2176 x 3856 does not): the same tensor within the
+ * layer kernels' bound for one operand image, every layer object with vfi_conv_allow_huge; about 6.24 KB of workspace per padded pixel.
+ * vfi_flavr_object_max_padded_pixels(net) is the limit vfi_flavr_forward applies (0 for a null object).  Frames at or under the first limit
+ * take the same launches with the switch on or off. */
+int64_t vfi_flavr_max_padded_pixels(void);
+int64_t vfi_flavr_large_max_padded_pixels(void);
+int64_t vfi_flavr_object_max_padded_pixels(const vfi_flavr_t* net);
+/* on != 0: the object serves padded frames up to vfi_flavr_large_max_padded_pixels(); 0 (every object as created): up to vfi_flavr_max_padded_pixels() */
+int vfi_flavr_set_large_frames(vfi_flavr_t* net, int on);
 
 /* ---- AMT (vfi_models/amt/amt_arch.py AMT_S / AMT_L / AMT_G): the kernels beside the layer objects ------------------------------------------- */
 
