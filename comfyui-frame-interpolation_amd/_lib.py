@@ -212,6 +212,12 @@ PROTOTYPES = {
                                          C.c_void_p, C.c_void_p]),
     "vfi_sepconvnet_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_sepconvnet_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "vfi_sepconv_pair_out_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vfi_sepconvnet_set_large_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfi_sepconvnet_max_pixels": (C.c_int64, []),
+    "vfi_sepconvnet_large_max_pixels": (C.c_int64, []),
+    "vfi_sepconvnet_object_max_pixels": (C.c_int64, [C.c_void_p]),
     "vfi_flavr_frame_in": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "vfi_flavr_stem": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "vfi_flavr_down1x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

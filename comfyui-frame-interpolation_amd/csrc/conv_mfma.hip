@@ -361,7 +361,8 @@ int conv_pick_variant(const ConvArgs& a, int stride, bool grouped) {
     // The layer objects (split_ok: FILM / M2M / ..., batch fixed by the model) size the choice by the launch; the RIFE network, whose
     // launches carry 1..32 tasks, by the image at a nominal 8 tasks: tile variants differ in K-chunk size, i.e. in fp32 summation
     // order, and a frame's result must not depend on how many tasks shared its launch (tests/test_gpu_rife.py: bit-equal).
-    const long px = (long)(a.split_ok ? a.N : 8) * a.Hout * a.Wout;
+    const int rows = stride == 1 && !grouped && conv_decide_rows(-1) > 0 ? conv_decide_rows(-1) : a.Hout;      // a band is sized as its frame
+    const long px = (long)(a.split_ok ? a.N : 8) * rows * a.Wout;
     // up-sample x2 + 2x2 (tap masks): the 16x8x64 tile with 16-channel chunks — 2 .. 8 K-steps per barrier where the 8-channel chunk has 1 .. 4
     // (tools/film_variant_ab.py at 1080p, ms for FILM's three layers: m2n2 2.40, m1n2 2.26, m2n2k16 2.27, m1n2k16 2.07)
     if (!grouped && stride == 1 && a.ntaps == 4 && a.tapmask) return kConv2Base + (a.Cin_p % 16 == 0 ? 28 : 26);

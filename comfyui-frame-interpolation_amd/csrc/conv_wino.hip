@@ -861,6 +861,13 @@ int conv_wino_mode(int set) {
     return g_wino_mode.load(std::memory_order_relaxed);
 }
 
+static thread_local int t_decide_rows = 0;
+int conv_decide_rows(int set) {
+    const int before = t_decide_rows;
+    if (set >= 0) t_decide_rows = set;
+    return before;
+}
+
 static int wino_cus(int dev) {
     static std::atomic<int> cus_of[kMaxDevices];
     int c = cus_of[dev].load(std::memory_order_relaxed);
@@ -912,7 +919,8 @@ bool conv_wino_eligible(const ConvArgs& a) {
     if (mode == 2) return true;
     // decided from the IMAGE, never from the launch's batch (the two kernels sum in different orders: a frame's bits must not depend
     // on its launch mates): work items of a nominal two-image launch — what FILM / M2M / IFRNet / GMFSS issue per pair
-    const long regions = 2L * cdiv(a.Hin, 8) * cdiv(a.Win, 16);
+    const int rows = conv_decide_rows(-1) > 0 ? conv_decide_rows(-1) : a.Hin;      // a band is sized as its frame
+    const long regions = 2L * cdiv(rows, 8) * cdiv(a.Win, 16);
     const long items = regions / 4 * (a.Cout_p / 32);
     if (items < 192) return false;
     // r5: ... and not a launch of at most two rounds whose last round is nearly empty.  The kernel is persistent, one workgroup per CU:

@@ -12,6 +12,10 @@
 // pre-activations in front of a block's first conv (whose raw input the block still needs) are vfi_prelu_scalar passes.  The four heads'
 // first convs are one 64 -> 256 layer with per-channel PReLU (act 3, each head's slope repeated 64 times) reading up2(row1) once.
 //
+// Two forms of the head stage (ensure_workspace, forward_pair): whole-frame, which materialises x1 = [Hp, Wp, 256] and heads = [Hp, Wp, 208]
+// and serves every frame of at most 2 097 151 padded pixels on plain layer forms, and banded (vfi_sepconvnet_set_large_frames; csrc/sepconv_bands.h), which runs
+// head1, the head2 layers, the transpose and the output stage per band of output rows and keeps those two tensors for one band only.
+//
 // New kernels: the fused output stage (sepconv_pair_out_kernel) and three data-movement helpers (the side-by-side interleave of the
 // normalised frames, the cropped residual add, the heads' transpose to planar, which makes the output stage's tap loads coalesced).
 #include <algorithm>
@@ -20,6 +24,7 @@
 
 #include "../../include/vfi_hip.h"
 #include "net_object.h"
+#include "sepconv_bands.h"
 #include "vfi_common.h"
 
 using namespace vfi;
@@ -79,17 +84,19 @@ __device__ __forceinline__ void row_sums(const float4* __restrict__ row, const f
 __global__ __launch_bounds__(256) void sepconv_pair_out_kernel(const float* __restrict__ f0, const float* __restrict__ f1, int C, int H, int W,
                                                                const float* __restrict__ v0, const float* __restrict__ v1,
                                                                const float* __restrict__ h0, const float* __restrict__ h1, long pstr, long fstr,
-                                                               int Wp, float* __restrict__ out) {
+                                                               int Wp, int yo, int nrows, float* __restrict__ out) {
     constexpr int LW = PO_TX + K - 1;
     constexpr int ROWS = PO_TY + K - 1;
     __shared__ float4 lds[PO_RS][LW];
     const int tid = threadIdx.x;
     const int tx = tid & 63, tp = tid >> 6;            // tp = wave = pixel-row pair
-    const int x0 = blockIdx.x * PO_TX, y0 = blockIdx.y * PO_TY;
+    // the launch owns the output rows [yo, yo + nrows) (yo a multiple of PO_TY, yo + nrows <= H) and the heads hold those rows only: row yo of
+    // the frame is the heads' row 0.  The whole frame is yo = 0, nrows = H.
+    const int x0 = blockIdx.x * PO_TX, y0 = yo + blockIdx.y * PO_TY;
     const int x = x0 + tx, ya = y0 + 2 * tp, yb = ya + 1;
-    const bool va = x < W && ya < H, vb = x < W && yb < H;
-    // tap f of pixel p at head[p * pstr + f * fstr]: NHWC (pstr = channel stride, fstr = 1) or planar (pstr = 1, fstr = Hp * Wp)
-    const size_t pa = ((size_t)ya * Wp + x) * pstr, pb = ((size_t)yb * Wp + x) * pstr;
+    const bool va = x < W && ya < yo + nrows, vb = x < W && yb < yo + nrows;
+    // tap f of pixel p at head[p * pstr + f * fstr]: NHWC (pstr = channel stride, fstr = 1) or planar (pstr = 1, fstr = the heads' pixels)
+    const size_t pa = ((size_t)(ya - yo) * Wp + x) * pstr, pb = ((size_t)(yb - yo) * Wp + x) * pstr;
     f2 aa_lo = {0.f, 0.f}, aa_hi = {0.f, 0.f}, ab_lo = {0.f, 0.f}, ab_hi = {0.f, 0.f};
     for (int fr = 0; fr < 2; ++fr) {
         const float* __restrict__ f = fr ? f1 : f0;
@@ -182,14 +189,15 @@ __global__ __launch_bounds__(256) void sepnet_add_crop_kernel(float* __restrict_
 unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 // heads NHWC [P, HEAD_CS] (head k at channel 52 k) -> planar [4 * 51][P] (head k's tap f at plane 51 k + f), 64 pixels per workgroup through LDS:
-// the output stage then reads each tap of 64 neighbouring pixels as one contiguous 256-byte run
-__global__ __launch_bounds__(256) void sepnet_heads_planar_kernel(const float* __restrict__ in, long P, float* __restrict__ out) {
+// the output stage then reads each tap of 64 neighbouring pixels as one contiguous 256-byte run.  The P pixels start at pixel pin of `in`
+// (a band's kept rows inside its heads, which begin with halo rows; the whole frame: 0) and are pixel 0.. of `out`, whose plane stride is P.
+__global__ __launch_bounds__(256) void sepnet_heads_planar_kernel(const float* __restrict__ in, long pin, long P, float* __restrict__ out) {
     __shared__ float t[HEAD_CS][65];
     const long p0 = (long)blockIdx.x * 64;
     const int np = P - p0 < 64 ? (int)(P - p0) : 64;
     for (int i = threadIdx.x; i < np * HEAD_CS; i += 256) {
         const int p = i / HEAD_CS, c = i - p * HEAD_CS;
-        t[c][p] = in[(p0 + p) * HEAD_CS + c];
+        t[c][p] = in[(pin + p0 + p) * HEAD_CS + c];
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 4 * K * 64; i += 256) {
@@ -199,10 +207,10 @@ __global__ __launch_bounds__(256) void sepnet_heads_planar_kernel(const float* _
 }
 
 int pair_out_launch(const float* f0, const float* f1, int C, int H, int W, const float* v0, const float* v1, const float* h0, const float* h1,
-                    long pstr, long fstr, int Wp, float* out, hipStream_t st) {
+                    long pstr, long fstr, int Wp, int yo, int nrows, float* out, hipStream_t st) {
     TraceScope ts("sepconv_pair_out", st);
-    sepconv_pair_out_kernel<<<dim3((W + PO_TX - 1) / PO_TX, (H + PO_TY - 1) / PO_TY), 256, 0, st>>>(f0, f1, C, H, W, v0, v1, h0, h1, pstr, fstr, Wp,
-                                                                                                 out);
+    sepconv_pair_out_kernel<<<dim3((W + PO_TX - 1) / PO_TX, (nrows + PO_TY - 1) / PO_TY), 256, 0, st>>>(f0, f1, C, H, W, v0, v1, h0, h1, pstr, fstr,
+                                                                                                     Wp, yo, nrows, out);
     VFI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -226,12 +234,15 @@ struct vfi_sepconvnet : NetObject {
     float* row[5][2] = {};
     int cur[5] = {};
     float *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *heads = nullptr;
+    bool large = false;                               // vfi_sepconvnet_set_large_frames: frames over kWholeMaxPixels take the banded head stage
+    int band = 0;                                     // the workspace's form: 0 whole-frame, > 0 banded with this band height
 };
 
 namespace {
 
-int ensure_workspace(vfi_sepconvnet* m, int Hp, int Wp) {
-    if (m->ws.live() && m->Hp == Hp && m->Wp == Wp) return 0;
+// band: 0 = the whole-frame form, > 0 = the banded form with that band height (x1 and heads sized for one band with its halo)
+int ensure_workspace(vfi_sepconvnet* m, int Hp, int Wp, int band) {
+    if (m->ws.live() && m->Hp == Hp && m->Wp == Wp && m->band == band) return 0;
     if (m->ws.release()) return -1;
     auto get = [&](float** p, size_t floats) { return m->ws.alloc(p, floats, Workspace::kNoFill, nullptr); };
     const size_t P = (size_t)Hp * Wp;
@@ -246,13 +257,22 @@ int ensure_workspace(vfi_sepconvnet* m, int Hp, int Wp) {
         x3 = std::max(x3, up * CH[r]);
         x2 = std::max(x2, up * CH[r + 1]);
     }
-    if (get(&m->nrm, 2 * P * 4) || get(&m->side, P * 8) || get(&m->stats, 64) || get(&m->nws, NORM_WS / 4) || get(&m->x1, 256 * P) ||
-        get(&m->x2, x2) || get(&m->x3, x3) || get(&m->heads, P * HEAD_CS) || get(&m->row[0][0], P * CH[0]))
+    size_t x1 = 256 * P, heads = P * HEAD_CS;
+    if (band) {
+        // x1 outside the head stage: the pre-activated rows of the encoder and the decoder blocks and, where a Ver block crops, its second
+        // conv's output at 2 h x 2 w
+        x1 = (size_t)sepbands::x1_band_floats(Hp, Wp, band);
+        for (int r = 0; r < 5; ++r) x1 = std::max(x1, (size_t)m->h[r] * m->w[r] * CH[r]);
+        for (int r = 1; r < 4; ++r) x1 = std::max(x1, (size_t)(2 * m->h[r + 1]) * (2 * m->w[r + 1]) * CH[r]);
+        heads = (size_t)sepbands::heads_band_floats(Hp, Wp, band);
+    }
+    if (get(&m->nrm, 2 * P * 4) || get(&m->side, P * 8) || get(&m->stats, 64) || get(&m->nws, NORM_WS / 4) || get(&m->x1, x1) ||
+        get(&m->x2, x2) || get(&m->x3, x3) || get(&m->heads, heads) || get(&m->row[0][0], P * CH[0]))
         return -1;
     for (int r = 1; r < 5; ++r)
         for (int j = 0; j < 2; ++j)
             if (get(&m->row[r][j], (size_t)m->h[r] * m->w[r] * CH[r])) return -1;
-    m->Hp = Hp, m->Wp = Wp;
+    m->Hp = Hp, m->Wp = Wp, m->band = band;
     return 0;
 }
 
@@ -268,6 +288,31 @@ int prelu(const float* in, float* out, int C, int h, int w, float slope, hipStre
 int up2(const float* in, float* out, int C, int h, int w, hipStream_t st) {
     // F.interpolate(scale_factor=2.0, bilinear, align_corners=False): output 2h x 2w, source step (float)(1 / 2)
     return vfi_resize_bilinear_ratio(in, C, out, C, 1, h, w, 2 * h, 2 * w, C, 0.5f, 0.5f, 1.f, st);
+}
+
+// The head stage from x2 = up2(row1) on, band by band (csrc/sepconv_bands.h: rows, halo and why the bits are the whole-frame form's): the
+// default forms only (one 64 -> 256 head1 layer, planar heads).  Every layer call is sized as the frame's (ConvDecideRows), so a band takes
+// the kernel and the tile the whole-frame call takes.
+int head_stage_bands(vfi_sepconvnet* m, const float* f0, const float* f1, int C, int H, int W, float* out, hipStream_t st) {
+    const int Hp = m->Hp, Wp = m->Wp, bh = m->band;
+    ConvDecideRows as_frame(Hp);
+    for (int b = 0; b < sepbands::band_count(Hp, bh); ++b) {
+        const sepbands::Band d = sepbands::band_at(Hp, bh, b);
+        const float* x2 = m->x2 + (size_t)d.in0 * Wp * 64;
+        if (conv(m->head1, x2, 64, d.in1 - d.in0, Wp, m->x1, 256, 3, 0.f, nullptr, 0, st)) return -1;
+        const float* x1 = m->x1 + (size_t)(d.mid0 - d.in0) * Wp * 256;
+        for (int k = 0; k < 4; ++k)
+            if (conv(m->head2[k], x1 + 64 * k, 256, d.mid1 - d.mid0, Wp, m->heads + 52 * k, HEAD_CS, 0, 0.f, nullptr, 0, st)) return -1;
+        const int nrows = std::min(d.y1, H) - d.y0;      // >= 1: y0 <= Hp - 2 < H
+        const long Pb = (long)(d.y1 - d.y0) * Wp;        // the planar band: all Wp columns of the band's rows, as the whole-frame form keeps them
+        {   // planar into x1 (free again)
+            TraceScope ts("sepnet_heads_planar", st);
+            sepnet_heads_planar_kernel<<<(unsigned)((Pb + 63) / 64), 256, 0, st>>>(m->heads, (long)(d.y0 - d.mid0) * Wp, Pb, m->x1);
+            VFI_CHECK_HIP(hipGetLastError());
+        }
+        if (pair_out_launch(f0, f1, C, H, W, m->x1, m->x1 + K * Pb, m->x1 + 2 * K * Pb, m->x1 + 3 * K * Pb, 1, Pb, Wp, d.y0, nrows, out, st)) return -1;
+    }
+    return 0;
 }
 
 int forward_pair(vfi_sepconvnet* m, const float* f0, const float* f1, int C, int H, int W, float* out, hipStream_t st) {
@@ -320,6 +365,7 @@ int forward_pair(vfi_sepconvnet* m, const float* f0, const float* f1, int C, int
     }
     // heads: conv3(prelu(conv3(up2(row1)))) x 4, the first convs as one 64 -> 256 layer
     if (up2(row[1], m->x2, CH[1], h[1], w[1], st)) return -1;
+    if (m->band) return head_stage_bands(m, f0, f1, C, H, W, out, st);
     if (option(kOptSepconvSplitHeads)) {
         for (int k = 0; k < 4; ++k)
             if (conv(m->head1s[k], m->x2, 64, Hp, Wp, m->x1, 64, 1, m->head_s[k], nullptr, 0, st) ||
@@ -332,13 +378,13 @@ int forward_pair(vfi_sepconvnet* m, const float* f0, const float* f1, int C, int
     }
     // heads order: netVerone, netVertwo, netHorone, netHortwo
     if (!option(kOptSepconvPlanar))
-        return pair_out_launch(f0, f1, C, H, W, m->heads, m->heads + 52, m->heads + 104, m->heads + 156, HEAD_CS, 1, Wp, out, st);
+        return pair_out_launch(f0, f1, C, H, W, m->heads, m->heads + 52, m->heads + 104, m->heads + 156, HEAD_CS, 1, Wp, 0, H, out, st);
     {   // planar into x1 (free again: 4 * 51 planes <= its 256)
         TraceScope ts("sepnet_heads_planar", st);
-        sepnet_heads_planar_kernel<<<(unsigned)((P + 63) / 64), 256, 0, st>>>(m->heads, P, m->x1);
+        sepnet_heads_planar_kernel<<<(unsigned)((P + 63) / 64), 256, 0, st>>>(m->heads, 0, P, m->x1);
         VFI_CHECK_HIP(hipGetLastError());
     }
-    return pair_out_launch(f0, f1, C, H, W, m->x1, m->x1 + K * P, m->x1 + 2 * K * P, m->x1 + 3 * K * P, 1, P, Wp, out, st);
+    return pair_out_launch(f0, f1, C, H, W, m->x1, m->x1 + K * P, m->x1 + 2 * K * P, m->x1 + 3 * K * P, 1, P, Wp, 0, H, out, st);
 }
 
 }  // namespace
@@ -355,10 +401,22 @@ int vfi_sepconv_pair_out(const float* const* frame0_dev, const float* const* fra
     for (int n = 0; n < N; ++n) {
         VFI_REQUIRE(frame0_dev[n] && frame1_dev[n], "vfi_sepconv_pair_out: null frame pointer for pair %d", n);
         if (int rc = pair_out_launch(frame0_dev[n], frame1_dev[n], C, H, W, ver0_dev + n * item, ver1_dev + n * item, hor0_dev + n * item,
-                                     hor1_dev + n * item, head_cs, 1, Wp, out_dev + (size_t)n * H * W * 3, (hipStream_t)stream))
+                                     hor1_dev + n * item, head_cs, 1, Wp, 0, H, out_dev + (size_t)n * H * W * 3, (hipStream_t)stream))
             return rc;
     }
     return 0;
+}
+
+int vfi_sepconv_pair_out_rows(const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ver0_dev, const float* ver1_dev,
+                              const float* hor0_dev, const float* hor1_dev, int64_t pixel_stride, int64_t tap_stride, int Wp, int row0, int rows,
+                              float* out_dev, void* stream) {
+    VFI_REQUIRE(frame0_dev && frame1_dev && ver0_dev && ver1_dev && hor0_dev && hor1_dev && out_dev && C >= 3 && H > 0 && W > 0 && Wp >= W &&
+                    pixel_stride > 0 && tap_stride > 0,
+                "vfi_sepconv_pair_out_rows: bad arguments (C=%d H=%d W=%d Wp=%d)", C, H, W, Wp);
+    VFI_REQUIRE(row0 >= 0 && row0 % PO_TY == 0 && rows > 0 && rows <= H - row0,
+                "vfi_sepconv_pair_out_rows: rows [%d, %d + %d) must start at a multiple of %d and lie inside the %d-row frame", row0, row0, rows, PO_TY, H);
+    return pair_out_launch(frame0_dev, frame1_dev, C, H, W, ver0_dev, ver1_dev, hor0_dev, hor1_dev, (long)pixel_stride, (long)tap_stride, Wp, row0, rows,
+                           out_dev, (hipStream_t)stream);
 }
 
 vfi_sepconvnet_t* vfi_sepconvnet_create(const float* const* tensors, const int64_t* numels, int n_tensors) {
@@ -448,12 +506,59 @@ int vfi_sepconvnet_release_workspace(vfi_sepconvnet_t* m) {
 
 int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* m) { return m ? m->ws.bytes() : 0; }
 
+// The largest padded frame (sides rounded up to even) without large frames: the whole-frame head stage materialises the four heads' first
+// layer x1 = [Hp, Wp, 256] fp32, which the layers' large-image forms serve below 4 GiB: Hp * Wp * 1024 <= 2^32 - 1.  (Up to 2 097 151 pixels
+// that tensor is below 2 GiB and every layer takes its plain form.)
+int64_t vfi_sepconvnet_max_pixels(void) { return sepbands::kMaxPixels; }
+
+// ... with vfi_sepconvnet_set_large_frames: x1 and the heads exist for one band of rows at a time, and the widest tensor that stays whole is
+// up2(row1) = x2 = [Hp, Wp, 64] fp32, an operand of plain layer forms: Hp * Wp * 256 < 2^31 - 1 (2160x3840 fits, 2898x2896 does not)
+int64_t vfi_sepconvnet_large_max_pixels(void) { return sepbands::kLargeMaxPixels; }
+
+// the limit vfi_sepconvnet_forward holds this object to: one of the two above (0 for a null object)
+int64_t vfi_sepconvnet_object_max_pixels(const vfi_sepconvnet_t* m) { return !m ? 0 : (m->large ? sepbands::kLargeMaxPixels : sepbands::kMaxPixels); }
+
+// on: padded frames over 2 097 151 pixels take the banded head stage and the limit is vfi_sepconvnet_large_max_pixels(); smaller frames run
+// the whole-frame form, the same launches and bits, either way.  Off (default): today's whole-frame form up to vfi_sepconvnet_max_pixels().
+// A workspace of the other form is released at the next forward (its key holds the form).
+int vfi_sepconvnet_set_large_frames(vfi_sepconvnet_t* m, int on) {
+    VFI_REQUIRE(m, "vfi_sepconvnet_set_large_frames: null object");
+    m->large = on != 0;
+    return 0;
+}
+
 int vfi_sepconvnet_forward(vfi_sepconvnet_t* m, const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W,
                            float* out_dev, void* stream) {
     VFI_REQUIRE(m && frame0_dev && frame1_dev && out_dev && N > 0 && C >= 3 && H > 0 && W > 0, "vfi_sepconvnet_forward: bad arguments");
     for (int n = 0; n < N; ++n) VFI_REQUIRE(frame0_dev[n] && frame1_dev[n], "vfi_sepconvnet_forward: null frame pointer for pair %d", n);
     hipStream_t st = (hipStream_t)stream;
-    if (ensure_workspace(m, H + H % 2, W + W % 2)) return -1;
+    // refusals first: nothing is allocated or launched for a frame the object cannot serve (64-bit sums: H + 1 and the product fit)
+    const int64_t Hp64 = (int64_t)H + H % 2, Wp64 = (int64_t)W + W % 2, px = Hp64 * Wp64;
+    VFI_REQUIRE(m->large || px <= sepbands::kMaxPixels,
+                "vfi_sepconvnet_forward: a %dx%d frame (padded %lldx%lld) is over the size limit of %lld padded pixels: the heads' first layer "
+                "[Hp, Wp, 256] must stay below 4 GiB; vfi_sepconvnet_set_large_frames raises the limit to %lld",
+                H, W, (long long)Hp64, (long long)Wp64, (long long)sepbands::kMaxPixels, (long long)sepbands::kLargeMaxPixels);
+    VFI_REQUIRE(!m->large || px <= sepbands::kLargeMaxPixels,
+                "vfi_sepconvnet_forward: a %dx%d frame (padded %lldx%lld) is over the size limit with large frames on, %lld padded pixels: "
+                "up2(row1) = [Hp, Wp, 64] must stay below 2 GiB",
+                H, W, (long long)Hp64, (long long)Wp64, (long long)sepbands::kLargeMaxPixels);
+    const int Hp = (int)Hp64, Wp = (int)Wp64;
+    int band = (int)option(kOptSepconvBandRows);      // 0 outside the test library
+    if (band > 0) {
+        VFI_REQUIRE(sepbands::band_rows_legal(Hp, Wp, band), "vfi_sepconvnet_forward: sepconv_band_rows = %d is no legal band height for %dx%d (a "
+                    "multiple of %d whose [rows + 8, Wp, 256] tensor stays below 2 GiB)", band, Hp, Wp, sepbands::kTileRows);
+    } else if (m->large && px > sepbands::kWholeMaxPixels) {
+        band = sepbands::default_band_rows(Hp, Wp);
+        VFI_REQUIRE(band > 0, "vfi_sepconvnet_forward: a %dx%d frame is too wide for the banded head stage: a band of %d rows with its halo, "
+                    "[%d, Wp, 256], must stay below 2 GiB (Wp <= %lld)", H, W, sepbands::kTileRows, sepbands::kTileRows + 2 * sepbands::kHaloIn,
+                    (long long)(sepbands::kBandMaxPixels / (sepbands::kTileRows + 2 * sepbands::kHaloIn)));
+    }
+    VFI_REQUIRE(!band || sepbands::widest_whole_bytes(Hp, Wp) < sepbands::kOperandBytes,
+                "vfi_sepconvnet_forward: a %dx%d frame has a decoder tensor of %lld bytes (an odd coarse level up-sampled past its finer one): it must "
+                "stay below 2 GiB", H, W, (long long)sepbands::widest_whole_bytes(Hp, Wp));
+    VFI_REQUIRE(!band || (!option(kOptSepconvSplitHeads) && option(kOptSepconvPlanar)),
+                "vfi_sepconvnet_forward: the banded head stage has the default forms only (sepconv_split_heads 0, sepconv_planar 1)");
+    if (ensure_workspace(m, Hp, Wp, band)) return -1;
     for (int n = 0; n < N; ++n)
         if (forward_pair(m, frame0_dev[n], frame1_dev[n], C, H, W, out_dev + (size_t)n * H * W * 3, st)) return -1;
     return 0;

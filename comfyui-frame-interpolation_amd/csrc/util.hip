@@ -34,6 +34,7 @@ static const struct { const char* name; long dflt; } kOptTable[kOptCount] = {
     {"splat_atomic", 0}, {"splat_spill_cap", -1}, {"wino_xcd", 1}, {"deconv_wino", 1}, {"encode_batched", 1}, {"wino_quant", 1}, {"xcd_bands", 0}, {"m2m_fused", 1}, {"m2m_side", 0}, {"film_side", 1}, {"wino_probe", 0},
     {"sepconv_split_heads", 0}, {"sepconv_planar", 1}, {"stage0", 1}, {"att_ksplit", 0}, {"wino_dead", 1},
     {"large_image_bytes", 0x7fffffffL},
+    {"sepconv_band_rows", 0},
 };
 static std::atomic<long> g_opt[kOptCount];
 static std::atomic<bool> g_opt_init{false};

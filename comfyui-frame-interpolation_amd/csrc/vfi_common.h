@@ -83,6 +83,7 @@ enum Option {
     kOptAttKsplit,          // 1..8: the number of key ranges attention_launch_t asks for (attention.hip; reduced so that no range is empty), default 0: chosen from the device's CU count
     kOptWinoDead,           // 1: the Winograd kernel skips the transform planes a transposed-convolution layer's weights leave zero (ConvArgs::wino_dead; default), 0: all 16 planes: same bits
     kOptLargeBytes,         // bytes of one image from which a layer object's operand counts as large and the launch takes the per-tile / per-region descriptors (conv_mfma2.hip, conv_wino.hip: LARGE); default 2^31 - 1, lower values put small images on that path: same bits
+    kOptSepconvBandRows,    // SepConv++'s head stage: 0 = automatic (whole frame up to 2 097 151 padded pixels, bands of the default height above, csrc/sepconv_bands.h), n > 0 = bands of n rows at any frame size: same bits
     kOptCount
 };
 long option(Option o);
@@ -235,6 +236,18 @@ bool conv_wino_eligible(const ConvArgs& a);
 inline bool conv_bytes_large(long bytes) { return bytes >= option(kOptLargeBytes); }
 inline bool conv_input_large(const ConvArgs& a) { return conv_bytes_large((long)a.Hin * a.Win * a.in_cs * 4); }
 int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal
+// A layer call that computes a horizontal BAND of a frame (csrc/sepconv_net.hip) must take the kernel and the tile the whole-frame call
+// would take, or the band's bits differ from the frame's (the two kernels sum in different orders): while rows > 0 on the calling thread,
+// conv_wino_eligible and conv_pick_variant size a stride-1 layer's choice by `rows` image rows instead of the call's own.  0 (default) = the
+// call's own rows; set < 0 queries.  Returns the value in force before the call.
+int conv_decide_rows(int set);
+struct ConvDecideRows {      // scope guard
+    int before;
+    explicit ConvDecideRows(int rows) : before(conv_decide_rows(rows)) {}
+    ~ConvDecideRows() { conv_decide_rows(before); }
+    ConvDecideRows(const ConvDecideRows&) = delete;
+    ConvDecideRows& operator=(const ConvDecideRows&) = delete;
+};
 int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* trace_name);
 void deconv4x4_taps(ConvArgs& a);
 

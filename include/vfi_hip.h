@@ -647,6 +647,14 @@ int64_t vfi_cain_workspace_bytes(const vfi_cain_t* net);
 int vfi_sepconv_pair_out(const float* const* frame0_dev, const float* const* frame1_dev, int N, int C, int H, int W, const float* ver0_dev,
                          const float* ver1_dev, const float* hor0_dev, const float* hor1_dev, int head_cs, int Hp, int Wp, float* out_dev,
                          void* stream);
+/* The same output stage for the rows [row0, row0 + rows) of ONE pair's frame (row0 a multiple of 8, the stage's tile rows; the band inside
+ * the H-row frame), from filters that exist for those rows only: tap f of the pixel (row0 + r, x) of head h at
+ * h_dev[(r * Wp + x) * pixel_stride + f * tap_stride] — NHWC (pixel_stride = the channel stride, tap_stride = 1) or planar (pixel_stride = 1,
+ * tap_stride = the band's pixels).  out_dev is the whole frame's [H,W,3]; only the band's rows are written.  The frames are read with
+ * clamp-to-frame addressing over all H rows.  row0 = 0, rows = H is one pair of vfi_sepconv_pair_out: same launch, same bits. */
+int vfi_sepconv_pair_out_rows(const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ver0_dev, const float* ver1_dev,
+                              const float* hor0_dev, const float* hor1_dev, int64_t pixel_stride, int64_t tap_stride, int Wp, int row0, int rows,
+                              float* out_dev, void* stream);
 
 typedef struct vfi_sepconvnet vfi_sepconvnet_t;
 /* The 88 state_dict tensors of SepConv++'s Network in sepconv_spec.sepconv_shapes() order (fp32 host memory, copied). */
@@ -660,6 +668,18 @@ int vfi_sepconvnet_forward(vfi_sepconvnet_t* net, const float* const* frame0_dev
                            float* out_dev, void* stream);
 int vfi_sepconvnet_release_workspace(vfi_sepconvnet_t* net);
 int64_t vfi_sepconvnet_workspace_bytes(const vfi_sepconvnet_t* net);
+/* Frame size, in padded pixels (both sides rounded up to even).  Without large frames the head stage materialises the four heads' first
+ * layer [Hp, Wp, 256], which the layers serve below 4 GiB: vfi_sepconvnet_max_pixels() = 4 194 303 (up to 2 097 151 on plain layer forms,
+ * 1080x1920 among them; above that on the large-image forms).  vfi_sepconvnet_set_large_frames(net, 1) runs the head stage of every frame
+ * over 2 097 151 pixels in horizontal bands, so that tensor exists for one band at a time and [Hp, Wp, 64] below 2 GiB sets the limit:
+ * vfi_sepconvnet_large_max_pixels() = 8 388 607, which takes 2160x3840.  Frames of at most 2 097 151 pixels run the same launches and give
+ * the same bits whatever the switch says.  vfi_sepconvnet_forward refuses a frame over the object's limit
+ * (vfi_sepconvnet_object_max_pixels; 0 for a null object), and with large frames on one so wide that a band of 8 rows with its halo of 8,
+ * [16, Wp, 256], reaches 2 GiB (Wp > 131 071), before it allocates or launches anything. */
+int vfi_sepconvnet_set_large_frames(vfi_sepconvnet_t* net, int on);
+int64_t vfi_sepconvnet_max_pixels(void);
+int64_t vfi_sepconvnet_large_max_pixels(void);
+int64_t vfi_sepconvnet_object_max_pixels(const vfi_sepconvnet_t* net);
 
 /* ---- FLAVR (vfi_models/flavr/flavr_arch.py UNet_3D_3D("unet_18", 4 inputs, "concat", "transpose"), resnet_3D.py) ------------------- */
 
