@@ -91,7 +91,8 @@ def _node_class_mappings():
 # (lite) / 1472x2560 (base), up to 2160x3840 with both, only when its atm_large_frames key is on (atm_spec.atm_large_frames_enabled).
 # FLAVR VFI serves frames beyond 1088x1920, up to 2160x3840, only when config.yaml's flavr_large_frames key is on (flavr.large_frames_enabled).
 # Sepconv VFI serves frames beyond 4 194 303 pixels, up to 2160x3840, only when config.yaml's sepconv_large_frames key is on (sepconv.large_frames_enabled).
-# AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled).
+# AMT VFI serves amt-g.pth (AMT-G) only when config.yaml's amt_g key is on as well (amt_spec.amt_g_enabled), and AMT-G frames beyond
+# 6 100 805 padded pixels, up to 2160x3840, only when its amt_large_frames key is on (amt.large_frames_enabled).
 # XVFI's key is "xvfi" (the reference's class is XVFI; upstream never registered it, so the node's name "XVFI VFI" follows the other nodes').
 EXTRA_NODES = {"cain": ("CAIN VFI", "CAIN VFI (MI355X HIP)"), "sepconv": ("Sepconv VFI", "Sepconv VFI (MI355X HIP)"),
                "flavr_vfi": ("FLAVR VFI", "FLAVR VFI (MI355X HIP)"), "amt_vfi": ("AMT VFI", "AMT VFI (MI355X HIP)"),

@@ -203,6 +203,7 @@ PROTOTYPES = {
     "vfi_cain_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "vfi_conv_accept_odd": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_conv_allow_huge": (C.c_int, [C.c_void_p, C.c_int]),
+    "vfi_conv_allow_large_res_prelu": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_conv_huge_max_floats": (C.c_int64, []),
     "vfi_sepconv_pair_out": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -250,6 +251,9 @@ PROTOTYPES = {
     "vfi_amt_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]),
     "vfi_amt_release_workspace": (C.c_int, [C.c_void_p]),
     "vfi_amt_workspace_bytes": (C.c_int64, [C.c_void_p]),
+    "vfi_amt_object_max_padded_pixels": (C.c_int64, [C.c_void_p]),
+    "vfi_amt_large_max_padded_pixels": (C.c_int64, [C.c_int]),
+    "vfi_amt_set_large_frames": (C.c_int, [C.c_void_p, C.c_int]),
     "vfi_atm_window_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vfi_atm_window_attention_labels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
@@ -335,6 +339,11 @@ WINO_TEST_PROTOTYPES = {
 ATM_TEST_PROTOTYPES = {
     "vfi_atm_ensemble_record": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
 }
+# ... and include/vfi_hip_test_amt.h (AMT's copy / add and warp kernels, which have no entry point of their own): test builds only
+AMT_TEST_PROTOTYPES = {
+    "vfi_test_amt_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vfi_test_amt_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+}
 # ... and include/vfi_hip_test_large.h (the log of LARGE-form launches): test builds only
 LARGE_TEST_PROTOTYPES = {
     "vfi_test_large_launches": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
@@ -392,6 +401,7 @@ def load():
         protos.update(WINO_TEST_PROTOTYPES)
         protos.update(ATM_TEST_PROTOTYPES)
         protos.update(LARGE_TEST_PROTOTYPES)
+        protos.update(AMT_TEST_PROTOTYPES)
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../include/vfi_hip.h"
+#include "../../include/vfi_hip_test_amt.h"
 #include "bilinear_src.h"
 #include "net_object.h"
 #include "rife_warp.h"
@@ -453,7 +454,9 @@ struct Cfg {
 };
 // (amt.py's MAX_PADDED_PIXELS_G is derived from the same 88; tests/test_gpu_amt_g.py asserts that the two limits agree.)
 // AMT-G's widest buffer is decoder1's ResBlock at half resolution: r8(3 * 84) + 8 + r8(84) = 352 channels = 88 floats per padded pixel
-// (gru.0's input in update2_high, r8(188 + 4 + 84) = 280 channels, is 70).  AMT-S / AMT-L keep their 64.
+// (gru.0's input in update2_high, r8(188 + 4 + 84) = 280 channels, is 70).  AMT-S / AMT-L keep their 64.  The limit is signed (every object
+// as created) or, for AMT-G after vfi_amt_set_large_frames, unsigned: every layer that meets an image of 2 GiB or more then has a
+// large-image form (docs/design/amt.md "4K").
 const Cfg kCfg[3] = {{{20, 32, 44, 56}, 20, 3, 84, 3, 76, 20, 64, 0, 68, 32, 3, {32, 64, 96}, {1, 2, 2}, 3, 64, 213, "AMT-S"},
                      {{48, 64, 72, 128}, 48, 5, 128, 7, 128, 48, 256, 160, 124, 64, 3, {64, 72, 128}, {1, 2, 2}, 3, 64, 207, "AMT-L"},
                      {{84, 96, 112, 128}, 84, 5, 128, 7, 192, 64, 256, 192, 188, 64, 4, {64, 112, 160, 160}, {1, 2, 2, 1}, 5, 88, 259, "AMT-G"}};
@@ -484,6 +487,7 @@ struct Upd {
 
 struct vfi_amt : PaddedNet {
     int variant = 0;      // 0 AMT-S, 1 AMT-L, 2 AMT-G
+    bool large = false;   // vfi_amt_set_large_frames on an AMT-G object: padded frames up to max_padded_pixels_large(px_floats) are served
     Stem fe_stem, py_stem;
     EncBlk blk[8];
     vfi_conv_t* fe_out = nullptr;
@@ -914,6 +918,45 @@ int vfi_amt_release_workspace(vfi_amt_t* m) {
 
 int64_t vfi_amt_workspace_bytes(const vfi_amt_t* m) { return m ? m->ws.bytes() : 0; }
 
+// AMT-S / AMT-L: px_floats = 64 is a bound on the frame, not on a buffer (their widest buffers stay below 2 GiB at 2^23 - 1 pixels, where the
+// 2^23 comes from the kernels' pixel arithmetic), so the switch has nothing to raise and changes nothing for them.
+int64_t vfi_amt_large_max_padded_pixels(int variant) {
+    if (variant < 0 || variant > 2) return 0;
+    return variant == 2 ? max_padded_pixels_large(kCfg[2].px_floats) : max_padded_pixels(kCfg[variant].px_floats);
+}
+
+int64_t vfi_amt_object_max_padded_pixels(const vfi_amt_t* m) {
+    return !m ? 0 : (m->large ? max_padded_pixels_large(kCfg[m->variant].px_floats) : max_padded_pixels(kCfg[m->variant].px_floats));
+}
+
+// AMT-G: every layer object gets the one permission the forward needs beyond the forms a layer takes on its own (decoder1's rb[4] is
+// residual + PReLU on a 2.92 GB input at 2160x3840), and the entry guard takes the 4 GiB bound.  AMT-S / AMT-L: nothing is set.
+int vfi_amt_set_large_frames(vfi_amt_t* m, int on) {
+    VFI_REQUIRE(m, "vfi_amt_set_large_frames: null object");
+    if (m->variant != 2) return 0;
+    for (vfi_conv_t* L : m->layers)
+        if (vfi_conv_allow_large_res_prelu(L, on != 0)) return -1;
+    m->large = on != 0;
+    return 0;
+}
+
+#ifdef VFI_TEST_TAPS      // include/vfi_hip_test_amt.h: only in libvfi_hip_test.so.  The launches are Run::add's and Run::warp's.
+int vfi_test_amt_add(const float* a, int a_cs, int a_w, int step, const float* b, int b_cs, float* out, int out_cs, int h, int w, int C, int reps,
+                     void* stream) {
+    VFI_REQUIRE(a && out && h > 0 && w > 0 && C > 0 && reps >= 1 && step >= 1 && a_w >= (w - 1) * step + 1 && a_cs >= reps * C && out_cs >= reps * C &&
+                    (!b || b_cs >= C),
+                "vfi_test_amt_add: bad arguments");
+    Run r{{nullptr, (hipStream_t)stream, 0.1f}};
+    return r.add(a, a_cs, a_w, step, b, b_cs, out, out_cs, h, w, C, reps);
+}
+
+int vfi_test_amt_warp(const float* in, int in_cs, const float* flow, int flow_cs, float* out, int out_cs, int H, int W, int C, void* stream) {
+    VFI_REQUIRE(in && flow && out && H > 1 && W > 1 && C > 0 && in_cs >= C && out_cs >= C && flow_cs >= 2, "vfi_test_amt_warp: bad arguments");
+    Run r{{nullptr, (hipStream_t)stream, 0.1f}};
+    return r.warp(in, in_cs, flow, flow_cs, out, out_cs, H, W, C);
+}
+#endif
+
 int vfi_amt_forward(vfi_amt_t* m, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ts_host, int n_t, float* out_dev,
                     void* stream) {
     VFI_REQUIRE(m && frame0_dev && frame1_dev && ts_host && out_dev && C >= 3 && H > 0 && W > 0 && n_t > 0, "vfi_amt_forward: bad arguments");
@@ -924,7 +967,7 @@ int vfi_amt_forward(vfi_amt_t* m, const float* frame0_dev, const float* frame1_d
                 "vfi_amt_forward: a %dx%d frame (padded %dx%d): AMT needs padded sides of at least 128 pixels (below, the coarsest correlation level is "
                 "one pixel wide and the reference is all-NaN)", H, W, Hp, Wp);
     const Cfg& g = kCfg[m->variant];      // px_floats: the variant's widest activation, floats per padded pixel
-    if (const int rc = m->enter("vfi_amt_forward", g.name, H, W, Hp, Wp, g.px_floats)) return rc;
+    if (const int rc = m->enter("vfi_amt_forward", g.name, H, W, Hp, Wp, g.px_floats, false, m->large)) return rc;
     return amt_forward(m, frame0_dev, frame1_dev, C, H, W, ts_host, n_t, out_dev, (hipStream_t)stream);
 }
 

@@ -77,6 +77,8 @@ struct Conv2Geom {
 // both are legal.  The output side needs nothing: the epilogue forms 64-bit addresses already.
 // LARGE with EXT: the one extended feature is the per-channel PReLU (act 3, no residual) — ATM's full-resolution layers.  Padding modes,
 // sigmoid, GELU, the post affine and the interleaved store (EXTF below) are compiled out of it and stay refused above 2 GiB (launch2_tl).
+// With a residual (3x3 stride-1 tiles, launch2_tl: the layer object's permission) the same instantiation takes its general epilogue, whose
+// residual reads and stores form 64-bit addresses from (n, oy, ox): nothing there counts bytes from an image's start in 32 bits.
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK, bool GROUPED, bool EXT, bool MASKED = false, bool TAIL4 = false, bool LARGE = false>
 __global__ __launch_bounds__(256) void conv_mfma2_kernel(const ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // the buffer-resource / LDS-DMA builtins do not exist in the host pass
@@ -592,7 +594,9 @@ static int launch2_e(ConvArgs a, hipStream_t s, const char* name) {
         VFI_REQUIRE(large_image_ok(a.Hin, a.Win, a.in_cs, a.huge_ok != 0) && !a.in_plane && !a.pad_mode && large_span_ok(G::THI, a.Win, a.in_cs),
                     "conv2 %s: image larger than 2 GiB", name);
         // ... and of the extended feature set the per-channel PReLU alone (the kernel has none of the others in this form)
-        VFI_REQUIRE(!EXT || (a.act == 3 && !a.res && a.post_scale == 0.f && a.out_mode == 0), "conv2 %s: image larger than 2 GiB", name);
+        // (with a residual only on the 3x3 stride-1 tiles and with the layer object's permission, ConvArgs::res_prelu_ok)
+        VFI_REQUIRE(!EXT || (a.act == 3 && (!a.res || (a.res_prelu_ok && STRIDE == 1 && TAPS == 9)) && a.post_scale == 0.f && a.out_mode == 0),
+                    "conv2 %s: image larger than 2 GiB", name);
     } else {
         VFI_REQUIRE((long)a.Hin * a.Win * a.in_cs * 4 < 0x7fffffffL, "conv2 %s: image larger than 2 GiB", name);
     }
@@ -723,13 +727,18 @@ static int launch2_t(const ConvArgs& a, hipStream_t s, const char* name) {
 // The tiles conv_pick_variant gives the plain layer forms (3x3 stride 1 / 2, 2x2 and 1x1 stride 1) also exist in the LARGE form.  It is
 // taken only from the size on (conv_input_large: 2 GiB, or what the test option large_image_bytes says); every smaller launch takes
 // launch2_t as before.  Of the extended feature set the 3x3 and 1x1 tiles serve one layer form large: per-channel PReLU (act 3) with zero
-// padding, no residual and no post affine.  Every other extended layer and every other tile keep the plain form and its 2 GiB guard.
+// padding, no residual and no post affine (3x3 stride 1: with a residual where the layer object permits it, below).  Every other extended
+// layer and every other tile keep the plain form and its 2 GiB guard.
 template <int STRIDE, int TAPS, int MT, int NT, int WM, int WN, int CK>
 static int launch2_tl(const ConvArgs& a, hipStream_t s, const char* name) {
     const bool ext = a.pad_mode || a.act >= 3 || a.post_scale != 0.f || a.out_mode == 2;
     if (!ext && !a.in_plane && conv_input_large(a)) return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, false, false, false, true>(a, s, name);
     if constexpr (TAPS != 4) {
-        const bool prelu_only = a.act == 3 && !a.pad_mode && a.post_scale == 0.f && a.out_mode == 0 && !a.res;
+        // ... and, for a layer object with the permission vfi_conv_allow_large_res_prelu, the same layer with a residual on the 3x3 stride-1
+        // tiles (AMT-G's ResBlock: prelu(conv5(x3) + r0)).  The kernel is the one instantiation: its general epilogue reads the residual and
+        // stores through 64-bit addresses in every form, so only the input needs the per-tile descriptor.
+        const bool res_ok = !a.res || (a.res_prelu_ok && STRIDE == 1 && TAPS == 9);
+        const bool prelu_only = a.act == 3 && !a.pad_mode && a.post_scale == 0.f && a.out_mode == 0 && res_ok;
         if (prelu_only && !a.in_plane && conv_input_large(a)) return launch2_e<STRIDE, TAPS, MT, NT, WM, WN, CK, false, true, false, false, true>(a, s, name);
     }
     return launch2_t<STRIDE, TAPS, MT, NT, WM, WN, CK, false>(a, s, name);

@@ -853,7 +853,8 @@ void pack_deconv_wino(const float* w_iohw, const float* bias, const float* prelu
     for (int nb = 0; nb < (int)forms.size() && nb < 32; ++nb) out.dead[nb >> 3] |= (unsigned)forms[nb] << ((nb & 7) * 4);
 }
 
-// 0 = automatic, 1 = direct kernel only, 2 = Winograd wherever the layer shape allows it.  Set through the test hook
+// 0 = automatic, 1 = direct kernel only, 2 = Winograd wherever the layer shape allows it, 3 = as 2 with 32x4 regions where the launcher
+// would pick the region shape (the plain forms and the LARGE form of residual + PReLU; the other LARGE forms have 16x8 only).  Set through the test hook
 // vfi_test_conv_algo only (both forms of one layer object on one input); never read from the environment.
 static std::atomic<int> g_wino_mode{0};
 int conv_wino_mode(int set) {
@@ -882,9 +883,12 @@ static int wino_cus(int dev) {
 
 // Large images: an operand (input, output, residual) of one image at or over the mark (conv_bytes_large).  The LARGE instantiations exist
 // for NHWC layers with zero padding, the epilogues none / LeakyReLU / clamp with or without a residual and per-channel PReLU without one (the hot
-// MODE 1; residual + PReLU, MODE 13, has no LARGE form and stays refused), and operands below 4 GiB — with the
+// MODE 1), and operands below 4 GiB — with the
 // layer object's permission (ConvArgs::huge_ok) up to kConvHugeMaxFloats floats each (conv_large.h: the kernel keeps an image's floats in an
 // int and forms every address from a per-region 64-bit base).
+// Residual + per-channel PReLU (MODE 13: AMT-G's ResBlock closes with prelu(conv5(x3) + r0) on a 2.92 GB x3 at 2160x3840) has LARGE forms for
+// both region shapes, taken only by a layer object with the permission vfi_conv_allow_large_res_prelu (ConvArgs::res_prelu_ok); without it
+// the layer keeps the plain form and its 2 GiB refusal.  The residual goes through a per-region descriptor of its own, as the output does.
 // The transposed convolution of a layer object (out_mode 2) has one LARGE form: the hot epilogue (MODE 0: none / LeakyReLU with a slope in
 // [0,1]), zero padding, no residual, no post affine.  Its operands are the input image and the interleaved [2 Hin, 2 Win] output image.
 static long wino_operand_bytes(const ConvArgs& a) {
@@ -898,7 +902,7 @@ static bool wino_large_ok(const ConvArgs& a) {
     const long bytes = wino_operand_bytes(a);
     if (a.out_mode == 2 && (a.res || !(a.act == 0 || (a.act == 1 && a.slope >= 0.f && a.slope <= 1.f)))) return false;
     return (a.huge_ok ? bytes / 4 <= kConvHugeMaxFloats : bytes <= kConvLargeMaxBytes) && !a.pad_mode && !a.in_plane && a.act >= 0 &&
-           (a.act <= 2 || (a.act == 3 && !a.res)) && a.post_scale == 0.f;
+           (a.act <= 2 || (a.act == 3 && (!a.res || a.res_prelu_ok))) && a.post_scale == 0.f;
 }
 
 // Is the Winograd kernel the better choice for this layer on this launch?  (3x3 stride 1 only; enough work items to fill the
@@ -916,7 +920,7 @@ bool conv_wino_eligible(const ConvArgs& a) {
     } else if (!wino_large_ok(a)) {
         return false;
     }
-    if (mode == 2) return true;
+    if (mode >= 2) return true;
     // decided from the IMAGE, never from the launch's batch (the two kernels sum in different orders: a frame's bits must not depend
     // on its launch mates): work items of a nominal two-image launch — what FILM / M2M / IFRNet / GMFSS issue per pair
     const int rows = conv_decide_rows(-1) > 0 ? conv_decide_rows(-1) : a.Hin;      // a band is sized as its frame
@@ -994,6 +998,8 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
     p.gray = a.out_mode != 0 ? a.wino_gray : 0;
     if (a.out_mode == 0 || !option(kOptWinoDead))      // the table belongs to the SHUF kernels; option 0 = all 16 planes (the order stays)
         for (unsigned& d : p.a.wino_dead) d = 0;
+    if (variant == 0 && conv_wino_mode(-1) == 3) variant = 16;      // test hook: 32x4 regions (the region shape changes no bit)
+    const int requested = variant;                                   // 0: the caller leaves the region shape to the launcher
     if (variant == 0) {     // region shape by covered-area efficiency: 16x8 pixels unless 32x4 wastes clearly less
         const double area = (double)a.Hin * a.Win;
         const double e8 = area / ((double)cdiv(a.Win, 16) * 16 * cdiv(a.Hin, 8) * 8);
@@ -1023,6 +1029,9 @@ int conv_wino_launch(const ConvArgs& a, int variant, hipStream_t s, const char* 
             case 1: return wino_launch_t<8, 1, 0, 0, true>(p, s, name);
             case 10: return wino_launch_t<8, 10, 0, 0, true>(p, s, name);
             case 11: return wino_launch_t<8, 11, 0, 0, true>(p, s, name);
+            // residual + per-channel PReLU (wino_large_ok: the layer object's permission).  Both region shapes exist: a 32x4 region's
+            // patch spans 6 rows, fewer than the 10 checked above.  The automatic choice is 16x8 as for the other LARGE forms.
+            case 13: return requested == 16 ? wino_launch_t<16, 13, 0, 0, true>(p, s, name) : wino_launch_t<8, 13, 0, 0, true>(p, s, name);
             default: return wino_launch_t<8, 12, 0, 0, true>(p, s, name);
         }
     }

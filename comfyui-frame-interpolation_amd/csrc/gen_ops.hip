@@ -237,6 +237,7 @@ struct vfi_conv {
     unsigned char* tapmask = nullptr;         // kind 2: taps of every 64-channel N block's parity
     bool odd_ok = false;                      // 3x3 stride-2 layer that takes odd input sizes (vfi_conv_accept_odd)
     bool huge_ok = false;                     // operand images of 4 GiB and more are served where a LARGE kernel form exists (vfi_conv_allow_huge)
+    bool res_prelu_ok = false;                // residual + per-channel PReLU may take its LARGE form (vfi_conv_allow_large_res_prelu)
     int cin_src = 0;                          // 4x4 stride-2 layer (kh == 4): channels of the caller's input window; Cin_p = 4 * cin_src is the
                                               //   space-to-depth image's (s2d_pad1_kernel), over which the layer is a 2x2 stride-1 one (taps == 4)
 };
@@ -494,6 +495,12 @@ int vfi_conv_allow_huge(vfi_conv_t* c, int on) {
     return 0;
 }
 
+int vfi_conv_allow_large_res_prelu(vfi_conv_t* c, int on) {
+    VFI_REQUIRE(c, "vfi_conv_allow_large_res_prelu: null handle");
+    c->res_prelu_ok = on != 0;
+    return 0;
+}
+
 int64_t vfi_conv_huge_max_floats(void) { return kConvHugeMaxFloats; }
 
 int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs, int N,
@@ -530,6 +537,7 @@ int vfi_conv_forward_ex(const vfi_conv_t* c, const float* in_dev, int in_cs, int
     a.slope = slope;
     a.split_ok = 1;
     a.huge_ok = c->huge_ok ? 1 : 0;
+    a.res_prelu_ok = c->res_prelu_ok ? 1 : 0;
     a.post_scale = post_scale;
     a.post_shift = post_shift;
     a.pad_mode = c->pad_mode;

@@ -155,9 +155,12 @@ struct ConvArgs {
     float post_scale, post_shift;  // y = act(...) * post_scale + post_shift  (post_scale == 0 means "not set" = 1, 0)
     int split_ok;          // caller: the launcher may cut K over several workgroups (split-K; generic layer objects only — the
                            //   RIFE network keeps one kernel per layer whatever the batch, so results do not depend on batching)
-    int huge_ok;           // host side only: the layer object's permission (vfi_conv_allow_huge) — the LARGE forms may serve operand images of 4 GiB
+    short huge_ok;         // host side only: the layer object's permission (vfi_conv_allow_huge) — the LARGE forms may serve operand images of 4 GiB
                            //   and more, up to kConvHugeMaxFloats floats (conv_large.h); 0 = refused from 4 GiB on.  It sits in the four bytes of
                            //   padding in front of the pointer below, so that no kernel argument moved when it was added (static_assert below)
+    short res_prelu_ok;    // host side only, the other half of those four bytes: the layer object's permission vfi_conv_allow_large_res_prelu — a 3x3
+                           //   stride-1 layer with a residual and per-channel PReLU (act 3) may take its LARGE form; 0 = it keeps the plain form and
+                           //   its 2 GiB refusal
     const unsigned char* tapmask;  // 2x2 layers in the "up-sample x2 first" form (conv_mfma2.hip, MASKED): per 64-channel N block the taps (bit a * 2 + b) of
     int par_cout;                  //   its parity; par_cout = channels per parity group (4 groups: Cout_p == 4 * par_cout), output [2 Hout, 2 Wout] interleaved
     int ksplit;            // set by the launcher: > 1 = split-K launch, blockIdx.z owns a K range and the slice
@@ -169,7 +172,7 @@ struct ConvArgs {
     int wino_gray;         //   1: the four parity groups of such a layer are packed in the order p00 p01 p11 p10 (wino_gray_order)
 };
 
-static_assert(sizeof(ConvArgs) == 208 && offsetof(ConvArgs, tapmask) == 160 && offsetof(ConvArgs, huge_ok) == 156, "ConvArgs: the kernels' argument offsets are part of their code");
+static_assert(sizeof(ConvArgs) == 208 && offsetof(ConvArgs, tapmask) == 160 && offsetof(ConvArgs, huge_ok) == 156 && offsetof(ConvArgs, res_prelu_ok) == 158, "ConvArgs: the kernels' argument offsets are part of their code");
 
 struct ConvVariant {
     const char* name;
@@ -235,7 +238,9 @@ bool conv_wino_eligible(const ConvArgs& a);
 // all three.
 inline bool conv_bytes_large(long bytes) { return bytes >= option(kOptLargeBytes); }
 inline bool conv_input_large(const ConvArgs& a) { return conv_bytes_large((long)a.Hin * a.Win * a.in_cs * 4); }
-int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal
+int conv_wino_mode(int set);      // set < 0: query.  0 automatic, 1 direct kernel only, 2 Winograd wherever legal, 3 as 2 with 32x4 regions wherever the
+                                  //   launcher would pick the region shape.  Process state that only the test hook vfi_test_conv_algo sets (the product library has no
+                                  //   setter, so it stays 0 there); conv_wino_eligible and conv_wino_launch read it on every launch, one relaxed atomic load
 // A layer call that computes a horizontal BAND of a frame (csrc/sepconv_net.hip) must take the kernel and the tile the whole-frame call
 // would take, or the band's bits differ from the frame's (the two kernels sum in different orders): while rows > 0 on the calling thread,
 // conv_wino_eligible and conv_pick_variant size a stride-1 layer's choice by `rows` image rows instead of the call's own.  0 (default) = the

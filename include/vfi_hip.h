@@ -245,6 +245,14 @@ int vfi_conv_accept_odd(vfi_conv_t* conv, int on);
  * 2 GiB refusal. */
 int vfi_conv_allow_huge(vfi_conv_t* conv, int on);
 int64_t vfi_conv_huge_max_floats(void);
+/* One more layer form may be served above 2 GiB, and only by an object that was given this permission: Conv2d 3x3 stride 1 + residual +
+ * per-channel PReLU (act 3, zero padding, no post affine) — the last layer of AMT-G's ResBlock, prelu(conv5(x3) + r0), whose input is 2.92 GB
+ * at 2160 x 3840.  With it the Winograd kernel (both region shapes) and the direct kernel's 3x3 stride-1 tiles take their large-image forms
+ * under the conditions that hold for act 3 without a residual (operand images below 4 GiB, or vfi_conv_allow_huge's bound with that
+ * permission too); input, output and residual are each addressed from a per-region / per-tile 64-bit base.  Same arithmetic and summation
+ * order as the plain form: the same bits wherever both are legal.  Off by default, a property of the object: without it every call decides,
+ * launches and refuses ("image larger than 2 GiB") exactly as before. */
+int vfi_conv_allow_large_res_prelu(vfi_conv_t* conv, int on);
 int vfi_conv_forward_ex(const vfi_conv_t* conv, const float* in_dev, int in_cs, int Hin, int Win, float* out_dev, int out_cs,
                         int N, int act, float slope, float post_scale, float post_shift, const float* res_dev, int res_cs,
                         void* stream);
@@ -788,9 +796,19 @@ void vfi_amt_destroy(vfi_amt_t* net);
  * update blocks, multi_flow_combine, clamp, un-pad; a timestep's result does not depend on the others of its call.  No correlation volume is
  * built.  AMT-G (:1494-1581) adds update3_high / update2_high after the low blocks, at 1/4 and 1/2 resolution, on the same lookup output.
  * Frames whose padded side is below 128 (the reference is all-NaN there) or whose padded size exceeds 2^23 - 1 pixels (AMT-G: 6 100 805,
- * its widest activation has 88 floats per padded pixel) are refused before any launch. */
+ * its widest activation has 88 floats per padded pixel; 12 201 611 after vfi_amt_set_large_frames, below) are refused before any launch. */
 int vfi_amt_forward(vfi_amt_t* net, const float* frame0_dev, const float* frame1_dev, int C, int H, int W, const float* ts_host, int n_t,
                     float* out_dev, void* stream);
+/* Large frames.  on != 0 on an AMT-G object: it serves padded frames up to vfi_amt_large_max_padded_pixels(2) = (2^32 - 1) / 352 =
+ * 12 201 611 pixels (2160 x 3840 pads to 8 294 400), its widest buffer staying below 4 GiB: every layer that meets an image of 2 GiB or more
+ * has a large-image form (docs/design/amt.md "4K"), and the object's layers are given vfi_conv_allow_large_res_prelu for the one that needs
+ * it, the ResBlock's closing residual + PReLU.  0 (every object as created): 6 100 805 pixels, and the launches, refusals and bits of before.
+ * AMT-S and AMT-L: the switch changes nothing — vfi_amt_large_max_padded_pixels(0 / 1) is their 2^23 - 1, the call sets nothing on the object
+ * or its layers, and the forward issues the same launches.  vfi_amt_object_max_padded_pixels is the limit vfi_amt_forward applies to that
+ * object; vfi_amt_large_max_padded_pixels of an unknown variant is 0. */
+int vfi_amt_set_large_frames(vfi_amt_t* net, int on);
+int64_t vfi_amt_large_max_padded_pixels(int variant);
+int64_t vfi_amt_object_max_padded_pixels(const vfi_amt_t* net);
 int vfi_amt_release_workspace(vfi_amt_t* net);
 int64_t vfi_amt_workspace_bytes(const vfi_amt_t* net);
 

@@ -23,7 +23,8 @@ int vfi_conv3x3_naive(const float* in_dev, const float* weight_host, const float
 
 
 /* Algorithm choice of the 3x3 stride-1 layers (layer objects and the RIFE network): 0 automatic (Winograd where the launch has
- * enough work items), 1 direct implicit-GEMM kernel only, 2 Winograd wherever the shape allows; mode < 0 queries.  Returns the
+ * enough work items), 1 direct implicit-GEMM kernel only, 2 Winograd wherever the shape allows, 3 as 2 with 32x4 regions wherever the
+ * launcher picks the region shape itself (the region shape changes no bit); mode < 0 queries.  Returns the
  * mode in force.  Lets a test run BOTH forms of one layer / network on one input. */
 int vfi_test_conv_algo(int mode);
 
