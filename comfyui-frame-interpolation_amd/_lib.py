@@ -348,6 +348,10 @@ AMT_TEST_PROTOTYPES = {
 LARGE_TEST_PROTOTYPES = {
     "vfi_test_large_launches": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
 }
+# ... and include/vfi_hip_test_rife.h (RIFE's fused block 1->2 transition on caller buffers): test builds only
+RIFE_TEST_PROTOTYPES = {
+    "vfi_test_rife_trans2_conv0a": (C.c_int, _T + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+}
 
 
 # The runtime variables this package honours — all of them select resources or diagnostics, none changes a frame's values
@@ -402,6 +406,7 @@ def load():
         protos.update(ATM_TEST_PROTOTYPES)
         protos.update(LARGE_TEST_PROTOTYPES)
         protos.update(AMT_TEST_PROTOTYPES)
+        protos.update(RIFE_TEST_PROTOTYPES)
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

@@ -52,6 +52,7 @@ def _digest():
     files.append(os.path.join(PKG, "..", "include", "vfi_hip_test_atm.h"))
     files.append(os.path.join(PKG, "..", "include", "vfi_hip_test_large.h"))
     files.append(os.path.join(PKG, "..", "include", "vfi_hip_test_amt.h"))
+    files.append(os.path.join(PKG, "..", "include", "vfi_hip_test_rife.h"))
     for f in files:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode())  # names only: the checkout path differs on the GPU box

@@ -12,6 +12,7 @@
 
 #include "../../include/vfi_hip.h"
 #include "../../include/vfi_hip_test.h"
+#include "../../include/vfi_hip_test_rife.h"
 #include "rife_ops.h"
 
 using namespace vfi;
@@ -556,7 +557,12 @@ int vfi_rife_interpolate(vfi_rife_t* net, int B, const int* slot0, const int* sl
     // The last transition of the standard scale list (block scales 2 -> 1) can run fused into the next block's conv0.0
     // (trans1_conv0a_launch: X never goes to HBM; the flow then lives in the other of two buffers).  Option fuse0a = 0 turns it
     // off (A/B measurements); the debug taps need X and keep the un-fused path.
+    // The transition before it (4 -> 2) runs fused into block 2's conv0.0 the same way (trans2_conv0a_launch, option fuse0a2; the same
+    // bits as the two kernels it replaces, recorded under the trace name stage_trans2 with no conv0a_b2 entry).  Each fused launch reads
+    // the flow from Fcur and writes it to Falt, so the two in a row ping-pong: F -> F2 -> F.  Other architectures, other scale lists,
+    // 4.26's carried features and frames whose padded size is not a multiple of 32 x 64 keep the two kernels.
     const bool fuse0a_enabled = option(kOptFuse0a) != 0;
+    const bool fuse0a2_enabled = option(kOptFuse0a2) != 0;
     float* Fcur = net->F.p;
     float* Falt = net->F2.p;
     bool a0_ready = false;   // conv0.0 of this block has already been computed by the fused transition
@@ -650,8 +656,18 @@ int vfi_rife_interpolate(vfi_rife_t* net, int B, const int* slot0, const int* sl
             fused_prev = on_grid && (sn == 4 || sn == 2 || sn == 1 || (net->NX && sn == 8));
             const bool fuse0a = fuse0a_enabled && fused_prev && sn == 1 && net->NF == 1 && !net->NX && !net->keep && i > 0 &&
                                 net->CX(i + 1) == 24 && kBlockC[i + 1] == 64 && net->conv00[i + 1].Cout_p == 32;
+            const bool fuse0a2 = fuse0a2_enabled && fused_prev && sn == 2 && net->NF == 1 && !net->NX && !net->keep && i > 0 &&
+                                 net->CX(i + 1) == 24 && kBlockC[i + 1] == 96 && net->conv00[i + 1].Cout_p == 64 &&
+                                 trans2_conv0a_geometry_ok(Hp, Wp);
             if (fuse0a) {
                 if (trans1_conv0a_launch(net->Ppool.p, net->pack_stride(), tasks, B, Tsrc, Fcur, Falt, net->conv00[i + 1].w.p,
+                                         net->conv00[i + 1].bias.p, net->A0.p, Hp, Wp, 0.2f, st))
+                    return -1;
+                std::swap(Fcur, Falt);
+                fused_prev = false;
+                a0_ready = true;
+            } else if (fuse0a2) {
+                if (trans2_conv0a_launch(net->Ppool.p, net->pack_stride(), tasks, B, Tsrc, Fcur, Falt, net->conv00[i + 1].w.p,
                                          net->conv00[i + 1].bias.p, net->A0.p, Hp, Wp, 0.2f, st))
                     return -1;
                 std::swap(Fcur, Falt);
@@ -818,6 +834,33 @@ int vfi_test_rife_trans1_conv0a(const float* Ppool, int64_t pack_stride, const i
         rc = trans1_conv0a_launch(Ppool, (size_t)pack_stride, tasks, B, T, Fin, Fout, w.p, bias.p, A0, Hp, Wp, slope, (hipStream_t)stream);
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == 0) {
             set_error("vfi_test_rife_trans1_conv0a: the launch failed");
+            rc = -1;
+        }
+    }
+    w.release();
+    bias.release();
+    return rc;
+}
+
+// conv0.0 of block 2 as plain OIHW [48][20][3][3] + bias [48] on the HOST: packed here exactly as vfi_rife_create packs conv00[2]
+// (include/vfi_hip_test_rife.h).  Every argument is checked before anything is uploaded or launched.
+int vfi_test_rife_trans2_conv0a(const float* Ppool, int64_t pack_stride, const int* slot0, const int* slot1, const float* t, int B, const float* T,
+                                const float* Fin, float* Fout, const float* w_oihw_host, const float* bias_host, float* A0, int Hp, int Wp, float slope,
+                                void* stream) {
+    RifeTasks tasks;
+    if (int rc = stage_geo(B, Hp, Wp, "vfi_test_rife_trans2_conv0a")) return rc;
+    if (int rc = stage_tasks(tasks, slot0, slot1, t, B, "vfi_test_rife_trans2_conv0a")) return rc;
+    VFI_REQUIRE(Ppool && T && Fin && Fout && Fin != Fout && A0 && w_oihw_host && bias_host && pack_stride >= (int64_t)Hp * Wp * 8,
+                "vfi_test_rife_trans2_conv0a: bad operands (stride %lld)", (long long)pack_stride);
+    VFI_REQUIRE(trans2_conv0a_geometry_ok(Hp, Wp) && slope >= 0.f && slope <= 1.f, "vfi_test_rife_trans2_conv0a: bad geometry %dx%d / slope %g", Hp, Wp, slope);
+    std::vector<float> wp, bp;
+    pack_conv3x3(w_oihw_host, bias_host, 48, 20, 24, 64, wp, bp);
+    DevBuf w, bias;
+    int rc = -1;
+    if (!upload(w, wp) && !upload(bias, bp)) {
+        rc = trans2_conv0a_launch(Ppool, (size_t)pack_stride, tasks, B, T, Fin, Fout, w.p, bias.p, A0, Hp, Wp, slope, (hipStream_t)stream);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == 0) {
+            set_error("vfi_test_rife_trans2_conv0a: the launch failed");
             rc = -1;
         }
     }

@@ -43,6 +43,12 @@ int stage_trans_launch(const float* Ppool, size_t pack_stride, const RifeTasks& 
 // reads Fin, writes the updated flow to Fout (a different buffer) and conv0.0's output A0 [B][Hp/2][Wp/2][32]; X is never stored
 int trans1_conv0a_launch(const float* Ppool, size_t pack_stride, const RifeTasks& tasks, int B, const float* T, const float* Fin,
                          float* Fout, const float* wpk, const float* bias, float* A0, int Hp, int Wp, float slope, hipStream_t st);
+// the transition before it (scales 4 -> 2, NF = 1) fused into block 2's conv0.0 (24 -> 48 channels of 64 packed, stride 2, LeakyReLU):
+// reads Fin, writes the updated flow to Fout (a different buffer) and A0 [B][Hp/4][Wp/4][48]; same bits as stage_trans_launch (quad
+// kernel) + the d2_m1n2_live4 tile.  Hp % 32 == 0 and Wp % 64 == 0 (trans2_conv0a_geometry_ok); trace name "stage_trans2"
+bool trans2_conv0a_geometry_ok(int Hp, int Wp);
+int trans2_conv0a_launch(const float* Ppool, size_t pack_stride, const RifeTasks& tasks, int B, const float* T, const float* Fin,
+                         float* Fout, const float* wpk, const float* bias, float* A0, int Hp, int Wp, float slope, hipStream_t st);
 // arch 4.26 (T with 4 planes, 8 carried feature channels, NF = 1); block scales 2*s_next -> s_next, s_next in {8,4,2,1}
 int stage_trans_x_launch(const float* Ppool, size_t pack_stride, const RifeTasks& tasks, int B, const float* T, float* F,
                          float* X, int Hp, int Wp, int s_prev, int s_next, bool has_prev, hipStream_t st);

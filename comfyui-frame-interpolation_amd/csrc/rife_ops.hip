@@ -1406,6 +1406,206 @@ int trans1_conv0a_launch(const float* Ppool, size_t pack_stride, const RifeTasks
 }
 
 // ---------------------------------------------------------------------------------------
+// The transition before it (block scales 4 -> 2) FUSED INTO block 2's conv0.0 (3x3, stride 2, 20 -> 48 channels, LeakyReLU 0.2), the
+// same way: the un-fused pair writes X as 24 channels at Hp/2 x Wp/2 and the convolution (conv_mfma2.hip, tile d2_m1n2_live4) reads it
+// back once.  A workgroup owns a 16x8 tile of the convolution's output (Hp/4 x Wp/4) and builds the 33x17 patch of X it needs in LDS.
+//   * phase A: a QUAD of lanes is one X pixel, its lanes the pixel's 2x2 full-resolution centre pixels — stage_trans_quad_kernel<2, true, 1, 0>
+//     for that cell, statement for statement (same helpers, same DPP mean); 561 pixels = 5 rounds of 128 quads.  The flow goes from Fin
+//     to Fout for the 32x64 full-resolution pixels the tile owns (the halo row / column belongs to the neighbours).
+//   * phase B: wave w multiplies sub-tile (w & 3) against N block (w >> 2) over the WHOLE K, in the K order of the tile it replaces:
+//     channel chunks 0 and 1 (taps 0..8, 4 MFMAs each: lane half h supplies channel 8 chunk + 4 h + j), then the live half chunk
+//     (taps 0..8, 2 MFMAs each: (16|17), (18|19)) — 90 MFMAs from +0, no partial sums to add, hence the same bits.
+//   * weights in LDS: the 48 real output channels only, the third chunk as its 4 live floats: [tap][ 2 x [48][8] | [48][4] ] = 34.6 KB
+//     next to the patch's 44.9 KB, so that two workgroups share a CU.  The lanes of N block 1 that stand for the padded channels
+//     48..63 read rows 32..47 again; their columns are never stored.
+// Every tile is interior (Hp % 32 == 0, Wp % 64 == 0): the epilogue is the fast path of conv_mfma2_kernel.
+// ---------------------------------------------------------------------------------------
+constexpr int F2_CO = 48;                                 // stored output channels
+constexpr int F2_WT = 2 * F2_CO * 8 + F2_CO * 4;          // floats of one tap's weights (960)
+constexpr int F2_WF = 9 * F2_WT;
+constexpr int F2_LDS = (F0_XF + F2_WF) * 4;               // 79 440 B
+constexpr int F2_LDS_ONE = 100 * 1024;                    // option fuse0a2 = 2: asked for, not used — one workgroup per CU (the A/B of the residency)
+
+__global__ __launch_bounds__(F0_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void trans2_conv0a_kernel(const float* __restrict__ Ppool, size_t pack_stride, RifeTasks tasks,
+                                                                   const float* __restrict__ T, const float* __restrict__ Fin,
+                                                                   float* __restrict__ Fout, const float* __restrict__ wpk,
+                                                                   const float* __restrict__ bias, float* __restrict__ A0, int Hp,
+                                                                   int Wp, int n_tiles, int tiles_x, int tiles_y, float slope) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // F0_XF floats of patch, then F2_WF floats of weights
+    float* wl = lds + F0_XF;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ql = tid & 3;
+    const int half = lane >> 5, l31 = lane & 31;
+    const int Hs = Hp / 2, Ws = Wp / 2;          // X
+    const int Ho = Hp / 4, Wo = Wp / 4;          // the convolution's output = resolution of the pixel-shuffled T of the scale-4 block
+    const int Hi = Ho, Wi = Wo;
+    // once per persistent workgroup: [tap][Cin/8][64][8] -> the compact image
+    for (int i = tid; i < F2_WF / 4; i += F0_THREADS) {
+        const int t = i / (F2_WT / 4), r = i - t * (F2_WT / 4);
+        const int c8 = r < 4 * F2_CO ? r / (2 * F2_CO) : 2;
+        const int src = r < 4 * F2_CO ? ((t * 3 + c8) * 64) * 2 + (r - c8 * 2 * F2_CO) : ((t * 3 + 2) * 64 + (r - 4 * F2_CO)) * 2;
+        ((float4*)wl)[i] = ((const float4*)wpk)[src];
+    }
+    const int sub = wave & 3, nb = wave >> 2;
+    const int sx = sub & 1, sy = sub >> 1;
+    const int co = nb * 32 + l31;
+    const int row = co < F2_CO ? co : co - 16;
+    const float bs = bias[co];
+    const int oyl = sy * 4 + (l31 >> 3), oxl = sx * 8 + (l31 & 7);
+    const int abase = ((2 * oyl) * F0_TWI + 2 * oxl) * F0_S + half * 4;
+    const int bbase = row * 8 + half * 4;
+    const int tbase = 2 * F2_CO * 8 + row * 4 + half;
+    const size_t hi_off = (size_t)Hp * Wp * 4;
+    const WarpGeo g = make_warp_geo(Wp, Hp);
+    const int tiles_per_img = tiles_x * tiles_y;
+
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int b = tile / tiles_per_img;
+        const int trem = tile - b * tiles_per_img;
+        const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+        const int Y0 = ty * F0_THO, X0 = tx * F0_TWO;
+        const int yl0 = 2 * Y0 - 1, xl0 = 2 * X0 - 1;
+        const float* Tb = T + (size_t)b * Hi * Wi * 8;
+        const float* P0 = Ppool + (size_t)tasks.slot0[b] * pack_stride;
+        const float* P1 = Ppool + (size_t)tasks.slot1[b] * pack_stride;
+        const float tstep = tasks.t[b];
+        // ---- phase A: the X patch, one quad per pixel (priority: see trans1_conv0a_kernel)
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll 1
+        for (int it = 0; it < (F0_NPIX + F0_THREADS / 4 - 1) / (F0_THREADS / 4); ++it) {
+            const int p = (tid >> 2) + (F0_THREADS / 4) * it;
+            if (p >= F0_NPIX) break;      // whole quads leave together
+            const int py = p / F0_TWI, px = p - py * F0_TWI;
+            const int yl = yl0 + py, xl = xl0 + px;
+            float r[20];
+#pragma unroll
+            for (int c = 0; c < 20; ++c) r[c] = 0.f;
+            if (yl >= 0 && xl >= 0 && yl < Hs && xl < Ws) {
+                const int X = xl * 2 + (ql & 1), Y = yl * 2 + (ql >> 1);
+                float v[5];
+                t_upsample_quad<0, true>(Tb, Hi, Wi, 1.0f / 4.0f, Y, X, ql, v);
+                const size_t pb = (size_t)b * Hp * Wp + (size_t)Y * Wp + X;
+                const float fs = 4.0f;
+                float4 f = make_float4(v[0] * fs, v[1] * fs, v[2] * fs, v[3] * fs);
+                const float4 o = ((const float4*)Fin)[pb];
+                f = make_float4(o.x + f.x, o.y + f.y, o.z + f.z, o.w + f.w);
+                if (py >= 1 && px >= 1) ((float4*)Fout)[pb] = f;        // this tile owns rows 4*Y0.. and columns 4*X0..
+                const Tap4 t0 = warp_taps(g, X, Y, f.x, f.y);
+                const Tap4 t1 = warp_taps(g, X, Y, f.z, f.w);
+                float4 a_lo, b_lo, a_hi[1], b_hi[1];
+                sample_pack<1>(P0, hi_off, t0, a_lo, a_hi);
+                sample_pack<1>(P1, hi_off, t1, b_lo, b_hi);
+                cat_inputs<1>(r, a_lo, b_lo, a_hi, b_hi, tstep);
+                r[15] = v[4];
+                r[16] = f.x; r[17] = f.y; r[18] = f.z; r[19] = f.w;
+#pragma unroll
+                for (int c = 0; c < 20; ++c) {   // 0.5*left + 0.5*right, then 0.5*top + 0.5*bottom (all four lanes get the result)
+                    const float rw = __fadd_rn(0.5f * r[c], 0.5f * quad_f<0xB1>(r[c]));
+                    r[c] = __fadd_rn(0.5f * rw, 0.5f * quad_f<0x4E>(rw));
+                }
+                const float inv_s = 1.0f / 2.0f;
+#pragma unroll
+                for (int c = 16; c < 20; ++c) r[c] = r[c] * inv_s;  // interpolate(flow) * 1.0 / scale
+            }
+            // lane ql of the quad stores channels 4 ql .. 4 ql + 3, lane 0 the flow as well
+            float4 val = make_float4(r[0], r[1], r[2], r[3]);
+#pragma unroll
+            for (int j = 1; j < 4; ++j)
+                if (ql == j) val = make_float4(r[4 * j], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]);
+            float* d = &lds[p * F0_S];
+            *(float4*)(d + 4 * ql) = val;
+            if (ql == 0) *(float4*)(d + 16) = make_float4(r[16], r[17], r[18], r[19]);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        __syncthreads();
+        // ---- phase B: 32 output pixels x 32 channels per wave, K = 2 x 9 x 8 + 9 x 4
+        f32x16_t acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        {
+            // one opaque byte base per operand + compile-time offsets, as in trans1_conv0a_kernel
+            int ab = abase * 4, bb = bbase * 4, tb = tbase * 4;
+            asm volatile("" : "+v"(ab), "+v"(bb), "+v"(tb));
+            const char* const ap = (const char*)lds + ab;
+            const char* const bp = (const char*)wl + bb;
+            const char* const ap1 = ap - half * 12;      // the half's 4-float step taken back to 1
+            const char* const bp1 = (const char*)wl + tb;
+#pragma unroll
+            for (int st = 0; st < 18; ++st) {
+                const int c8 = st / 9, t = st - 9 * c8;
+                const int toff = ((t / 3) * F0_TWI + (t % 3)) * F0_S;
+                const f32x4_t av = *(const f32x4_t*)(ap + (toff + c8 * 8) * 4);
+                const f32x4_t bv = *(const f32x4_t*)(bp + (t * F2_WT + c8 * F2_CO * 8) * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
+                if (st & 1) __builtin_amdgcn_sched_barrier(0);    // at most two steps' fragments in flight
+            }
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int toff = ((t / 3) * F0_TWI + (t % 3)) * F0_S;
+                const float a0 = *(const float*)(ap1 + (toff + 16) * 4), a1 = *(const float*)(ap1 + (toff + 18) * 4);
+                const float b0 = *(const float*)(bp1 + t * F2_WT * 4), b1 = *(const float*)(bp1 + t * F2_WT * 4 + 8);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
+                if (t & 1) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // ---- epilogue: + bias, LeakyReLU, NHWC store with channel stride 48 (the padded channels 48..63 are not stored)
+        if (co < F2_CO) {
+            int ot = tid;                     // lane part of the store address re-derived here (trans1_conv0a_kernel)
+            asm volatile("" : "+v"(ot));
+            const int oy0 = Y0 + sy * 4, ox0 = X0 + sx * 8 + 4 * ((ot >> 5) & 1);
+            float* ob = A0 + ((size_t)((size_t)b * Ho + oy0) * Wo + ox0) * F2_CO + nb * 32 + (ot & 31);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float v = acc[i] + bs;
+                ob[((size_t)(i >> 2) * Wo + (i & 3)) * F2_CO] = fmaxf(v, v * slope);
+            }
+        }
+        __syncthreads();   // the patch is consumed; the next tile may overwrite it
+    }
+#endif
+}
+
+// Geometry the fused 4 -> 2 transition serves; checked by the caller that chooses it (rife_net.hip) and again by the launch.
+bool trans2_conv0a_geometry_ok(int Hp, int Wp) { return Hp > 0 && Wp > 0 && Hp % 32 == 0 && Wp % 64 == 0; }
+
+int trans2_conv0a_launch(const float* Ppool, size_t pack_stride, const RifeTasks& tasks, int B, const float* T, const float* Fin,
+                         float* Fout, const float* wpk, const float* bias, float* A0, int Hp, int Wp, float slope, hipStream_t st) {
+    VFI_REQUIRE(B >= 1 && B <= kMaxTasks, "trans2_conv0a: batch %d outside 1..%d", B, kMaxTasks);
+    VFI_REQUIRE(trans2_conv0a_geometry_ok(Hp, Wp) && slope >= 0.f && slope <= 1.f, "trans2_conv0a: bad geometry %dx%d / slope %g", Hp, Wp, slope);
+    const int tiles_x = (Wp / 4) / F0_TWO, tiles_y = (Hp / 4) / F0_THO;
+    const long long n_tiles_ll = (long long)B * tiles_x * tiles_y;
+    VFI_REQUIRE(n_tiles_ll <= 0x7fffffffLL, "trans2_conv0a: %lld tiles", n_tiles_ll);
+    const int n_tiles = (int)n_tiles_ll;
+    static std::atomic<int> cus_of[kMaxDevices];
+    int dev = 0;
+    VFI_CHECK_HIP(hipGetDevice(&dev));
+    VFI_REQUIRE(dev >= 0 && dev < kMaxDevices, "trans2_conv0a: device index %d out of range", dev);
+    int cus = cus_of[dev].load(std::memory_order_relaxed);
+    if (!cus) {
+        hipDeviceProp_t p;
+        VFI_CHECK_HIP(hipGetDeviceProperties(&p, dev));
+        cus = p.multiProcessorCount;
+        cus_of[dev].store(cus, std::memory_order_relaxed);
+    }
+    // 77.6 KB of LDS and 512 threads: two workgroups per CU.  Option fuse0a2 = 2 asks for 100 KB, which leaves room for one: the
+    // residency A/B of docs/design/rife_trans2_conv0a.md
+    const bool one = option(kOptFuse0a2) == 2;
+    static std::atomic<bool> attr_set[kMaxDevices];
+    if (!attr_set[dev].load(std::memory_order_acquire)) {
+        VFI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trans2_conv0a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS_ONE));
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    const int grid = std::min(n_tiles, (one ? 1 : 2) * launch_cus(cus));
+    TraceScope ts("stage_trans2", st);      // the name bench.py prices this transition under; no conv0a_b2 entry follows
+    hipLaunchKernelGGL(trans2_conv0a_kernel, dim3(grid), dim3(F0_THREADS), one ? F2_LDS_ONE : F2_LDS, st, Ppool, pack_stride, tasks, T, Fin, Fout, wpk, bias, A0,
+                       Hp, Wp, n_tiles, tiles_x, tiles_y, slope);
+    VFI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // fused block transition for arch 4.26: as stage_trans_kernel, plus the 8 feature channels the block returns
 // (T planes 1..3 = mask, g0..g7) which the next block takes un-warped, between mask and flow (rife_arch.py:555-583).
 // Block scales 2*SP -> SP with SP in {8, 4, 2, 1} (the first transition of 4.26 is 16 -> 8).

@@ -35,6 +35,7 @@ static const struct { const char* name; long dflt; } kOptTable[kOptCount] = {
     {"sepconv_split_heads", 0}, {"sepconv_planar", 1}, {"stage0", 1}, {"att_ksplit", 0}, {"wino_dead", 1},
     {"large_image_bytes", 0x7fffffffL},
     {"sepconv_band_rows", 0},
+    {"fuse0a2", 1},
 };
 static std::atomic<long> g_opt[kOptCount];
 static std::atomic<bool> g_opt_init{false};

@@ -84,6 +84,7 @@ enum Option {
     kOptWinoDead,           // 1: the Winograd kernel skips the transform planes a transposed-convolution layer's weights leave zero (ConvArgs::wino_dead; default), 0: all 16 planes: same bits
     kOptLargeBytes,         // bytes of one image from which a layer object's operand counts as large and the launch takes the per-tile / per-region descriptors (conv_mfma2.hip, conv_wino.hip: LARGE); default 2^31 - 1, lower values put small images on that path: same bits
     kOptSepconvBandRows,    // SepConv++'s head stage: 0 = automatic (whole frame up to 2 097 151 padded pixels, bands of the default height above, csrc/sepconv_bands.h), n > 0 = bands of n rows at any frame size: same bits
+    kOptFuse0a2,            // 1: RIFE's block 1->2 transition fused with block 2's conv0.0 (rife_ops.hip: trans2_conv0a_kernel; default), 0: stage_trans2 + conv0a_b2 as two kernels, 2: fused with one workgroup per CU instead of two: same bits
     kOptCount
 };
 long option(Option o);

@@ -2,7 +2,9 @@
 (include/vfi_hip_test.h: vfi_test_variant_override) — per-kernel HIP-event milliseconds for each override set.
     python tools/rife_variant_ab.py "conv0b_b3=40" "conv0b_b3=40,conv0b_b2=40" ...
 A spec "opt:NAME=VALUE" sets a library A/B option instead (it stays set for the specs after it), e.g. the forms the live-K kernels
-replace: "conv0a_b1=39,conv0a_b2=39" (plain stride-2 tile), "opt:fuse0a=2" (trans1_conv0a with all 24 input channels multiplied)."""
+replace: "conv0a_b1=39,conv0a_b2=39" (plain stride-2 tile), "opt:fuse0a=2" (trans1_conv0a with all 24 input channels multiplied),
+"opt:fuse0a2=0" (block 1->2 transition and block 2's conv0.0 as two kernels; 2 = fused with one workgroup per CU).  With fuse0a2 on
+(the default) the fused launch is the stage_trans2 entry and there is no conv0a_b2 entry: names a step did not record are left out."""
 import os
 import sys
 
